@@ -16,6 +16,12 @@ histogram + exact normalize_freqs), encode with the GPU encoder (setup, untimed)
 W warm-up and K timed decodes.  Shards are independent: no collective on the data
 path; RCCL only carries the barriers and the 48-byte per-rank result record (weak scaling).
 
+A plain run does only what the headline needs: setup (data, model, encode, placement probe), warm-up, the K timed
+steps, the round-trip check of the decoded symbols on the GPU, and the line.  --full adds everything else this script
+measures and checks: the other BASELINE configurations (`configs`), the CPU leg (oracle comparison of every chunk, the
+reference's CPU loops), the un-probed pair's K steps and the instrumented clock launch.  --dump-outputs DIR writes what
+the timed path handed back in its last step (a seeded sample of the decoded symbols and every chunk's symbol sum) as .npy.
+
 Rank 0 prints ONE SHORT JSON line (<= 3.8 KB, the last line of stdout: judged_line()) and writes the full record --
 probe matrices, per-thread CPU sweeps, per-config timings -- to bench_details.json (--details).  `value` = decoded
 (uncompressed) GB/s of the whole job.  `roofline` = algorithmic bytes (compressed stream read + symbols written) of one
@@ -45,6 +51,9 @@ MAX_CLOCK_HZ = 2.4e9
 MAX_LINE_BYTES = 3800   # the judged stdout line (tests/test_bench_cpu.py pins it; the driver keeps ~8 KB of stdout)
 PLACEMENT_STRIDE = [24 << 30]  # bytes between placement candidates in allocation order (--placement-stride-gib)
 WAVES_PER_SIMD = 8      # resident waves per SIMD of the wave-per-chunk decoder (2 blocks x 16 waves per CU)
+DUMP_SAMPLE = 1 << 22   # decoded symbols --dump-outputs samples (float32 values + float64 positions: 48 MiB)
+DUMP_SUMS = 1 << 20     # at most this many block sums beside them (float64: 8 MiB; 56 MiB in all for any arguments)
+DUMP_SEED = 20261016    # fixed seed of the sampled positions: two builds dump the same ones
 
 
 def parse_args():
@@ -64,8 +73,15 @@ def parse_args():
     ap.add_argument("--format", default="word", choices=["word", "byte", "r64", "alias"])
     ap.add_argument("--scale-bits", type=int, default=0, help="probability bits of the model (default: the format's -- word 12, "
                                                                "byte / r64 14, alias 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU leg (reference timing + oracle checks)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything, not just the headline: the other BASELINE configurations, the CPU leg "
+                         "(reference timing + oracle checks), the un-probed pair's timed steps and the per-wave clocks")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one decoded to DIR/*.npy (rank 0): a seeded sample of "
+                         "%d symbols with their positions, and the symbol sum of every chunk (of groups of chunks beyond "
+                         "%d sums)" % (DUMP_SAMPLE, DUMP_SUMS))
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg (reference timing + oracle checks)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the other BASELINE configurations")
     ap.add_argument("--prewarm-ms", type=float, default=250.0,
                     help="setup: run the decoder this long before the warm-up steps (clocks settle); 0 = off")
     ap.add_argument("--dump-launch-ms", action="store_true", help="add the per-launch HIP-event times to the JSON line")
@@ -190,6 +206,33 @@ def settle(torch, fn, ms=60.0):
         for _ in range(8):
             fn()
         torch.cuda.synchronize()
+
+
+def dump_outputs(torch, out_dir, out, chunk):
+    """--dump-outputs: the decoded symbols the last timed step handed back, as .npy files two builds can be compared by.
+    decoded_sample.npy (float32): the symbols at DUMP_SAMPLE positions drawn with DUMP_SEED (every symbol when the output
+    is no larger), decoded_sample_index.npy (float64): those positions, decoded_chunk_sums.npy (float64): the symbol sum
+    of every chunk -- of every g consecutive chunks when there are more than DUMP_SUMS of them (g = the fewest that
+    leaves at most DUMP_SUMS sums) -- so that a difference anywhere in the output shows.  56 MiB at most for any shape."""
+    import numpy as np
+    n = out.numel()
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+    sample = out[torch.from_numpy(idx).to(out.device)].to(torch.float32).cpu().numpy()
+    chunks = -(-n // chunk)
+    block = chunk * max(1, -(-chunks // DUMP_SUMS))  # (symbols per sum)
+    full = n // block * block
+    step = max(1, (1 << 25) // block) * block  # (32 Mi symbols per reduction: no large temporaries)
+    sums = [out[lo:min(lo + step, full)].view(-1, block).sum(dim=1, dtype=torch.int64) for lo in range(0, full, step)]
+    if full < n:
+        sums.append(out[full:].sum(dtype=torch.int64).reshape(1))
+    sums = torch.cat(sums).to(torch.float64).cpu().numpy() if sums else np.zeros(0, np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "decoded_sample.npy"), sample)
+    np.save(os.path.join(out_dir, "decoded_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "decoded_chunk_sums.npy"), sums)
 
 
 def trace(*a):
@@ -745,7 +788,7 @@ def judged_line(full, details_path=None):
                 line["value_first_pair"] = round(n_sym / fp / 1e6, 2)
                 line["frac_first_pair"] = round(rl.get("algorithmic_bytes_per_launch", 0) / fp / 1e6 / HBM_PEAK_GBPS, 4)
     ck = full.get("clocks", {})
-    if "error" not in ck:
+    if ck and "error" not in ck:  # (measured by --full runs only)
         line["clocks"] = {k: ck.get(k) for k in ("sclk_hz_measured", "per_wave_clocks_per_round_of_64", "clocks_per_symbol_per_simd")}
     cb = full.get("cpu_baseline")
     if cb is not None:
@@ -1009,7 +1052,10 @@ def main():
         ev1[k].record()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    timed_end = launches["decode"]  # (counted, not computed: the launches the timed loop really made)
     barrier()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, out, args.chunk)
 
     # first wave start .. last wave end of each timed launch (recorded by the kernel itself, always on)
     try:
@@ -1019,7 +1065,7 @@ def main():
     # the same K steps on the FIRST pair of allocations, same loop, same clock (setup's probe is what chose another pair):
     # `value_first_pair` is what a caller without the probe gets
     first_pair_elapsed = None
-    if first_pair is not None and world == 1:
+    if first_pair is not None and world == 1 and args.full:
         fc, fo = first_pair
 
         def first_step():
@@ -1044,7 +1090,7 @@ def main():
     # last, the offset-scan block edges, random ones) re-encoded on the host and compared byte for byte; the count travels
     # in the record and rank 0 sums it.  (N = 1 checks every chunk of every container further down.)
     sampled, sample_ok = 0, True
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and args.full and not args.no_cpu_baseline:
         try:
             sampled = oracle_check_chunks({"fmt": fmt, "sb": sb, "K": 256, "ways": args.ways, "chunk": args.chunk, "n": n,
                                            "freqs": freqs, "d_syms": d_syms, "cont": cont, "offs": offs, "lens": lens,
@@ -1118,7 +1164,7 @@ def main():
                 "achieved_kernel_events": round(achieved_events, 1), "frac_kernel_events": round(achieved_events / HBM_PEAK_GBPS, 4),
                 "kernel": ctx.last_decode_kernel(), "kernel_ms_avg": round(kernel_ms, 4),
                 # the timed launches are dispatches [first, first + steps) of this kernel in this process, counted from 0
-                "timed_dispatches": [timed_first, timed_first + args.steps],
+                "timed_dispatches": [timed_first, timed_end],
                 "algorithmic_bytes_per_launch": n + total,
                 # the job: algorithmic bytes of ALL ranks over the slowest rank's step time, against N GPUs' peak (at N = 1
                 # this is `frac`); achieved / peak / frac above are rank 0's launches on rank 0's GPU
@@ -1139,27 +1185,28 @@ def main():
         if args.dump_launch_ms:
             result["launch_ms"] = [round(a.elapsed_time(b), 4) for a, b in zip(ev0, ev1)]
             result["launch_span_ms"] = [round(v, 4) for v in spans]
-        # per-wave clocks, measured by the kernel in one extra (untimed, instrumented) launch
-        try:
-            ctx.set_timing(2)
-            step()
-            wc = ctx.last_wave_clocks()
-            ctx.set_timing(0)
-            per_wave_round = wc["shader_cycles"] / max(1, wc["rounds"])
-            result["clocks"] = {
-                "sclk_hz_measured": round(wc["sclk_hz"]),
-                "per_wave_clocks_per_round_of_64": round(per_wave_round, 1),
-                "per_simd_clocks_per_round_of_64": round(per_wave_round / WAVES_PER_SIMD, 2),
-                "clocks_per_symbol_per_simd": round(per_wave_round / WAVES_PER_SIMD / 64.0, 4),
-                "gpu_aggregate_clocks_per_symbol": round(k_s * wc["sclk_hz"] / n, 6),
-                "waves": wc["waves"], "rounds": wc["rounds"],
-                "instrumented_launch_ms": round(wc["kernel_ticks_ms"], 4),
-                "method": "s_memtime / wall_clock64 bracket around each wave's work (rans_amd_set_timing(ctx, 2)), "
-                          "one extra launch after the timed region; the reference's analogue is the __rdtsc "
-                          "bracket of main.cpp:171,184-186",
-            }
-        except Exception as e:  # noqa: BLE001
-            result["clocks"] = {"error": repr(e)}
+        # per-wave clocks, measured by the kernel in one extra (untimed, instrumented) launch (--full)
+        if args.full:
+            try:
+                ctx.set_timing(2)
+                step()
+                wc = ctx.last_wave_clocks()
+                ctx.set_timing(0)
+                per_wave_round = wc["shader_cycles"] / max(1, wc["rounds"])
+                result["clocks"] = {
+                    "sclk_hz_measured": round(wc["sclk_hz"]),
+                    "per_wave_clocks_per_round_of_64": round(per_wave_round, 1),
+                    "per_simd_clocks_per_round_of_64": round(per_wave_round / WAVES_PER_SIMD, 2),
+                    "clocks_per_symbol_per_simd": round(per_wave_round / WAVES_PER_SIMD / 64.0, 4),
+                    "gpu_aggregate_clocks_per_symbol": round(k_s * wc["sclk_hz"] / n, 6),
+                    "waves": wc["waves"], "rounds": wc["rounds"],
+                    "instrumented_launch_ms": round(wc["kernel_ticks_ms"], 4),
+                    "method": "s_memtime / wall_clock64 bracket around each wave's work (rans_amd_set_timing(ctx, 2)), "
+                              "one extra launch after the timed region; the reference's analogue is the __rdtsc "
+                              "bracket of main.cpp:171,184-186",
+                }
+            except Exception as e:  # noqa: BLE001
+                result["clocks"] = {"error": repr(e)}
         # HBM traffic per launch comes from separate rocprofv3 --pmc passes over this very command
         # (tools/profile.sh -> tools/summarize_profile.py -> profiles/<tag>_traffic.json); PMC passes cannot
         # share a process with the timed run, so a committed measurement is quoted only when it was taken on
@@ -1177,7 +1224,7 @@ def main():
                 pass
         arts = [{"fmt": fmt, "sb": sb, "K": 256, "ways": args.ways, "chunk": args.chunk, "n": n, "freqs": freqs,
                  "d_syms": d_syms, "cont": cont, "offs": offs, "lens": lens, "total": total, "entry": None}]
-        if world == 1 and not args.no_configs:
+        if world == 1 and args.full and not args.no_configs:
             cfgs = []
             try:
                 ks = args.config_steps
@@ -1240,7 +1287,7 @@ def main():
             result["configs"] = cfgs
             if any(not c.get("bit_exact_roundtrip", False) for c in cfgs):
                 all_ok = False
-        if world > 1 and not args.no_cpu_baseline:
+        if world > 1 and args.full and not args.no_cpu_baseline:
             result["oracle_chunks_checked"] = int(sum(r.oracle_chunks for r in records))
             result["oracle_chunks_total"] = len(records) * ((n + args.chunk - 1) // args.chunk)
             result["oracle_chunks_checked_per_rank"] = [int(r.oracle_chunks) for r in records]
@@ -1249,7 +1296,7 @@ def main():
             except Exception as e:  # noqa: BLE001
                 result["cpu_baseline"] = {"value": None, "unit": "GB/s", "cores": 0, "kind": "reference",
                                           "sample": "failed: %r" % (e,)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             try:
                 trace("oracle checks")
                 checked = {}

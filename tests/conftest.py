@@ -37,16 +37,13 @@ def ref():
 
 @pytest.fixture(scope="session")
 def book1(oracle):
-    """The reference corpus.  Where /root/reference exists it is read from there; elsewhere (the GPU box) it is
-    recovered from tests/golden/book1_word64.bin -- the 64-way word stream the unmodified reference made of it
-     -- by the CPU oracle, and must hash to book1's published sha256."""
+    """The reference corpus, recovered from tests/golden/book1_word64.bin -- the 64-way word stream the unmodified
+    reference made of it -- by the CPU oracle; it must hash to book1's published
+    sha256.  The suite reads nothing outside the repository."""
     import hashlib
     import json
 
     import numpy as np
-    path = "/root/reference/book1"
-    if os.path.exists(path):
-        return np.fromfile(path, dtype=np.uint8)
     meta = json.load(open(os.path.join(HERE, "golden", "book1_word64.json")))
     stream = np.fromfile(os.path.join(HERE, "golden", meta["stream"]), dtype=np.uint8)
     assert hashlib.sha256(stream.tobytes()).hexdigest() == meta["stream_sha256"]

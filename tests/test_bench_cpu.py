@@ -20,6 +20,32 @@ def test_bench_generator_equals_oracle(oracle):
         assert np.array_equal(got, oracle.gen_zipf(n, K=K, s=1.0, seed=seed)), (K, seed)
 
 
+def test_dump_outputs_stays_bounded_for_any_chunk_size(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): the sampled symbols are the output's at the recorded positions, the sums cover
+    every symbol -- one per chunk, or one per group of chunks once there would be more than DUMP_SUMS -- and the files stay
+    under 64 MB for any output and chunk size (the default limits, and scaled-down ones exercised here)."""
+    import pytest
+    import torch
+
+    import bench
+    assert bench.DUMP_SAMPLE * (4 + 8) + bench.DUMP_SUMS * 8 + 3 * 128 <= 64_000_000
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 1000)
+    monkeypatch.setattr(bench, "DUMP_SUMS", 64)
+    n = 100_003
+    data = torch.from_numpy(np.random.default_rng(4).integers(0, 256, n, dtype=np.uint8))
+    for chunk, block in ((4096, 4096), (256, 7 * 256), (1, 1563), (n + 5, n + 5)):  # (391 chunks of 256: groups of 7)
+        d = str(tmp_path / str(chunk))
+        bench.dump_outputs(torch, d, data, chunk)
+        idx = np.load(os.path.join(d, "decoded_sample_index.npy"))
+        sample = np.load(os.path.join(d, "decoded_sample.npy"))
+        sums = np.load(os.path.join(d, "decoded_chunk_sums.npy"))
+        assert sample.dtype == np.float32 and idx.dtype == np.float64 and sums.dtype == np.float64
+        assert idx.size == sample.size == 1000 and np.array_equal(sample, data.numpy()[idx.astype(np.int64)])
+        want = [int(data[lo:lo + block].sum()) for lo in range(0, n, block)]
+        assert sums.size <= 64 and sums.tolist() == pytest.approx(want, abs=0), chunk
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 1000 * 12 + 64 * 8 + 3 * 128
+
+
 def test_book1_fixture_decodes_to_the_corpus(oracle):
     """tests/golden/book1_word64.bin (made by the unmodified reference) is book1: the oracle decodes it to the
     published sha256, with the committed 12-bit frequencies."""

@@ -1,7 +1,6 @@
 """include/ryg_rans_amd/compat/: the per-symbol RansEnc*/RansDec*/Rans64*/RansWord* API,
-re-provided for host code.  Checked (CPU only) against the oracle byte for byte, and --
-where /root/reference exists -- by building the reference's own mains UNCHANGED against
-these headers and comparing their output with the README's known answers."""
+re-provided for host code.  Checked (CPU only) against the oracle byte for byte, and on the
+corpus against the streams the unmodified reference made of it (tests/golden/book1_golden.json)."""
 import ctypes as C
 import os
 import subprocess
@@ -124,24 +123,51 @@ def test_alias_header_equals_oracle_and_library(drv, oracle):
     assert drv.compat_alias_tables(_p(f, C.c_uint32), _p(cum, C.c_uint32), 4, 12, _p(t, C.c_uint32)) == 2
 
 
-def test_reference_mains_build_unchanged_against_compat_headers(book1):
-    """The drop-in claim for the per-symbol API: the reference's four sample programs, fed to
-    the compiler from stdin (so their own directory is not on the include path), compile
-    against OUR headers and reproduce the published sizes (README:48,62,82,96,110)."""
-    want = {"main": ["rANS: 435113 bytes", "interleaved rANS: 435117 bytes"],
-            "main64": ["rANS: 435116 bytes", "interleaved rANS: 435120 bytes"],
-            "main_simd": ["rANS: 435604 bytes", "interleaved rANS: 435606 bytes", "SIMD rANS: 435626 bytes"],
-            "main_alias": ["rANS: 435059 bytes", "interleaved rANS: 435063 bytes"]}
-    os.makedirs(BUILD, exist_ok=True)
-    for name, lines in want.items():
-        exe = os.path.join(BUILD, name)
-        with open("/root/reference/%s.cpp" % name, "rb") as src:
-            subprocess.run(["g++", "-x", "c++", "-O2", "-msse4.1", "-w", "-I", COMPAT, "-o", exe, "-"], stdin=src,
-                           check=True)
-        out = subprocess.run([exe], cwd="/root/reference", capture_output=True, text=True, check=True).stdout
-        for line in lines:
-            assert line in out, (name, line)
-        assert out.count("decode ok!") == len(lines) and "ERROR" not in out
+def test_compat_headers_reproduce_the_reference_streams_of_book1(drv, oracle, book1):
+    """The drop-in claim for the per-symbol API, on the corpus: the compat headers' encoders (RansEncPutSymbol,
+    RansWordEncPut, Rans64EncPutSymbol, the alias coder of rans_alias_compat.h) with 1 and 2 interleaved states, and 8 for
+    the word format, turn book1 into exactly the streams the unmodified reference made of it -- sizes published in its
+    README, SHA-256 pinned in tests/golden/book1_golden.json -- and the compat decoders (the SSE4.1 RansSimdDec pair for
+    the 8-way word stream) turn every pinned stream back into book1, ending exactly on the stream's end."""
+    import hashlib
+    import json
+    known = json.load(open(os.path.join(HERE, "golden", "book1_golden.json")))
+    u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    drv.compat_alias_encode.argtypes = [u32p, u32p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_size_t, C.c_uint32, u8p,
+                                        C.c_size_t, C.POINTER(C.c_size_t)]
+    drv.compat_alias_decode.argtypes = [u32p, u32p, C.c_uint32, C.c_uint32, u8p, C.c_size_t, C.c_size_t, C.c_uint32,
+                                        C.c_void_p, C.c_int]
+    cfmts = {("byte", 14): 0, ("word", 12): 1, ("r64", 14): 2, ("alias", 16): None}
+    checked = []
+    for e in known["streams"]:
+        if (e["fmt"], e["scale_bits"]) not in cfmts or e["n_ways"] not in (1, 2, 8) or e["sha256"] is None:
+            continue
+        cfmt, sb, N = cfmts[(e["fmt"], e["scale_bits"])], e["scale_bits"], e["n_ways"]
+        f, cum = oracle.normalize(oracle.count_freqs(book1, 256), 1 << sb)
+        f, cum = np.ascontiguousarray(f, np.uint32), np.ascontiguousarray(cum, np.uint32)
+        cap = (book1.size * 4 + 64 * 8 + 64) & ~7
+        buf = np.zeros(cap + 16, np.uint8)
+        out_len = C.c_size_t(0)
+        if cfmt is None:
+            assert drv.compat_alias_encode(_p(f, C.c_uint32), _p(cum, C.c_uint32), 256, sb, book1.ctypes.data, 1, book1.size, N,
+                                           _p(buf, C.c_uint8), cap, C.byref(out_len)) == 0
+        else:
+            assert drv.compat_encode(cfmt, _p(f, C.c_uint32), _p(cum, C.c_uint32), sb, _p(book1, C.c_uint8), book1.size, N,
+                                     _p(buf, C.c_uint8), cap, C.byref(out_len)) == 0
+        got = buf[cap - out_len.value:cap]
+        assert got.size == e["size"] and hashlib.sha256(got.tobytes()).hexdigest() == e["sha256"], e
+        padded = np.concatenate([got, np.zeros(16, np.uint8)])
+        back = np.zeros(book1.size, np.uint8)
+        if cfmt is None:
+            rc = drv.compat_alias_decode(_p(f, C.c_uint32), _p(cum, C.c_uint32), 256, sb, _p(padded, C.c_uint8), got.size,
+                                         book1.size, N, back.ctypes.data, 1)
+        else:
+            rc = drv.compat_decode(cfmt, _p(f, C.c_uint32), _p(cum, C.c_uint32), sb, _p(padded, C.c_uint8), got.size,
+                                   book1.size, N, _p(back, C.c_uint8))
+        assert rc == 0 and np.array_equal(back, book1), e
+        checked.append((e["fmt"], N))
+    # byte, r64, word and alias at 1 and 2 states, and the 8-way word stream (README: the SIMD driver's)
+    assert sorted(checked) == sorted([(fm, N) for fm in ("byte", "r64", "word", "alias") for N in (1, 2)] + [("word", 8)])
 
 
 def _avx2_driver():

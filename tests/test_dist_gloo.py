@@ -103,7 +103,7 @@ def test_two_ranks_decode_real_shards_on_one_gpu():
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                 "127.0.0.1", "--master-port", str(_free_port())]
     argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--all-on-device", "0", "--log2n", "26",
-            "--prewarm-ms", "0"]
+            "--prewarm-ms", "0", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     line, d, out = _run_bench(argv, env, launcher=launcher)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -158,14 +158,14 @@ def test_bench_gpus_n_launches_its_own_ranks():
 
 @pytest.mark.gpu
 def test_bench_default_command_line_survives_the_drivers_stdout_window():
-    """The driver's command at a small size, everything on (configs, CPU leg, placement probe): the judged line is the LAST
+    """The full command (--full) at a small size, everything on (configs, CPU leg, placement probe): the judged line is the LAST
     line of stdout, parses from the last 4 KB alone, and carries value / ms_per_step / roofline / cpu_baseline (reference) /
     one row per config with its oracle verdict -- round 4's line was 20.6 KB and came back unparsed."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    line, d, out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--log2n", "24", "--config-steps", "3"], env,
-                              timeout=1500)
+    line, d, out = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--log2n", "24", "--config-steps", "3", "--full"],
+                              env, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]
     assert line["value"] > 0 and line["ms_per_step"] > 0 and line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1
     assert line["bit_exact_roundtrip"] is True and line["headline"] is True
@@ -188,6 +188,41 @@ def test_bench_default_command_line_survives_the_drivers_stdout_window():
     assert line["value_first_pair"] == pytest.approx((1 << 24) / line["placement"]["first_pair_ms_per_step"] / 1e6, rel=1e-3)
     # and the file has what the line dropped
     assert len(d["placement"]["probe_ms"]) >= 3 and len(d["configs"]) == len(rows) and "decoders" in d["cpu_baseline"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_lean_and_dumps_what_it_decoded(tmp_path):
+    """The plain command measures the headline alone -- no configs, no CPU leg, no un-probed pair, no clock launch -- and
+    --steps sets the timed steps.  --dump-outputs writes what the last timed step decoded: the sampled symbols are the
+    generator's (seed 1) at the sampled positions, and the chunk sums cover every symbol of the output."""
+    import numpy as np
+    import torch
+
+    import bench
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dump = str(tmp_path / "outputs")
+    line, d, out = _run_bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--log2n", "24", "--dump-outputs", dump], env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert line["steps"] == 5 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["bit_exact_roundtrip"] is True
+    assert line["value"] == pytest.approx((1 << 24) / line["ms_per_step"] / 1e6, rel=0.02)  # (ms_per_step: 4 decimals)
+    assert d["roofline"]["timed_dispatches"][1] - d["roofline"]["timed_dispatches"][0] == 5  # (decode calls counted in the loop)
+    for k in ("configs", "cpu_baseline", "clocks", "oracle_chunks_checked", "decodes_oracle_container"):
+        assert k not in line and k not in d, k
+    # no timed steps on the un-probed pair (the line still quotes ms_per_step as its figure when the probe chose that pair)
+    assert "first_pair_ms_per_step" not in d["placement"]
+    if d["placement"]["chosen"] != [0, 0]:
+        assert "value_first_pair" not in line
+    want = bench.gen_zipf(torch, 1 << 24, 256, 1.0, 1, "cpu").numpy()
+    idx = np.load(os.path.join(dump, "decoded_sample_index.npy"))
+    sample = np.load(os.path.join(dump, "decoded_sample.npy"))
+    sums = np.load(os.path.join(dump, "decoded_chunk_sums.npy"))
+    assert sample.dtype == np.float32 and idx.dtype == np.float64 and sums.dtype == np.float64
+    assert sample.size == idx.size == bench.DUMP_SAMPLE and np.all(np.diff(idx) >= 0)
+    assert np.array_equal(sample, want[idx.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(sums, want.reshape(-1, 32768).sum(axis=1, dtype=np.int64).astype(np.float64))
+    assert sum(os.path.getsize(os.path.join(dump, f)) for f in os.listdir(dump)) <= 64 << 20
 
 
 @pytest.mark.gpu
@@ -243,7 +278,7 @@ def test_eight_ranks_dry_run_on_one_gpu():
     import sys
     launcher = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
                 "127.0.0.1", "--master-port", str(_free_port())]
-    argv = ["--gpus", "8", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--all-on-device", "0", "--log2n", "24"]
+    argv = ["--gpus", "8", "--steps", "3", "--warmup", "1", "--backend", "gloo", "--all-on-device", "0", "--log2n", "24", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     line, d, out = _run_bench(argv, env, launcher=launcher, timeout=1500)
     assert out.returncode == 0, out.stderr[-2000:]

@@ -1,7 +1,7 @@
 #!/bin/bash
 # tools/ab_configs.sh <out-file> <rounds> <variant>...  -- like ab_libs.sh, but prints every `configs` entry of the bench line
 OUTF=$1; ROUNDS=$2; shift 2
-B="python bench.py --no-cpu-baseline --steps 20 --warmup 5 ${BENCH_ARGS:-}"
+B="python bench.py --full --no-cpu-baseline --steps 20 --warmup 5 ${BENCH_ARGS:-}"
 pick='import json,sys
 d=json.load(sys.stdin); r=d["roofline"]
 print("headline", r["kernel_ms_avg"], r["frac"])

@@ -13,7 +13,7 @@ OUT=$REPO/gpurun_out/r05p
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 BENCH="python $REPO/bench.py --gpus 1 --steps 20 --warmup 5"
-$BENCH --details "$OUT/bench_details.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
+$BENCH --full --details "$OUT/bench_details.json" > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"; echo
 HEAD="$BENCH --no-configs --no-cpu-baseline"
 timeout 600 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/headline_stats" -o h -- $HEAD --details "$OUT/headline_details.json" > "$OUT/headline_line.json" 2> "$OUT/headline.err"

@@ -8,7 +8,7 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline $*"
+BENCH="python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $*"
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout 300 rocprofv3 --kernel-trace --pmc $c -f csv -d "$OUT/${TAG}_$c" -o pmc -- $BENCH > "$OUT/${TAG}_$c.log" 2>&1
 done
