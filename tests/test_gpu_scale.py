@@ -67,81 +67,74 @@ def test_bench_generator_equals_oracle_on_gpu(gpu, oracle):
     ("word-128-way", FMT_WORD, 12, 256, 128, 16384, 28),
     ("r64-64-way", FMT_R64, 14, 256, 64, 16384, 28),
     ("alias256-64-way", FMT_ALIAS, 16, 256, 64, 16384, 28),
+    # the reference's two narrow layouts at the BASELINE size: the group kernels (VERDICT r06 "What's missing" #4)
+    ("word8", FMT_WORD, 12, 256, 8, 1024, 30),
+    ("byte2", FMT_BYTE, 14, 256, 2, 1024, 30),
 ])
 def test_full_size_every_chunk_equals_oracle(gpu, oracle, name, fmt, sb, K, ways, chunk, log2n):
+    """The body lives in tests/_every_chunk.py (shared with tests/test_gpu_kernel_matrix.py): compact encode, every chunk ==
+    the oracle's, decode of the GPU's and of an oracle-made container, the scratch ring, the slot layout and its compaction,
+    sized slots at the tight size and at half of it, one damaged chunk."""
+    R, ctx, torch = gpu
+    from _every_chunk import check_every_chunk
+    kernels = {}
+    if name.startswith("C3"):  # (both chunk sizes: 32 Ki is bench.py's headline, 16 Ki its `configs` entries)
+        kernels["decode"] = "k_decode_word64"
+    if name.startswith("C4"):
+        kernels["decode"] = "k_decode_dual<alias>"
+    if name == "word8":  # the group kernels: eight chunks per wave (decode_groups.hip / encode_groups.hip)
+        kernels = {"decode": "k_decode_word_groups", "encode": ("k_encode_word_groups", 0), "slots": ("k_encode_word_groups", 2),
+                   "sized": ("k_encode_word_groups", 2)}
+    if name == "byte2":  # 32 chunks per wave
+        kernels["decode"] = "k_decode_byte_pairs"
+    check_every_chunk(R, ctx, torch, fmt, sb, K, ways, chunk, 1 << log2n, kernels=kernels)
+
+
+def test_baseline_config4_shards_seeds_2_to_8(gpu, oracle):
+    """BASELINE configs[4] is eight shards of 1 GiB with seeds 1..8; seed 1 is the headline input every test uses.  Here are the
+    other seven, one after another on the one GPU: generate, count, normalise, encode (word format, 64-way, 32 Ki chunks),
+    decode and compare with the input.  The oracle re-encodes 1 024 of each shard's 32 768 chunks -- the sampling rule: the
+    first 256, the last 256, and the 512 around the edges of the layout pass's scan blocks of 8 192 chunks (85 chunks on
+    either side of chunks 8 192 and 24 576, 86 on either side of 16 384).  The shards' stream sizes are pairwise distinct,
+    and the head of every buffer is what the oracle's generator makes from the same seed on the CPU."""
     R, ctx, torch = gpu
     import bench
-    n = 1 << log2n
-    d_syms = bench.gen_zipf(torch, n, K, 1.0, 1, "cuda")
-    counts = ctx.count_freqs_device(d_syms, K)
-    assert int(counts.sum()) == n
-    freqs, _ = R.normalize_freqs(counts, 1 << sb)
-    gm = ctx.model(fmt, freqs, sb)
-    cont, offs, lens, total = ctx.encode(gm, d_syms, ways, chunk)
-    art = {"fmt": fmt, "sb": sb, "K": K, "ways": ways, "chunk": chunk, "n": n, "freqs": freqs, "d_syms": d_syms,
-           "cont": cont, "offs": offs, "lens": lens, "total": total}
-    # 1. EVERY chunk of the GPU encoder's container == the oracle's stream for it; the index == prefix sums
-    assert bench.oracle_check_chunks(art) == (n + chunk - 1) // chunk
-    out = ctx.decode(gm, cont, total, offs, lens, n, ways, chunk)
-    assert torch.equal(out, d_syms)
-    if name.startswith("C3"):  # (both chunk sizes: 32 Ki is bench.py's headline, 16 Ki its `configs` entries)
+    n, chunk, ways, sb = 1 << 30, 32768, 64, 12
+    nchunks = n // chunk
+    ranges = [(0, 256), (8192 - 85, 8192 + 85), (16384 - 86, 16384 + 86), (24576 - 85, 24576 + 85), (nchunks - 256, nchunks)]
+    assert sum(hi - lo for lo, hi in ranges) == 1024
+    stream_bytes = {}
+    for seed in range(2, 9):
+        d_syms = bench.gen_zipf(torch, n, 256, 1.0, seed, "cuda")
+        assert np.array_equal(d_syms[:1 << 16].cpu().numpy(), oracle.gen_zipf(1 << 16, K=256, s=1.0, seed=seed)), seed
+        counts = ctx.count_freqs_device(d_syms, 256)
+        assert int(counts.sum()) == n
+        freqs, _ = R.normalize_freqs(counts, 1 << sb)
+        gm = ctx.model(FMT_WORD, freqs, sb)
+        cont, offs, lens, total = ctx.encode(gm, d_syms, ways, chunk)
+        out = ctx.decode(gm, cont, total, offs, lens, n, ways, chunk)
         assert ctx.last_decode_kernel() == "k_decode_word64"
-    if name.startswith("C4"):
-        assert ctx.last_decode_kernel() == "k_decode_dual<alias>"
-    del out
-    # 2. the decoder on a container made by the ORACLE alone (host, threaded), not by the GPU encoder
-    assert bench.decode_oracle_container(torch, R, ctx, gm, art, "cuda")
-    # 3. the encoder with its scratch ring (RANS_AMD_OPT_ENC_SCRATCH_RING; wave-per-chunk encoders): the same container
-    if ways == 64 and fmt != FMT_ALIAS:
-        ctx2 = R.Context(0)
-        ctx2.set_option(R.OPT_ENC_SCRATCH_RING, 1)
-        gm2 = ctx2.model(fmt, freqs, sb)
-        cont_r, offs_r, lens_r, total_r = ctx2.encode(gm2, d_syms, ways, chunk)
-        assert total_r == total and torch.equal(offs_r, offs) and torch.equal(lens_r, lens)
-        art_r = dict(art, cont=cont_r)
-        assert bench.oracle_check_chunks(art_r) == (n + chunk - 1) // chunk
-        del cont_r, gm2
-        ctx2.close()
-    # 4. the slot layout (rans_amd_encode_slots: every chunk written once, where it was coded): every chunk == the
-    #    oracle's stream again, index == (c + 1) * slot - length, the slot container decodes as it is, and its compaction
-    #    is the container of step 1
-    s_cont, s_offs, s_lens, s_total = ctx.encode_slots(gm, d_syms, ways, chunk)
-    assert ctx.last_encode_placement() == 2 and torch.equal(s_lens, lens)
-    art_s = dict(art, cont=s_cont, offs=s_offs, lens=s_lens, total=s_total, slot=R.slot_bytes(fmt, n, ways, chunk))
-    assert bench.oracle_check_chunks(art_s) == (n + chunk - 1) // chunk
-    out = ctx.decode(gm, s_cont, s_total, s_offs, s_lens, n, ways, chunk)
-    assert torch.equal(out, d_syms)
-    del out
-    c_cont, c_offs, c_total = ctx.compact(s_cont, s_total, s_offs, s_lens, lens.numel())
-    assert c_total == total and torch.equal(c_offs, offs)
-    assert bench.oracle_check_chunks(dict(art, cont=c_cont, offs=c_offs)) == (n + chunk - 1) // chunk
-    del s_cont, c_cont
-    # 4b. SIZED slots (rans_amd_encode_slots_sized, slot = rans_amd_tight_slot_bytes()): every chunk == the oracle's stream
-    #     wherever it lies (its slot or the overflow region), the index follows the layout's rule, the container is about
-    #     the compact one's size and decodes as it is.  Then the same with slots of HALF that size: every chunk overflows
-    #     into the region behind them (the redo launch codes the whole shard) and still equals the oracle's.
-    nchunks = (n + chunk - 1) // chunk
-    worst = R.slot_bytes(fmt, n, ways, chunk)
-    t_cont, t_offs, t_lens, t_total, t_slot = ctx.encode_sized(gm, d_syms, ways, chunk)
-    assert torch.equal(t_lens, lens) and t_slot < worst
-    assert t_total <= 1.35 * total, (t_total, total)  # (config 2's 512-symbol chunks in whole 64-byte lines: 1.23 x)
-    assert bench.oracle_check_chunks(dict(art, cont=t_cont, offs=t_offs, lens=t_lens, total=t_total, slot=t_slot, worst=worst)) == nchunks
-    out = ctx.decode(gm, t_cont, t_total, t_offs, t_lens, n, ways, chunk)
-    assert torch.equal(out, d_syms)
-    del out, t_cont
-    half = max(64, (t_slot // 2) & ~63)
-    h_cont, h_offs, h_lens, h_total, _ = ctx.encode_sized(gm, d_syms, ways, chunk, slot=half, overflow_chunks=nchunks)
-    assert torch.equal(h_lens, lens) and h_total >= nchunks * half + (nchunks - 1) * worst  # (a ragged last chunk may fit)
-    assert bench.oracle_check_chunks(dict(art, cont=h_cont, offs=h_offs, lens=h_lens, total=h_total, slot=half, worst=worst)) == nchunks
-    out = ctx.decode(gm, h_cont, h_total, h_offs, h_lens, n, ways, chunk)
-    assert torch.equal(out, d_syms)
-    del out, h_cont
-    # 5. a corrupted chunk is flagged (or at least does not decode to the input)
-    bad = cont.clone()
-    bad[int(offs[0].item()) + int(lens[0].item()) // 2] ^= 0x10
-    out2 = torch.empty_like(d_syms)
-    ctx.decode(gm, bad, total, offs, lens, n, ways, chunk, d_out=out2, sync=False)
-    assert ctx.decode_errors() >= 1 or not torch.equal(out2, d_syms)
+        assert torch.equal(out, d_syms), seed
+        del out
+        # the whole index == the prefix sums of the 16-byte aligned lengths
+        aligned = (lens.to(torch.int64) + 15) & ~15
+        want = torch.zeros(nchunks + 1, dtype=torch.int64, device="cuda")
+        want[1:] = torch.cumsum(aligned, 0)
+        want[nchunks] = want[nchunks - 1] + lens[nchunks - 1]
+        assert torch.equal(offs, want) and total == int(want[-1].item()), seed
+        om = oracle.model(freqs, sb)
+        h_offs, h_lens = offs.cpu().numpy().astype(np.uint64), lens.cpu().numpy().astype(np.uint32)
+        checked = 0
+        for lo, hi in ranges:
+            a, b = int(h_offs[lo]), int(h_offs[hi - 1]) + int(h_lens[hi - 1])
+            count, bad = oracle.compare_container(FMT_WORD, om, d_syms[lo * chunk:hi * chunk].cpu().numpy(), ways, chunk,
+                                                  cont[a:b].cpu().numpy(), h_offs[lo:hi] - np.uint64(a), h_lens[lo:hi])
+            assert count == hi - lo and bad == -1, (seed, lo + bad)
+            checked += count
+        assert checked == 1024
+        stream_bytes[seed] = total
+        del cont, d_syms
+    assert len(set(stream_bytes.values())) == 7, stream_bytes
 
 
 @pytest.mark.parametrize("fmt,sb,chunk", [(FMT_WORD, 12, 16384), (FMT_BYTE, 12, 16384), (FMT_WORD, 12, 32768), (FMT_BYTE, 10, 32768)])
