@@ -59,7 +59,8 @@ extern "C" {
  * rans_amd_container_compact, rans_amd_container_slice, chunk offsets on any multiple of the format's unit in every decoder
  * (0.4.0); rans_amd_encode_slots_sized + rans_amd_tight_slot_bytes / rans_amd_encode_sized_bound, rans_amd_probe_placement,
  * rans_amd_encode_adaptive_fmt / rans_amd_decode_adaptive_fmt (0.5.0); rans_amd_encode_adaptive_sized,
- * rans_amd_container_pack_indexed[_adaptive] (0.6.0).  A caller built
+ * rans_amd_container_pack_indexed[_adaptive] (0.6.0); ragged batches -- rans_amd_batch_layout, rans_amd_encode_batch,
+ * rans_amd_decode_batch, rans_amd_batch_order, rans_amd_batch_slice (still 0.6.0: additions only).  A caller built
  * against an older header keeps working, with two behaviour changes it can observe: since 0.4.0
  * rans_amd_container_parse[_adaptive] want a 4-byte aligned `src` (RANS_AMD_E_ARG otherwise; an mmap at an odd offset must
  * be copied first), and since 0.5.0 rans_amd_container_compact checks its SOURCE index against src_bytes
@@ -348,6 +349,60 @@ int rans_amd_decode(rans_amd_ctx *ctx, const rans_amd_model *model, const void *
  * relative to *byte_begin -- copy that byte range to the device, pass it with the rebased offsets and d_lengths + lo. */
 int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, uint64_t n_chunks, uint64_t lo, uint64_t hi,
                              uint64_t *byte_begin, uint64_t *byte_end, uint64_t *rebased_offsets);
+
+/* ---- ragged batches: many independent streams, each with its own symbol count ---------------
+ *
+ * What a user of the reference holds is rarely one long input cut into equal chunks: it is many independent reference
+ * streams, each with a symbol count kept out of band (main.cpp:182-188, main_simd.cpp:305-317).  The batch calls take the
+ * symbol side as an index too:
+ *
+ *     stream c  <->  the d_sym_counts[c] symbols at d_syms / d_out + d_sym_offsets[c]   (in symbols; any value)
+ *
+ * beside the stream index (d_offsets[c], d_lengths[c]) every decoder already takes.  One wavefront codes one stream,
+ * whatever the interleave: n_ways is anything rans_amd_ways_supported accepts (word 8-way, byte 2-way, rans64 2-way and
+ * alias streams of the reference included -- narrow interleaves leave lanes idle, but across the whole GPU; kernels that
+ * pack several ragged streams into a wave are later work).  A stream of 0 symbols is the n_ways flushed initial states.
+ * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
+ * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).
+ *
+ * rans_amd_batch_layout (host, no GPU): from sym_counts[n_streams]
+ *     sym_offsets[n_streams + 1]   prefix sum of the counts, each rounded up to sym_align symbols (1 = dense).  sym_align = 4
+ *                                  (u8 symbols) keeps every stream's output 4-byte aligned: the decoders store such a
+ *                                  stream a dword per lane, any other stream element by element
+ *     slot_offsets[n_streams + 1]  prefix sum of rans_amd_chunk_bound(format, count, n_ways) (a multiple of 16): where
+ *                                  rans_amd_encode_batch puts its streams; the last entry is the capacity it needs */
+int rans_amd_batch_layout(const uint32_t *sym_counts, uint64_t n_streams, int format, uint32_t n_ways, uint32_t sym_align,
+                          uint64_t *sym_offsets, uint64_t *slot_offsets);
+/* Code stream c from its symbols into the slot [d_slot_offsets[c], d_slot_offsets[c + 1]) of d_out, ENDING at the slot's end
+ * (the layout of rans_amd_encode_slots: nothing moves afterwards): d_lengths[c] = its bytes, d_offsets[c] =
+ * d_slot_offsets[c + 1] - d_lengths[c]; every stream is byte for byte the reference's stream of that input.  The slot
+ * index is data: a slot that does not start and end on 16 bytes, does not lie inside [0, out_cap) or is smaller than
+ * rans_amd_chunk_bound() of its count is not written (d_lengths[c] = 0) and the call reports RANS_AMD_E_SPACE through
+ * rans_amd_encode_status, which also reports a symbol outside the model (RANS_AMD_E_MODEL).  Asynchronous.
+ * rans_amd_container_compact / rans_amd_container_pack_indexed take (d_offsets, d_lengths) as they are. */
+int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_syms, const uint64_t *d_sym_offsets,
+                          const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint64_t *d_slot_offsets,
+                          void *d_out, uint64_t out_cap, uint64_t *d_offsets, uint32_t *d_lengths, void *stream);
+/* Decode stream c to d_out + d_sym_offsets[c] (d_out holds out_syms symbols).  The checks of rans_amd_decode apply to every
+ * stream; the symbol index is data as well: a stream whose [sym_offset, sym_offset + count) does not lie inside
+ * [0, out_syms) is skipped and counted as failed -- nothing outside d_out is ever written.  d_order (NULL, or a permutation
+ * of the stream indices, e.g. from rans_amd_batch_order): the k-th claim of the launch takes stream d_order[k]; streams are
+ * handed out dynamically either way, the order only keeps a long stream from being claimed last.  h_bad_streams as
+ * h_bad_chunks of rans_amd_decode. */
+int rans_amd_decode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_container, uint64_t container_bytes,
+                          const uint64_t *d_offsets, const uint32_t *d_lengths, const uint64_t *d_sym_offsets,
+                          const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint32_t *d_order, void *d_out,
+                          uint64_t out_syms, uint64_t *h_bad_streams, void *stream);
+/* d_order[n_streams] = a permutation of the stream indices in which floor(log2(count + 1)) never increases (the order
+ * inside a bucket is unspecified).  On the device, asynchronous: a histogram over 33 buckets, a scan, a scatter.  The
+ * context keeps ONE small workspace for it: calls on one context must be ordered by their stream (or synchronised), and a
+ * captured call must not run at the same time as another call of this function on the same context -- the rule the
+ * encoders' status words follow. */
+int rans_amd_batch_order(rans_amd_ctx *ctx, const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t *d_order, void *stream);
+/* Split a batch over n_ranks ranks by stream bytes (host): bounds[n_ranks + 1], bounds[g] = the first stream in front of
+ * which at least floor(g * total / n_ranks) of the total bytes lie (bounds[0] = 0, bounds[n_ranks] = n_streams; ranks may be
+ * empty).  Rank g passes [bounds[g], bounds[g + 1]) to rans_amd_container_slice. */
+int rans_amd_batch_slice(const uint32_t *lengths, uint64_t n_streams, uint32_t n_ranks, uint64_t *bounds);
 
 /* Placement probe (setup time, not the data path).  On MI355X the same decode over the same bytes runs 4-6 % faster when
  * its container and its output lie in DIFFERENT classes of device memory than when they share one (profiles/r04_allocation.md:

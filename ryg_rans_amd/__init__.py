@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "rans_amd_offsets_from_lengths", "rans_amd_container_bytes", "rans_amd_container_pack",
     "rans_amd_packed_payload_bytes", "rans_amd_container_pack_indexed", "rans_amd_container_pack_indexed_adaptive",
     "rans_amd_container_parse", "rans_amd_encode_workspace_bytes", "rans_amd_build_model_o0",
+    "rans_amd_batch_layout", "rans_amd_encode_batch", "rans_amd_decode_batch", "rans_amd_batch_order", "rans_amd_batch_slice",
 ]
 
 
@@ -124,6 +125,11 @@ def _load():
         "rans_amd_container_slice": (i32, [u64p, u32p, u64, u64, u64, u64p, u64p, u64p]),
         "rans_amd_decode": (i32, [vp, vp, vp, u64, vp, vp, u64, u32, u32, vp, u64p, vp]),
         "rans_amd_decode_errors": (i32, [vp, u64p, vp]),
+        "rans_amd_batch_layout": (i32, [u32p, u64, i32, u32, u32, u64p, u64p]),
+        "rans_amd_encode_batch": (i32, [vp, vp, vp, vp, vp, u64, u32, vp, vp, u64, vp, vp, vp]),
+        "rans_amd_decode_batch": (i32, [vp, vp, vp, u64, vp, vp, vp, vp, u64, u32, vp, vp, u64, u64p, vp]),
+        "rans_amd_batch_order": (i32, [vp, vp, u64, vp, vp]),
+        "rans_amd_batch_slice": (i32, [u32p, u64, u32, u64p]),
         "rans_amd_probe_placement": (i32, [vp, vp, C.POINTER(vp), u32, u64, vp, vp, u64, u32, u32, C.POINTER(vp), u32, u32, u32,
                                          u32p, u32p, C.POINTER(C.c_float), vp]),
         "rans_amd_encode_host": (i32, [vp, vp, vp, u64, u32, vp, u64, u64p]),
@@ -232,6 +238,27 @@ def encode_sized_bound(fmt, n, n_ways, chunk_syms, slot, overflow_chunks):
 
 def ways_supported(fmt, n_ways):
     return bool(_lib.rans_amd_ways_supported(fmt, n_ways))
+
+
+def batch_layout(sym_counts, fmt, n_ways, sym_align=1):
+    """rans_amd_batch_layout: -> (sym_offsets, slot_offsets), uint64[n_streams + 1] each; slot_offsets[-1] is the capacity
+    encode_batch needs.  sym_align = 4 keeps u8 streams on the decoders' dword store path."""
+    counts = np.ascontiguousarray(sym_counts, dtype=np.uint32)
+    sym_offs = np.zeros(counts.size + 1, dtype=np.uint64)
+    slot_offs = np.zeros(counts.size + 1, dtype=np.uint64)
+    _check(_lib.rans_amd_batch_layout(counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size, fmt, n_ways, sym_align,
+                                      sym_offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                      slot_offs.ctypes.data_as(C.POINTER(C.c_uint64))), "batch_layout")
+    return sym_offs, slot_offs
+
+
+def batch_slice(lengths, n_ranks):
+    """rans_amd_batch_slice: stream ranges of n_ranks ranks with about equal stream bytes -> bounds, uint64[n_ranks + 1]."""
+    lengths = np.ascontiguousarray(lengths, dtype=np.uint32)
+    bounds = np.zeros(max(int(n_ranks), 0) + 1, dtype=np.uint64)
+    _check(_lib.rans_amd_batch_slice(lengths.ctypes.data_as(C.POINTER(C.c_uint32)), lengths.size, n_ranks,
+                                     bounds.ctypes.data_as(C.POINTER(C.c_uint64))), "batch_slice")
+    return bounds
 
 
 class Context:
@@ -436,6 +463,56 @@ class Context:
                                     d_lengths.data_ptr(), n, n_ways, chunk_syms, d_out.data_ptr(),
                                     C.byref(bad) if sync else None, _torch_stream()), "decode")
         return d_out
+
+    # -- ragged batches: many independent streams, each with its own symbol count
+    def encode_batch(self, model, d_syms, d_sym_offsets, d_sym_counts, n_ways, d_slot_offsets, d_out=None, d_offsets=None,
+                     d_lengths=None, out_cap=None):
+        """rans_amd_encode_batch (asynchronous; encode_status() reports): stream c = the d_sym_counts[c] symbols at
+        d_sym_offsets[c], coded to the end of slot [d_slot_offsets[c], d_slot_offsets[c + 1]).  d_sym_offsets / d_slot_offsets:
+        int64 tensors (batch_layout), d_sym_counts: int32.  Returns (d_container, d_offsets, d_lengths)."""
+        import torch
+        n_streams = d_sym_counts.numel()
+        dev = d_sym_counts.device
+        if d_out is None:
+            cap = int(d_slot_offsets[n_streams].item()) if out_cap is None else out_cap
+            d_out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        if d_offsets is None:
+            d_offsets = torch.zeros(max(n_streams, 1), dtype=torch.int64, device=dev)
+        if d_lengths is None:
+            d_lengths = torch.zeros(max(n_streams, 1), dtype=torch.int32, device=dev)
+        _check(_lib.rans_amd_encode_batch(self._h, model._h, d_syms.data_ptr(), d_sym_offsets.data_ptr(), d_sym_counts.data_ptr(),
+                                          n_streams, n_ways, d_slot_offsets.data_ptr(), d_out.data_ptr(),
+                                          d_out.numel() if out_cap is None else out_cap, d_offsets.data_ptr(),
+                                          d_lengths.data_ptr(), _torch_stream()), "encode_batch")
+        return d_out, d_offsets, d_lengths
+
+    def decode_batch(self, model, d_container, container_bytes, d_offsets, d_lengths, d_sym_offsets, d_sym_counts, n_ways,
+                     d_out, d_order=None, out_syms=None, sync=True, n_streams=None):
+        """rans_amd_decode_batch into d_out (out_syms symbols, default all of it); d_order: int32 tensor or None.  With
+        sync a failed stream raises RansAmdError(E_CORRUPT) whose `bad_streams` is the count the call wrote to h_bad_streams;
+        without, decode_errors() has the count."""
+        n_streams = d_sym_counts.numel() if n_streams is None else n_streams
+        bad = C.c_uint64(0)
+        rc = _lib.rans_amd_decode_batch(self._h, model._h, d_container.data_ptr(), container_bytes, d_offsets.data_ptr(),
+                                        d_lengths.data_ptr(), d_sym_offsets.data_ptr(), d_sym_counts.data_ptr(), n_streams,
+                                        n_ways, d_order.data_ptr() if d_order is not None else None, d_out.data_ptr(),
+                                        d_out.numel() if out_syms is None else out_syms, C.byref(bad) if sync else None,
+                                        _torch_stream())
+        if rc != OK:
+            err = RansAmdError(rc, "decode_batch", _lib.rans_amd_last_error().decode())
+            err.bad_streams = int(bad.value)
+            raise err
+        return d_out
+
+    def batch_order(self, d_sym_counts, d_order=None):
+        """rans_amd_batch_order: int32 tensor, a permutation of the stream indices, longest bucket first (asynchronous)."""
+        import torch
+        n_streams = d_sym_counts.numel()
+        if d_order is None:
+            d_order = torch.empty(max(n_streams, 1), dtype=torch.int32, device=d_sym_counts.device)
+        _check(_lib.rans_amd_batch_order(self._h, d_sym_counts.data_ptr(), n_streams, d_order.data_ptr(), _torch_stream()),
+               "batch_order")
+        return d_order[:n_streams]
 
     def probe_placement(self, model, d_containers, container_bytes, d_offsets, d_lengths, n, n_ways, chunk_syms, d_outs,
                         launches=6, sweeps=2):

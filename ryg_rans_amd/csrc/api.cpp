@@ -111,6 +111,7 @@ struct rans_amd_ctx {
     DeviceBuffer enc_status;  // fused encoder: look-back word per chunk + the claim counters (EncParams::status)
     DeviceBuffer enc_mailboxes; // fused encoder whose tables fill the LDS: one mailbox per block (EncParams::mailbox_global)
     DeviceBuffer wave_scratch; // one 64-byte line per resident decoder wave (DecParams::wave_scratch)
+    DeviceBuffer order_ws;     // bucket totals and cursors of rans_amd_batch_order (small, allocated once, kept)
     DeviceBuffer adapt_rcp;    // reciprocals by frequency for the fused per-chunk-model encoder (AdaptEncParams::rcp); built once, kept
     DeviceBuffer host_in, host_out, host_idx; // staging of the *_host wrappers, kept between calls (under host_mu)
     std::mutex host_mu;
@@ -351,6 +352,7 @@ int rans_amd_ctx_destroy(rans_amd_ctx *ctx)
     ctx->trace.release();
     ctx->wave_scratch.release();
     ctx->adapt_rcp.release();
+    ctx->order_ws.release();
     if (ctx->d_words)
         (void)hipFree(ctx->d_words);
     for (int i = 0; i < 4; ++i)
@@ -1285,6 +1287,243 @@ int rans_amd_decode(rans_amd_ctx *ctx, const rans_amd_model *model, const void *
         *h_bad_chunks = bad;
         if (bad)
             return fail(RANS_AMD_E_CORRUPT, "decode: at least one chunk failed its integrity check");
+    }
+    return RANS_AMD_OK;
+}
+
+/* ---- ragged batches: many independent streams, each with its own symbol count ------------- */
+
+int rans_amd_batch_layout(const uint32_t *sym_counts, uint64_t n_streams, int format, uint32_t n_ways, uint32_t sym_align,
+                          uint64_t *sym_offsets, uint64_t *slot_offsets)
+{
+    if (!sym_offsets || !slot_offsets || (n_streams && !sym_counts) || sym_align == 0)
+        return fail(RANS_AMD_E_ARG, "batch_layout: NULL argument or sym_align == 0");
+    if (!ways_supported(format, n_ways))
+        return fail(RANS_AMD_E_UNSUPPORTED, "batch_layout: no kernel for this format / n_ways (1..512)");
+    uint64_t sym = 0, slot = 0;
+    for (uint64_t c = 0; c < n_streams; ++c) {
+        sym_offsets[c] = sym;
+        slot_offsets[c] = slot;
+        sym += ((uint64_t)sym_counts[c] + sym_align - 1) / sym_align * sym_align;
+        slot += rans_amd_chunk_bound(format, sym_counts[c], n_ways); // (a multiple of 16 already)
+    }
+    sym_offsets[n_streams] = sym;
+    slot_offsets[n_streams] = slot;
+    return RANS_AMD_OK;
+}
+
+int rans_amd_batch_slice(const uint32_t *lengths, uint64_t n_streams, uint32_t n_ranks, uint64_t *bounds)
+{
+    if (!bounds || n_ranks == 0 || (n_streams && !lengths))
+        return fail(RANS_AMD_E_ARG, "batch_slice: NULL argument or n_ranks == 0");
+    uint64_t total = 0;
+    for (uint64_t c = 0; c < n_streams; ++c)
+        total += lengths[c];
+    // bounds[g]: the first stream in front of which at least floor(g * total / G) bytes lie
+    uint64_t c = 0, before = 0;
+    for (uint32_t g = 0; g < n_ranks; ++g) {
+        const uint64_t target = (uint64_t)(((unsigned __int128)total * g) / n_ranks);
+        while (c < n_streams && before < target)
+            before += lengths[c++];
+        bounds[g] = c;
+    }
+    bounds[n_ranks] = n_streams;
+    return RANS_AMD_OK;
+}
+
+int rans_amd_batch_order(rans_amd_ctx *ctx, const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t *d_order, void *stream)
+{
+    if (!ctx || (n_streams && (!d_sym_counts || !d_order)))
+        return fail(RANS_AMD_E_ARG, "batch_order: NULL argument");
+    if (n_streams > 0xffffffffull)
+        return fail(RANS_AMD_E_UNSUPPORTED, "batch_order: stream indices are 32-bit");
+    if (n_streams == 0)
+        return RANS_AMD_OK;
+    DeviceGuard guard(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CaptureScope capture(s);
+    if (int rc = ctx->order_ws.reserve((size_t)2 * kOrderBuckets * 4))
+        return rc;
+    uint32_t *ws = static_cast<uint32_t *>(ctx->order_ws.ptr);
+    ZeroList zero(s);
+    HIP_TRY(zero.add(ws, (uint64_t)2 * kOrderBuckets * 4));
+    HIP_TRY(zero.flush());
+    HIP_TRY(launch_batch_order(d_sym_counts, n_streams, d_order, ws, ctx->num_cus, s));
+    return RANS_AMD_OK;
+}
+
+int rans_amd_decode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_container, uint64_t container_bytes,
+                          const uint64_t *d_offsets, const uint32_t *d_lengths, const uint64_t *d_sym_offsets,
+                          const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint32_t *d_order, void *d_out,
+                          uint64_t out_syms, uint64_t *h_bad_streams, void *stream)
+{
+    if (!ctx || !model || (n_streams && (!d_container || !d_offsets || !d_lengths || !d_sym_offsets || !d_sym_counts || (out_syms && !d_out))))
+        return fail(RANS_AMD_E_ARG, "decode_batch: NULL argument");
+    if (model->ctx != ctx)
+        return fail(RANS_AMD_E_ARG, "decode_batch: model belongs to another context");
+    const int format = model->host.format;
+    if (!ways_supported(format, n_ways))
+        return fail(RANS_AMD_E_UNSUPPORTED, "decode_batch: n_ways must be in 1..512");
+    if ((reinterpret_cast<uintptr_t>(d_container) & 15u) != 0)
+        return fail(RANS_AMD_E_ARG, "decode_batch: d_container must be 16-byte aligned");
+    if (n_streams >= 0xffffffffull)
+        return fail(RANS_AMD_E_UNSUPPORTED, "decode_batch: stream indices are 32-bit");
+    DeviceGuard guard(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CaptureScope capture(s);
+    if (capture.active && h_bad_streams)
+        return fail(RANS_AMD_E_ARG, "decode_batch: h_bad_streams must be NULL while the stream is capturing (rans_amd_decode_errors after the replay)");
+    if (n_streams) {
+        DecParams dp{};
+        dp.container = static_cast<const uint8_t *>(d_container);
+        dp.container_bytes = container_bytes;
+        dp.offsets = d_offsets;
+        dp.lengths = d_lengths;
+        dp.out = static_cast<uint8_t *>(d_out);
+        dp.n = 0;
+        dp.nchunks = n_streams;
+        dp.chunk_syms = 0;
+        dp.n_ways = n_ways;
+        dp.sym_offsets = d_sym_offsets;
+        dp.sym_counts = d_sym_counts;
+        dp.order = d_order;
+        dp.out_syms = out_syms;
+        dp.table0 = model->d_table0;
+        dp.table1 = model->d_table1 ? model->d_table1 : model->d_table0;
+        dp.table0_bytes = model->table0_bytes;
+        dp.table1_bytes = model->table1_bytes;
+        dp.scale_bits = model->host.scale_bits;
+        dp.log2nsyms = model->host.log2nsyms;
+        if (model->host.r64_search) { // log2 of the padded cum table
+            dp.log2nsyms = 0;
+            while ((1u << dp.log2nsyms) < model->host.cum_padded.size())
+                dp.log2nsyms++;
+        }
+        dp.sym_bytes = (uint32_t)model->host.sym_bytes;
+        dp.err_count = ctx->d_err();
+        if (int wrc = ctx->wave_scratch.reserve((size_t)ctx->num_cus * 2u * (kDecBlockThreads / 64) * 64u))
+            return wrc;
+        dp.wave_scratch = static_cast<uint8_t *>(ctx->wave_scratch.ptr);
+        dp.variant = ctx->variant;
+        // the counter ring, exactly as rans_amd_decode uses it: claim from slot i, re-zero the slot launch i + 32 will use;
+        // a captured launch takes one of the capture slots and a k_zero node in front of it
+        unsigned int *ring = reinterpret_cast<unsigned int *>(ctx->d_words + 256);
+        if (capture.active) {
+            dp.work_counter = capture_counters(ctx);
+            ZeroList zero(s);
+            HIP_TRY(zero.add(dp.work_counter, (uint64_t)kWorkSlotWords * 4));
+            HIP_TRY(zero.flush());
+            dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
+        } else {
+            dp.work_counter = ring + (size_t)(ctx->launch_seq % kWorkSlots) * kWorkSlotWords;
+            dp.work_counter_reset = ring + (size_t)((ctx->launch_seq + kWorkSlots / 2) % kWorkSlots) * kWorkSlotWords;
+            dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
+            dp.span_reset = reinterpret_cast<unsigned long long *>(dp.work_counter_reset + kWorkPools * kWorkPoolStride);
+        }
+        if (ctx->timing && !t_capturing)
+            HIP_TRY(hipEventRecord(ctx->ev[0], s));
+        int dec_format = model->host.r64_search ? kKernelFormatR64Search
+                         : (format == RANS_AMD_FMT_WORD && model->host.sym_bytes == 2) ? kKernelFormatWord16
+                                                                                     : format;
+        // byte format: the fused slot records where the model has them and they leave room for two blocks per CU (rans_amd_decode)
+        if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12) {
+            dp.table0 = model->d_fused;
+            dp.table0_bytes = (uint32_t)(model->host.byte_slots.size() * sizeof(WordSlot));
+            dp.table1 = model->d_fused;
+            dp.table1_bytes = 0;
+            dec_format = kKernelFormatByteFused;
+        }
+        HIP_TRY(launch_decode_batch(dec_format, dp, ctx->num_cus, s, &ctx->last_kernel));
+        if (!capture.active)
+            ctx->launch_seq++;
+        if (ctx->timing && !t_capturing) {
+            HIP_TRY(hipEventRecord(ctx->ev[1], s));
+            ctx->dec_timed = true;
+        }
+    }
+    if (h_bad_streams) {
+        unsigned long long bad = 0;
+        HIP_TRY(hipMemcpyAsync(&bad, ctx->d_err(), 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemsetAsync(ctx->d_err(), 0, 8, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        *h_bad_streams = bad;
+        if (bad)
+            return fail(RANS_AMD_E_CORRUPT, "decode_batch: at least one stream failed its integrity check");
+    }
+    return RANS_AMD_OK;
+}
+
+int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_syms, const uint64_t *d_sym_offsets,
+                          const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint64_t *d_slot_offsets,
+                          void *d_out, uint64_t out_cap, uint64_t *d_offsets, uint32_t *d_lengths, void *stream)
+{
+    if (!ctx || !model || (n_streams && (!d_sym_offsets || !d_sym_counts || !d_slot_offsets || !d_out || !d_offsets || !d_lengths)))
+        return fail(RANS_AMD_E_ARG, "encode_batch: NULL argument");
+    if (model->ctx != ctx)
+        return fail(RANS_AMD_E_ARG, "encode_batch: model belongs to another context");
+    const int format = model->host.format;
+    if (!ways_supported(format, n_ways))
+        return fail(RANS_AMD_E_UNSUPPORTED, "encode_batch: n_ways must be in 1..512");
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0)
+        return fail(RANS_AMD_E_ARG, "encode_batch: d_out must be 16-byte aligned");
+    if (n_streams >= 0xffffffffull)
+        return fail(RANS_AMD_E_UNSUPPORTED, "encode_batch: stream indices are 32-bit");
+    const int enc_format = model->host.r64_search ? kKernelFormatR64Search
+                           : (format == RANS_AMD_FMT_WORD && model->host.sym_bytes == 2) ? kKernelFormatWord16
+                           : (format == RANS_AMD_FMT_ALIAS && model->d_alias_remap16) ? kKernelFormatAliasLds
+                                                                                                  : format;
+    if (enc_format == RANS_AMD_FMT_ALIAS)
+        return fail(RANS_AMD_E_UNSUPPORTED, "encode_batch: this alias model has no LDS tables (cannot happen for a model rans_amd_model_create accepted)");
+    DeviceGuard guard(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CaptureScope capture(s);
+    ZeroList zero(s);
+    HIP_TRY(zero.add(ctx->d_enc_flags(), 8)); // (encode flags and histogram flags, not the compaction's word: encode_impl)
+    const size_t claim_bytes = (size_t)(kWorkPools + 2) * kWorkPoolStride * 4;
+    if (n_streams) {
+        if (int rc = ctx->enc_status.reserve(claim_bytes))
+            return rc;
+        HIP_TRY(zero.add(ctx->enc_status.ptr, claim_bytes));
+    }
+    if (ctx->timing && !t_capturing)
+        HIP_TRY(hipEventRecord(ctx->ev[2], s));
+    HIP_TRY(zero.flush());
+    if (n_streams) {
+        EncParams ep{};
+        ep.syms = static_cast<const uint8_t *>(d_syms);
+        ep.nchunks = n_streams;
+        ep.n_ways = n_ways;
+        ep.scratch = static_cast<uint8_t *>(d_out);
+        ep.out_cap = out_cap;
+        ep.slot_layout = 1u;
+        ep.offsets = d_offsets;
+        ep.lengths = d_lengths;
+        ep.claims = static_cast<unsigned int *>(ctx->enc_status.ptr);
+        ep.sym_offsets = d_sym_offsets;
+        ep.sym_counts = d_sym_counts;
+        ep.slot_offsets = d_slot_offsets;
+        ep.enc_recs = model->d_enc;
+        ep.word_enc_recs = model->d_word_enc;
+        ep.word_small = model->host.word_small ? 1u : 0u;
+        ep.dense256 = model->host.dense256 ? 1u : 0u;
+        ep.alias_remap = static_cast<const uint32_t *>(model->d_remap);
+        ep.alias_recs8 = model->d_alias_recs8;
+        ep.alias_remap16 = static_cast<const uint16_t *>(model->d_alias_remap16);
+        ep.nsyms = model->host.nsyms;
+        ep.scale_bits = model->host.scale_bits;
+        ep.sym_bytes = (uint32_t)model->host.sym_bytes;
+        ep.flags = ctx->d_enc_flags();
+        ep.variant = ctx->variant;
+        HIP_TRY(launch_encode_batch(enc_format, ep, ctx->num_cus, s, &ctx->last_enc_kernel));
+        ctx->last_enc_fused = false;
+        ctx->last_enc_slots = true;
+    }
+    if (ctx->timing && !t_capturing) {
+        HIP_TRY(hipEventRecord(ctx->ev[3], s));
+        ctx->enc_timed = true;
     }
     return RANS_AMD_OK;
 }

@@ -152,9 +152,13 @@ __device__ __forceinline__ void decode_group_word(uint32_t &x, uint32_t &pa, uin
 #undef RANS_WORD_LOOKUP
 
 
-template <int FMT, int K, int OUT>
+// RAGGED (rans_amd_decode_batch): the symbol side of a stream is data as well -- claim k takes stream order[k] (or k), its
+// output position and symbol count come from sym_offsets[] / sym_counts[] instead of c * chunk_syms, and the dword store
+// path is chosen per stream from the output address.  The uniform instantiations never read those fields.
+template <int FMT, int K, int OUT, bool RAGGED = false>
 __global__ void __launch_bounds__(kDecBlockThreads, (K <= 2 ? 8 : 4)) k_decode(const DecParams p)
 {
+    static_assert(!RAGGED || !kIsAdaptive<FMT>, "per-chunk models have no ragged form");
     using Tr = FmtTraits<FMT>;
     using state_t = typename Tr::state_t;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -230,12 +234,33 @@ __global__ void __launch_bounds__(kDecBlockThreads, (K <= 2 ? 8 : 4)) k_decode(c
             break;
         // everything derived from the chunk index is wave-uniform; say so explicitly
         // so it lives in SGPRs and the loop control below is scalar
-        const uint64_t chunk = uniform64(chunk_v);
+        uint64_t chunk = uniform64(chunk_v);
         chunk_v += total_waves; // static stride when there is no counter
+        uint64_t first = chunk * p.chunk_syms;
+        uint32_t nsym = 0;
+        if constexpr (RAGGED) {
+            // the order and the symbol index are the caller's data, like the stream index: an entry that names no stream,
+            // or a symbol range that does not lie inside [0, out_syms), is counted as failed and nothing of it is written
+            bool inside = true;
+            if (p.order) {
+                chunk = uniform64((uint64_t)p.order[chunk]);
+                inside = chunk < p.nchunks;
+            }
+            if (inside) {
+                first = uniform64(p.sym_offsets[chunk]);
+                nsym = uniform(p.sym_counts[chunk]);
+                inside = first <= p.out_syms && nsym <= p.out_syms - first;
+            }
+            if (!inside) { // wave-uniform
+                if (lane == 0)
+                    atomicAdd(p.err_count, 1ull);
+                continue;
+            }
+        } else {
+            nsym = (uint32_t)((p.n - first) < p.chunk_syms ? (p.n - first) : p.chunk_syms);
+        }
         const uint64_t off = uniform64(p.offsets[chunk]);
         const uint32_t len = uniform(p.lengths[chunk]);
-        const uint64_t first = chunk * p.chunk_syms;
-        const uint32_t nsym = (uint32_t)((p.n - first) < p.chunk_syms ? (p.n - first) : p.chunk_syms);
         const uint64_t src = cbase + off;
         uint8_t RANS_GLOBAL *dst = reinterpret_cast<uint8_t RANS_GLOBAL *>(
             reinterpret_cast<uint64_t>(p.out) + first * p.sym_bytes);
@@ -289,13 +314,17 @@ __global__ void __launch_bounds__(kDecBlockThreads, (K <= 2 ? 8 : 4)) k_decode(c
         rounds_done += rounds;
         const uint32_t tail = uniform(nsym - rounds * N);
         uint32_t r = 0;
+        // ragged: a stream whose output is not 4-byte aligned takes the element stores below for all of its rounds
+        bool dword_out = true;
+        if constexpr (RAGGED)
+            dword_out = (uniform((uint32_t)reinterpret_cast<uint64_t>(dst)) & 3u) == 0;
         // sub-steps between two window checkpoints: at most kMaxAdvance bytes are consumed
         constexpr int kCheckEvery = kIsR64<FMT> ? 2 : 4;
 
         if constexpr (OUT == OUT_FAST16) {
             // ---- pairs of full rounds, u16 symbols: lane 2i ends up with round r's symbols of
             // lanes 2i,2i+1 and lane 2i+1 with round r+1's: one dword store per lane and pair
-            const uint32_t pairs = rounds >> 1;
+            const uint32_t pairs = dword_out ? rounds >> 1 : 0u;
             uint8_t RANS_GLOBAL *gdst = dst;
             const uint32_t sel16 = (lane & 1u) ? 0x03020706u : 0x05040100u;
             const uint32_t lane_off16 = ((lane & 1u) * N + (lane & ~1u)) * 2u;
@@ -333,7 +362,7 @@ __global__ void __launch_bounds__(kDecBlockThreads, (K <= 2 ? 8 : 4)) k_decode(c
             r = pairs << 1;
         } else if constexpr (OUT != OUT_SLOW) {
             // ---- groups of 4 full rounds, symbols transposed in registers ----
-            const uint32_t groups = rounds >> 2;
+            const uint32_t groups = dword_out ? rounds >> 2 : 0u;
             // symbol stores go through a descriptor of the chunk's output with the running offset in an SGPR
             // (soffset): no 64-bit VALU pointer arithmetic in the loop
             const rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -458,7 +487,10 @@ __device__ __forceinline__ rsrc_t chunk_rsrc(uint64_t cbase, uint64_t cbytes16, 
 // (eight waves per SIMD at 64 VGPRs with a few spills; a spill-free 72-VGPR build in blocks of 14 waves -- seven per SIMD -- was
 //  1.47 x slower: profiles/r04_word64_launch_bounds.md)
 constexpr int kWord64Threads = kDecBlockThreads;
-__global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64(const DecParams p)
+// (RAGGED: the batch form, reported as k_decode_batch_word64 -- see k_decode's RAGGED: the index entry of a stream gains the
+//  scalar loads of its symbol offset and count, everything else -- the asm rounds, the hand-over -- is shared.)
+template <bool RAGGED>
+__global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64_t(const DecParams p)
 {
     using Tr = FmtTraits<FMT_WORD>;
     constexpr uint32_t N = 64;
@@ -517,6 +549,8 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64(const DecPa
     uint64_t n_idx = 0;               // chunk index
     uint64_t n_off = 0;               // its index entry: scalar loads, i.e. SGPRs from the start
     uint32_t n_len = 0;
+    uint64_t n_first = 0;             // ragged: its symbol range, from the same kind of loads
+    uint32_t n_nsym = 0;
     uint32_t n_x = 0;                 // initial state of this lane (RansDecInit order: lane l's state is the l-th)
     u32x4 n_b0 = {0u, 0u, 0u, 0u}, n_b1 = n_b0; // stream blocks 0 and 1
     bool n_any = false, n_ok = false; // a chunk was claimed / its index entry passed validation and data is on its way
@@ -541,6 +575,35 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64(const DecPa
         n_any = n_idx < p.nchunks;                                                          \
         n_ok = false;                                                                       \
         if (n_any) {                                                                        \
+            if constexpr (RAGGED) {                                                         \
+                bool n_inside = true;                                                       \
+                if (p.order) { /* claim k takes stream order[k]; an entry that names no stream fails */ \
+                    uint32_t n_ord;                                                         \
+                    asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)"         \
+                                 : "=&s"(n_ord)                                             \
+                                 : "s"(uniform64(reinterpret_cast<uint64_t>(p.order + n_idx))) \
+                                 : "memory");                                               \
+                    n_idx = uniform64((uint64_t)uniform(n_ord));                            \
+                    n_inside = n_idx < p.nchunks;                                           \
+                }                                                                           \
+                if (n_inside) { /* the stream entry and, beside it, the symbol entry */     \
+                    asm volatile("s_load_dwordx2 %0, %4, 0x0\n\ts_load_dword %1, %5, 0x0\n\t" \
+                                 "s_load_dwordx2 %2, %6, 0x0\n\ts_load_dword %3, %7, 0x0\n\ts_waitcnt lgkmcnt(0)" \
+                                 : "=&s"(n_off), "=&s"(n_len), "=&s"(n_first), "=&s"(n_nsym) \
+                                 : "s"(uniform64(reinterpret_cast<uint64_t>(p.offsets + n_idx))), \
+                                   "s"(uniform64(reinterpret_cast<uint64_t>(p.lengths + n_idx))), \
+                                   "s"(uniform64(reinterpret_cast<uint64_t>(p.sym_offsets + n_idx))), \
+                                   "s"(uniform64(reinterpret_cast<uint64_t>(p.sym_counts + n_idx))) \
+                                 : "memory");                                               \
+                    n_off = uniform64(n_off);                                               \
+                    n_len = uniform(n_len);                                                 \
+                    n_first = uniform64(n_first);                                           \
+                    n_nsym = uniform(n_nsym);                                               \
+                    n_inside = n_first <= p.out_syms && n_nsym <= p.out_syms - n_first;     \
+                }                                                                           \
+                n_ok = n_inside && ((n_off & 1u) == 0) && (n_len >= N * Tr::kStateBytes) && (n_off <= p.container_bytes) && \
+                       (n_len <= p.container_bytes - n_off);                                \
+            } else {                                                                        \
             asm volatile("s_load_dwordx2 %0, %2, 0x0\n\ts_load_dword %1, %3, 0x0\n\ts_waitcnt lgkmcnt(0)" \
                          : "=&s"(n_off), "=&s"(n_len)                                       \
                          : "s"(uniform64(reinterpret_cast<uint64_t>(p.offsets + n_idx))),   \
@@ -550,6 +613,7 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64(const DecPa
             n_len = uniform(n_len);                                                         \
             n_ok = ((n_off & 1u) == 0) && (n_len >= N * Tr::kStateBytes) && (n_off <= p.container_bytes) && \
                    (n_len <= p.container_bytes - n_off);                                    \
+            }                                                                               \
             if (n_ok) {                                                                     \
                 n_x = *(reinterpret_cast<const uint32_t RANS_GLOBAL *>(cbase + n_off) + lane); \
                 StreamWindow::prefetch(chunk_rsrc(cbase, cbytes16, n_off, n_len), lane, n_b0, n_b1); \
@@ -576,12 +640,14 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64(const DecPa
         StreamWindow W;
         W.install(ring, chunk_rsrc(cbase, cbytes16, n_off, n_len), c_skip + N * Tr::kStateBytes, lane, n_b0, n_b1);
         uint32_t x = n_x;
-        const uint64_t first_sym = c_idx * p.chunk_syms;
-        const uint32_t nsym = uniform((uint32_t)((p.n - first_sym) < p.chunk_syms ? (p.n - first_sym) : p.chunk_syms));
+        const uint64_t first_sym = RAGGED ? uniform64(n_first) : c_idx * p.chunk_syms;
+        const uint32_t nsym = RAGGED ? uniform(n_nsym)
+                                     : uniform((uint32_t)((p.n - first_sym) < p.chunk_syms ? (p.n - first_sym) : p.chunk_syms));
         uint8_t RANS_GLOBAL *dst = reinterpret_cast<uint8_t RANS_GLOBAL *>(reinterpret_cast<uint64_t>(p.out) + first_sym);
         const uint32_t rounds = uniform(nsym / N);
         const uint32_t tail = uniform(nsym - rounds * N);
-        const uint32_t groups = rounds >> 2;
+        // (ragged: a stream whose output is not 4-byte aligned takes the element stores below for all of its rounds)
+        const uint32_t groups = (!RAGGED || (uniform((uint32_t)reinterpret_cast<uint64_t>(dst)) & 3u) == 0) ? rounds >> 2 : 0u;
         rounds_done += rounds;
         n_any = false;
         n_ok = false;
@@ -659,24 +725,29 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64(const DecPa
     record_span(p, t_start, smem);
 }
 
+constexpr auto k_decode_word64 = k_decode_word64_t<false>;
+constexpr auto k_decode_batch_word64 = k_decode_word64_t<true>;
+
+template <bool RAGGED = false>
 hipError_t launch_decode_word64(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {
+    auto kern = RAGGED ? k_decode_batch_word64 : k_decode_word64;
     const uint32_t t0 = (p.table0_bytes + 15u) & ~15u;
     const uint32_t waves = kWord64Threads / 64;
     const size_t lds = (size_t)t0 + (size_t)waves * kRingStride;
     static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(k_decode_word64), 160 * 1024, lds_ok); e != hipSuccess)
+    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
         return e;
     const uint64_t want = (p.nchunks + waves - 1) / waves;
     const uint64_t cap = (uint64_t)num_cus * 2u;
     const uint32_t grid = (uint32_t)(want < cap ? (want ? want : 1) : cap);
     if (name)
         *name = "k_decode_word64";
-    RANS_LAUNCH(k_decode_word64, dim3(grid), dim3(kWord64Threads), lds, stream, p);
+    RANS_LAUNCH(kern, dim3(grid), dim3(kWord64Threads), lds, stream, p);
     return hipGetLastError();
 }
 
-template <int FMT, int K, int OUT>
+template <int FMT, int K, int OUT, bool RAGGED = false>
 hipError_t launch_decode_t(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {
     // per-chunk models: every wave owns its tables (5 KiB) and window, nothing is shared -- workgroups of FOUR waves, five of
@@ -693,7 +764,7 @@ hipError_t launch_decode_t(const DecParams &p, int num_cus, hipStream_t stream, 
     const size_t lds = (size_t)t0 + t1 + (size_t)waves * kRingStride;
     if (lds > 160 * 1024)
         return hipErrorInvalidValue;
-    auto kern = k_decode<FMT, K, OUT>;
+    auto kern = k_decode<FMT, K, OUT, RAGGED>;
     static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
     if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
         return e;
@@ -705,7 +776,7 @@ hipError_t launch_decode_t(const DecParams &p, int num_cus, hipStream_t stream, 
     uint64_t want = (p.nchunks + waves - 1) / waves;
     uint64_t cap = (uint64_t)num_cus * blocks_per_cu;
     const uint32_t grid = (uint32_t)(want < cap ? (want ? want : 1) : cap);
-    if (name)
+    if (name && !RAGGED) // (the batch launcher reports its own names: launch_decode_batch_wave)
         *name = FMT == FMT_WORD ? "k_decode<word>" : FMT == FMT_BYTE ? "k_decode<byte>" : FMT == FMT_BYTEF ? "k_decode<byte, slot records>"
                 : FMT == FMT_R64 ? "k_decode<r64>" : FMT == FMT_R64S ? "k_decode<r64 search>"
                 : FMT == FMT_WORD16 ? "k_decode<word, u16 symbols>"
@@ -761,7 +832,81 @@ template <int FMT> hipError_t launch_decode_f(const DecParams &p, int num_cus, h
 }
 
 
+// Ragged batches: the store path is chosen per stream inside the kernel, so the launcher goes by the interleave and the
+// symbol width alone -- full waves get the kernel with the transposed dword stores, every other lane count the general one.
+template <int FMT> hipError_t launch_decode_batch_f(const DecParams &p, int num_cus, hipStream_t s)
+{
+    constexpr bool kHasFast = FMT != FMT_R64S; // (the search decoder exists in its general form only)
+    if constexpr (FMT == FMT_ALIAS) { // (u16 symbols: the paired-round stores for the alias format and, below, the word format)
+        if (p.sym_bytes == 2) {
+            switch (p.n_ways) {
+            case 64: return launch_decode_t<FMT, 1, OUT_FAST16, true>(p, num_cus, s, nullptr);
+            case 128: return launch_decode_t<FMT, 2, OUT_FAST16, true>(p, num_cus, s, nullptr);
+            default: break;
+            }
+        }
+    }
+    if constexpr (FMT == FMT_WORD16) {
+        switch (p.n_ways) {
+        case 64: return launch_decode_t<FMT, 1, OUT_FAST16, true>(p, num_cus, s, nullptr);
+        case 128: return launch_decode_t<FMT, 2, OUT_FAST16, true>(p, num_cus, s, nullptr);
+        default: break;
+        }
+    }
+    const bool fast = kHasFast && p.sym_bytes == 1;
+    if constexpr (kHasFast && FMT != FMT_WORD16) {
+        if (fast) {
+            switch (p.n_ways) {
+            case 64:
+                if constexpr (FMT == FMT_WORD)
+                    return launch_decode_word64<true>(p, num_cus, s, nullptr);
+                else
+                    return launch_decode_t<FMT, 1, OUT_FAST8, true>(p, num_cus, s, nullptr);
+            case 128: return launch_decode_t<FMT, 2, OUT_FAST8, true>(p, num_cus, s, nullptr);
+            case 256: return launch_decode_t<FMT, 4, OUT_FAST8, true>(p, num_cus, s, nullptr);
+            case 512: return launch_decode_t<FMT, 8, OUT_FAST8, true>(p, num_cus, s, nullptr);
+            default: break;
+            }
+        }
+    }
+    if (p.n_ways >= 1 && p.n_ways <= 64)
+        return launch_decode_t<FMT, 1, OUT_SLOW, true>(p, num_cus, s, nullptr);
+    if (p.n_ways <= 128)
+        return launch_decode_t<FMT, 2, OUT_SLOW, true>(p, num_cus, s, nullptr);
+    if (p.n_ways <= 256)
+        return launch_decode_t<FMT, 4, OUT_SLOW, true>(p, num_cus, s, nullptr);
+    if (p.n_ways <= 512)
+        return launch_decode_t<FMT, 8, OUT_SLOW, true>(p, num_cus, s, nullptr);
+    return hipErrorInvalidValue;
+}
+
 } // namespace
+
+hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+{
+    if (!p.sym_offsets || !p.sym_counts)
+        return hipErrorInvalidValue;
+    const bool word64 = format == FMT_WORD && p.n_ways == 64 && p.sym_bytes == 1;
+    if (batch_kernel)
+        *batch_kernel = word64                ? "k_decode_batch_word64"
+                        : format == FMT_WORD  ? "k_decode_batch<word>"
+                        : format == FMT_BYTE  ? "k_decode_batch<byte>"
+                        : format == FMT_BYTEF ? "k_decode_batch<byte, slot records>"
+                        : format == FMT_R64   ? "k_decode_batch<r64>"
+                        : format == FMT_R64S  ? "k_decode_batch<r64 search>"
+                        : format == FMT_WORD16 ? "k_decode_batch<word, u16 symbols>"
+                                              : "k_decode_batch<alias>";
+    switch (format) {
+    case FMT_WORD: return launch_decode_batch_f<FMT_WORD>(p, num_cus, stream);
+    case FMT_BYTE: return launch_decode_batch_f<FMT_BYTE>(p, num_cus, stream);
+    case FMT_BYTEF: return launch_decode_batch_f<FMT_BYTEF>(p, num_cus, stream);
+    case FMT_R64: return launch_decode_batch_f<FMT_R64>(p, num_cus, stream);
+    case FMT_R64S: return launch_decode_batch_f<FMT_R64S>(p, num_cus, stream);
+    case FMT_WORD16: return launch_decode_batch_f<FMT_WORD16>(p, num_cus, stream);
+    case FMT_ALIAS: return launch_decode_batch_f<FMT_ALIAS>(p, num_cus, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t launch_decode_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {

@@ -30,6 +30,17 @@ hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_
     return launch_decode_wave(format, p, num_cus, stream, kernel_name);
 }
 
+// ragged batches: the wave-per-stream kernels, whatever the interleave (ragged group / lane kernels are later work)
+hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+{
+    return launch_decode_batch_wave(format, p, num_cus, stream, batch_kernel);
+}
+
+hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+{
+    return launch_encode_batch_wave(format == kKernelFormatWord16 ? (int)RANS_AMD_FMT_WORD : format, p, num_cus, stream, batch_kernel);
+}
+
 // Fused placement needs a mailbox for the block's coders and copier (encode_wave.hip launch_encode_t computes the same
 // sizes).  It lives behind the tables in LDS where there is room; the alias tables of a 16-bit model over 4096 symbols
 // fill the CU's 160 KiB to the last byte (config 4), and that kernel keeps its mailbox in global memory (round 3; a push

@@ -90,6 +90,9 @@ constexpr int enc_fused_waves_per_simd(int K) { return K == 1 ? 8 : (K <= 4 ? 4 
 //         still lies inside the slot -- exactly where the stream is staged in LDS (the flush knows what it is about to
 //         write), by the round's worst case elsewhere -- and a chunk that does not fit is abandoned and listed for the
 //         second launch (EncParams::redo), which codes the listed chunks into worst-case slots behind the sized ones.
+// MODE 4: MODE 2 for a ragged batch (rans_amd_encode_batch): stream c's symbols are sym_counts[c] at sym_offsets[c] and its
+//         slot is [slot_offsets[c], slot_offsets[c + 1]) -- both the caller's data: a slot that is misplaced, lies outside
+//         out_cap or is smaller than the worst case of its stream is not written at all (flags bit 1, RANS_AMD_E_SPACE).
 template <int FMT, int K, int MODE>
 __global__ void __launch_bounds__(FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (MODE != 0 ? kEncFusedThreads : kEncBlockThreads),
                                   (MODE != 0 && FMT != FMT_ALIAS_LDS) ? enc_fused_waves_per_simd(K) : 1)
@@ -100,6 +103,7 @@ __global__ void __launch_bounds__(FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (
     constexpr bool FUSED = MODE == 1;
     constexpr bool DYNAMIC = MODE != 0; // chunks are claimed from EncParams::claims
     constexpr bool SIZED = MODE == 3;   // slots of the caller's size: overflow checks, abandoned chunks, the redo launch
+    constexpr bool RAGGED = MODE == 4;  // per-stream symbol ranges and slots
     constexpr uint32_t kMaxEmit = kIsR64<FMT> ? 4u : 2u; // bytes one symbol can push out of one state (scale_bits <= 16 for the byte formats)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     uint32_t redo_todo = 0; // redo launch: listed chunks this launch codes
@@ -267,15 +271,36 @@ __global__ void __launch_bounds__(FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (
         if (chunk_v >= p.nchunks)
             break;
         const uint64_t chunk = uniform64(chunk_v);
-        const uint64_t first = chunk * p.chunk_syms;
-        const uint32_t nsym = (uint32_t)((p.n - first) < p.chunk_syms ? (p.n - first) : p.chunk_syms);
+        uint64_t first = chunk * p.chunk_syms;
+        uint32_t nsym = 0;
+        uint64_t slot_size = p.slot_bytes, ragged_at = 0;
+        if constexpr (RAGGED) {
+            first = uniform64(p.sym_offsets[chunk]);
+            nsym = uniform(p.sym_counts[chunk]);
+            ragged_at = uniform64(p.slot_offsets[chunk]);
+            const uint64_t slot_end = uniform64(p.slot_offsets[chunk + 1]);
+            // what rans_amd_chunk_bound() asks for this stream: units per symbol (2 bytes, 4 for rans64) + the flushed states
+            const uint64_t need = ((uint64_t)nsym * (kIsR64<FMT> ? 4u : 2u) + (uint64_t)p.n_ways * Tr::kStateBytes + 15u) & ~15ull;
+            slot_size = slot_end - ragged_at;
+            if (((ragged_at | slot_end) & 15u) != 0 || slot_end < ragged_at || slot_end > p.out_cap || slot_size < need || slot_size > 0xfffffff0ull) {
+                if (lane == 0) { // wave-uniform: nothing of this stream is written
+                    atomicOr(p.flags, 2u);
+                    p.lengths[chunk] = 0u;
+                    p.offsets[chunk] = slot_end;
+                }
+                continue;
+            }
+        } else {
+            nsym = (uint32_t)((p.n - first) < p.chunk_syms ? (p.n - first) : p.chunk_syms);
+        }
         const uint8_t RANS_GLOBAL *src = (const uint8_t RANS_GLOBAL *)p.syms + first * p.sym_bytes;
         const uint32_t ring_j = (FUSED && p.ring_slots) ? coded % p.ring_slots : 0u;
         const uint64_t slot_no = (FUSED && p.ring_slots) ? ((uint64_t)blockIdx.x * waves_per_block + wave) * p.ring_slots + ring_j : chunk;
         // (sized slots, redo launch: the overflow region behind the sized slots, one worst-case slot per listed chunk)
-        const uint64_t slot_at = (SIZED && p.redo) ? p.ovf_base + (uint64_t)redo_slot * p.slot_bytes : uniform64(slot_no) * p.slot_bytes;
+        const uint64_t slot_at = RAGGED ? ragged_at
+                                 : (SIZED && p.redo) ? p.ovf_base + (uint64_t)redo_slot * p.slot_bytes : uniform64(slot_no) * p.slot_bytes;
         uint8_t RANS_GLOBAL *slot = (uint8_t RANS_GLOBAL *)p.scratch + slot_at;
-        uint32_t wp = (uint32_t)p.slot_bytes;
+        uint32_t wp = (uint32_t)slot_size;
         bool ovf = false; // SIZED, wave-uniform: the chunk's stream does not fit its slot
         // SIZED, the coders that store every round's units themselves: 0, or ~0 from the pair of rounds on before which the slot no
         // longer had room for what two rounds can emit at most -- OR-ed into the renormalisation thresholds, so that nothing
@@ -302,15 +327,18 @@ __global__ void __launch_bounds__(FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (
         // arrive as one coalesced dword per lane and are transposed in registers; loads run
         // one super-group (16 rounds) ahead of the arithmetic.
         // (N == 64 K exactly: with N = 192 on the K = 4 kernel the fourth sub-step has no lanes)
+        // (ragged: every stream starts where its index says -- its own first symbol decides)
         const bool fast_in = p.sym_bytes == 1 && N == 64u * K &&
-                             ((reinterpret_cast<uintptr_t>(p.syms) | p.chunk_syms) & 3u) == 0;
+                             ((RAGGED ? (uintptr_t)uniform((uint32_t)reinterpret_cast<uintptr_t>(src))
+                                      : (reinterpret_cast<uintptr_t>(p.syms) | p.chunk_syms)) & 3u) == 0;
         // (the word path addresses its record table by raw LDS address: dynamic LDS must start at 0)
         const bool lds_at_zero = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t *)smem == 0u;
         // The same for u16 symbols (alias coding over more than 256 symbols): two rounds per dword, lane pairs
         // swap halves (the mirror image of the decoder's OUT_FAST16 stores).
         // (K <= 2: sixteen rounds in flight twice over are 32 K registers)
         const bool fast_in16 = (kIsAlias<FMT> || FMT == FMT_WORD) && K <= 2 && p.sym_bytes == 2 && N == 64u * K &&
-                               ((reinterpret_cast<uintptr_t>(p.syms) | (p.chunk_syms * 2u)) & 3u) == 0;
+                               ((RAGGED ? (uintptr_t)uniform((uint32_t)reinterpret_cast<uintptr_t>(src))
+                                        : (reinterpret_cast<uintptr_t>(p.syms) | (p.chunk_syms * 2u))) & 3u) == 0;
         const uint32_t fast_rounds =
             ((fast_in && (FMT != FMT_WORD || lds_at_zero)) || fast_in16) ? (rounds & ~15u) : 0u;
 
@@ -664,12 +692,12 @@ __global__ void __launch_bounds__(FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (
                 }
             }
         }
-        const uint32_t len = (uint32_t)p.slot_bytes - wp;
+        const uint32_t len = (uint32_t)slot_size - wp;
         if (lane == 0)
             p.lengths[chunk] = len;
         if (p.slot_layout && lane == 0) { // the slot is the chunk's place: the stream is [slot end - len, slot end)
             p.offsets[chunk] = slot_at + wp;
-            if (chunk + 1 == p.nchunks && !(SIZED && p.redo)) // (sized slots: the redo launch has the last word on the end)
+            if (chunk + 1 == p.nchunks && !(SIZED && p.redo) && !RAGGED) // (sized slots: the redo launch has the last word on the end)
                 p.offsets[p.nchunks] = p.nchunks * p.slot_bytes;
         }
         if constexpr (FUSED) {
@@ -697,6 +725,7 @@ template <int FMT, int K> hipError_t launch_encode_t(const EncParams &p, int num
 {
     const bool fused = p.status != nullptr;
     const bool slots = !fused && p.slot_layout && p.claims; // MODE 2: dynamic claims, no copiers
+    const bool ragged = slots && p.slot_offsets;            // MODE 4: ... per-stream symbol ranges and slots
     const bool sized = slots && p.ovf_ctl;                  // MODE 3: ... slots of the caller's size
     const bool dynamic = fused || slots;
     const uint32_t threads = FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (dynamic ? kEncFusedThreads : kEncBlockThreads);
@@ -748,6 +777,16 @@ template <int FMT, int K> hipError_t launch_encode_t(const EncParams &p, int num
         RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, q);
         return hipGetLastError();
     }
+    if (ragged) {
+        if (!p.sym_offsets || !p.sym_counts || p.ovf_ctl)
+            return hipErrorInvalidValue;
+        auto kern = k_encode<FMT, K, 4>;
+        static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), (int)lds_cap, lds_ok); e != hipSuccess)
+            return e;
+        RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, q);
+        return hipGetLastError();
+    }
     if (sized) {
         auto kern = k_encode<FMT, K, 3>;
         static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
@@ -767,6 +806,8 @@ template <int FMT, int K> hipError_t launch_encode_t(const EncParams &p, int num
     } else if (fused || slots) {
         return hipErrorInvalidValue;
     }
+    if (p.slot_offsets) // (a ragged request that did not reach MODE 4)
+        return hipErrorInvalidValue;
     auto kern = k_encode<FMT, K, 0>;
     static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
     if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), (int)lds_cap, lds_ok); e != hipSuccess)
@@ -812,6 +853,21 @@ hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipSt
     //  its encoder tables in LDS form, model.cpp; the lane encoders keep their own gather for narrow interleaves)
     default: return hipErrorInvalidValue;
     }
+}
+
+// ragged batches (k_encode's MODE 4): the same kernels under names of their own
+hipError_t launch_encode_batch_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+{
+    if (!p.slot_offsets || !p.sym_offsets || !p.sym_counts || !p.slot_layout || !p.claims || p.status || p.chunk_freqs ||
+        format == FMT_WORDA)
+        return hipErrorInvalidValue;
+    if (batch_kernel)
+        *batch_kernel = format == FMT_WORD   ? "k_encode_batch<word>"
+                        : format == FMT_BYTE ? "k_encode_batch<byte>"
+                        : format == FMT_R64  ? "k_encode_batch<r64>"
+                        : format == FMT_R64S ? "k_encode_batch<r64 full-width>"
+                                             : "k_encode_batch<alias, LDS remap>";
+    return launch_encode_wave(format, p, num_cus, stream, nullptr);
 }
 
 } // namespace rans_amd

@@ -95,6 +95,12 @@ struct DecParams {
     unsigned long long *span_reset;   // the span record of a LATER launch that this launch zeroes
     unsigned long long *trace;        // wave clocks: per wave kTraceWords words {start, end (100 MHz ticks), xcc,
                                       // shader cycles, 64-symbol rounds}; NULL = off (wave-per-chunk kernels only)
+    // Ragged batches (rans_amd_decode_batch; the k_decode_batch* kernels, nobody else reads these): stream c decodes
+    // sym_counts[c] symbols to out + sym_offsets[c] * sym_bytes, inside [0, out_syms); claim k takes stream order[k]
+    const uint64_t *sym_offsets;
+    const uint32_t *sym_counts;
+    const uint32_t *order;            // or NULL: claim k takes stream k
+    uint64_t out_syms;
 };
 
 struct EncParams {
@@ -164,6 +170,12 @@ struct EncParams {
     uint32_t redo;              // 1 = the second launch
     uint64_t ovf_base;          // redo: byte offset of the overflow region (= nchunks * the first launch's slot_bytes)
     uint32_t no_lanes;          // the request goes to the wave encoders whatever its interleave (sized slots the lane encoders cannot take)
+    // Ragged batches (rans_amd_encode_batch; k_encode's MODE 4, nobody else reads these): stream c codes the sym_counts[c]
+    // symbols at syms + sym_offsets[c] * sym_bytes into the slot [slot_offsets[c], slot_offsets[c + 1]) of `scratch` (the
+    // caller's container, out_cap bytes), ending at the slot's end
+    const uint64_t *sym_offsets;
+    const uint32_t *sym_counts;
+    const uint64_t *slot_offsets; // [nchunks + 1], multiples of 16
 };
 constexpr uint32_t kEncFusedThreads = 512; // 7 encoder waves + 1 copier wave; 4 blocks per CU
 constexpr uint32_t kEncFusedCopiers16 = 2; // copier waves of a 16-wave block
@@ -235,6 +247,15 @@ bool encode_lanes_can_fuse(int format, const EncParams &p, int num_cus); // lane
 hipError_t launch_layout(const LayoutParams &p, hipStream_t stream);
 uint32_t layout_blocks(uint64_t nchunks); // blocks (and block_sums entries) launch_layout uses
 hipError_t launch_compact(const CompactParams &p, int num_cus, hipStream_t stream);
+// Ragged batches (rans_amd_decode_batch / rans_amd_encode_batch): always one stream per wave, whatever the interleave;
+// *batch_kernel receives the name of the kernel that was launched.  `format` is the kernel-side format number.
+hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
+hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
+// rans_amd_batch_order: a permutation of the stream indices in which floor(log2(count + 1)) never increases.
+// d_hist: 2 * kOrderBuckets words of workspace.
+constexpr uint32_t kOrderBuckets = 33;
+hipError_t launch_batch_order(const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t *d_order, uint32_t *d_hist, int num_cus,
+                              hipStream_t stream);
 hipError_t launch_histogram(const void *syms, uint64_t n, int sym_bytes, uint32_t nsyms, uint32_t *d_hist,
                             uint32_t *d_flags, int num_cus, hipStream_t stream);
 
