@@ -45,6 +45,13 @@ int hip_fail(hipError_t e, const char *where)
             return hip_fail(e__, #expr);                \
     } while (0)
 
+// ... and for a step that returns a status of this ABI (the message is already in place)
+#define RC_TRY(expr)                                    \
+    do {                                                \
+        if (int rc__ = (expr))                          \
+            return rc__;                                \
+    } while (0)
+
 // Stream capture (hipStreamBeginCapture ... EndCapture around calls of this library: the launches become nodes of a
 // hipGraph).  What a captured call may not do is what a graph cannot replay: allocate, wait for the stream, read
 // anything back.  The entry points find out once per call (CaptureScope) and the workspaces refuse to grow meanwhile
@@ -207,14 +214,6 @@ struct ZeroList {
     }
 };
 
-// counter slot of a launch that is being captured (kernels.h kCaptureSlots: that many captured launches of one context
-// may run at the same time)
-unsigned int *capture_counters(rans_amd_ctx *ctx)
-{
-    unsigned int *ring = reinterpret_cast<unsigned int *>(ctx->d_words + 256);
-    return ring + (size_t)(kWorkSlots + ctx->capture_seq++ % kCaptureSlots) * kWorkSlotWords;
-}
-
 struct DeviceGuard {
     int prev = -1;
     bool ok = true;
@@ -266,6 +265,230 @@ uint64_t empty_stream(int format, uint32_t n_ways, uint8_t *dst)
 }
 
 uint32_t state_bytes(int format) { return format == RANS_AMD_FMT_R64 ? 8u : 4u; }
+
+/* ---- what the decode entry points share: plain steps, called in sequence ---- */
+
+// the kernel-side format number of a model's decoders (kernels.h kKernelFormat*)
+int decoder_kernel_format(const rans_amd_model *model)
+{
+    const HostModel &h = model->host;
+    return h.r64_search ? kKernelFormatR64Search : (h.format == RANS_AMD_FMT_WORD && h.sym_bytes == 2) ? kKernelFormatWord16 : h.format;
+}
+
+// the model's own decode tables and what the kernels need to know about them
+void fill_decoder_tables(DecParams &dp, const rans_amd_model *model)
+{
+    dp.table0 = model->d_table0;
+    dp.table1 = model->d_table1 ? model->d_table1 : model->d_table0;
+    dp.table0_bytes = model->table0_bytes;
+    dp.table1_bytes = model->table1_bytes;
+    dp.scale_bits = model->host.scale_bits;
+    dp.log2nsyms = model->host.log2nsyms;
+    if (model->host.r64_search) { // log2 of the padded cum table
+        dp.log2nsyms = 0;
+        while ((1u << dp.log2nsyms) < model->host.cum_padded.size())
+            dp.log2nsyms++;
+    }
+    dp.sym_bytes = (uint32_t)model->host.sym_bytes;
+}
+
+// byte format: the fused slot records (one gather per symbol) in place of cum2sym + records; returns the kernel format
+// that reads them.  When they are worth it is the caller's question.
+int use_byte_fused_tables(DecParams &dp, const rans_amd_model *model)
+{
+    dp.table0 = model->d_fused;
+    dp.table0_bytes = (uint32_t)(model->host.byte_slots.size() * sizeof(WordSlot));
+    dp.table1 = model->d_fused;
+    dp.table1_bytes = 0;
+    return kKernelFormatByteFused;
+}
+
+// one 64-byte line per resident decoder wave (small, allocated once, kept: not part of what rans_amd_ctx_trim drops)
+int use_wave_scratch(rans_amd_ctx *ctx, DecParams &dp)
+{
+    RC_TRY(ctx->wave_scratch.reserve((size_t)ctx->num_cus * 2u * (kDecBlockThreads / 64) * 64u));
+    dp.wave_scratch = static_cast<uint8_t *>(ctx->wave_scratch.ptr);
+    return RANS_AMD_OK;
+}
+
+// Dynamic chunk hand-out: a decoder claims its chunks from counters that must be zero when it starts.  The counters form a
+// ring of kWorkSlots slots at d_words + 256 (all zero at context creation), shared by every decode launch of the context
+// whatever its kernel family: eager launch i claims from slot i % 64 and re-zeroes slot (i + 32) % 64 from inside the
+// kernel, so no memset node is needed and up to 32 decode launches may be in flight at once (launch_decoder moves the ring
+// on).  A launch that becomes a graph node runs again and again with these very arguments: its counters are one of the
+// kCaptureSlots slots behind the ring (that many captured launches of one context may run at the same time), zeroed by a
+// k_zero node in front of the kernel -- every replay starts from zero, and the eager ring never sees a slot a replay used.
+int take_counter_slot(rans_amd_ctx *ctx, const CaptureScope &capture, hipStream_t s, DecParams &dp)
+{
+    unsigned int *ring = reinterpret_cast<unsigned int *>(ctx->d_words + 256);
+    if (capture.active) {
+        dp.work_counter = ring + (size_t)(kWorkSlots + ctx->capture_seq++ % kCaptureSlots) * kWorkSlotWords;
+        ZeroList zero(s);
+        HIP_TRY(zero.add(dp.work_counter, (uint64_t)kWorkSlotWords * 4));
+        HIP_TRY(zero.flush());
+    } else {
+        dp.work_counter = ring + (size_t)(ctx->launch_seq % kWorkSlots) * kWorkSlotWords;
+        dp.work_counter_reset = ring + (size_t)((ctx->launch_seq + kWorkSlots / 2) % kWorkSlots) * kWorkSlotWords;
+        dp.span_reset = reinterpret_cast<unsigned long long *>(dp.work_counter_reset + kWorkPools * kWorkPoolStride);
+    }
+    // the slot's last line: first wave start / last wave end of the launch (rans_amd_launch_spans)
+    dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
+    return RANS_AMD_OK;
+}
+
+// launch_decode or launch_decode_batch (kernels.h)
+typedef hipError_t (*DecodeLauncher)(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **kernel_name);
+
+// time (rans_amd_set_timing), launch, advance the counter ring
+int launch_decoder(rans_amd_ctx *ctx, const CaptureScope &capture, hipStream_t s, DecodeLauncher launch, int dec_format,
+                   const DecParams &dp)
+{
+    if (ctx->timing && !t_capturing)
+        HIP_TRY(hipEventRecord(ctx->ev[0], s));
+    HIP_TRY(launch(dec_format, dp, ctx->num_cus, s, &ctx->last_kernel));
+    // the launch that uses slot i zeroes slot i + 32: move on only once it really is in the stream,
+    // or a later launch would start from a counter nobody reset
+    if (dp.work_counter && !capture.active)
+        ctx->launch_seq++;
+    if (ctx->timing && !t_capturing) {
+        HIP_TRY(hipEventRecord(ctx->ev[1], s));
+        ctx->dec_timed = true;
+    }
+    return RANS_AMD_OK;
+}
+
+// the decoders' error counter: read, cleared for the next call, waited for (the caller holds ctx->mu); `corrupt` is the
+// entry point's own message for a count that is not zero
+int read_bad_count(rans_amd_ctx *ctx, hipStream_t s, uint64_t *h_bad, const char *corrupt)
+{
+    unsigned long long bad = 0;
+    HIP_TRY(hipMemcpyAsync(&bad, ctx->d_err(), 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemsetAsync(ctx->d_err(), 0, 8, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *h_bad = bad;
+    return bad ? fail(RANS_AMD_E_CORRUPT, corrupt) : RANS_AMD_OK;
+}
+
+// wave clocks (rans_amd_set_timing(ctx, 2)) and the debug timeline (RANS_AMD_TRACE=<file>): the per-wave records of the
+// launch just made (start/end ticks, XCD, shader cycles, rounds), read back after a sync
+int read_wave_trace(rans_amd_ctx *ctx, hipStream_t s, const unsigned long long *d_trace, size_t trace_words, const char *trace_path)
+{
+    std::vector<unsigned long long> host(trace_words);
+    HIP_TRY(hipMemcpyAsync(host.data(), d_trace, trace_words * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    rans_amd_wave_clocks wc = {0, 0, 0, 0.0, 0.0};
+    unsigned long long t_first = ~0ull, t_last = 0, longest_ticks = 0, longest_cycles = 0;
+    for (size_t w = 0; w < trace_words / kTraceWords; ++w) {
+        const unsigned long long *t = &host[kTraceWords * w];
+        if (!t[1])
+            continue; // this slot's wave never ran (grid smaller than the buffer) or is not instrumented
+        wc.waves++;
+        wc.shader_cycles += t[3];
+        wc.rounds += t[4];
+        t_first = t[0] < t_first ? t[0] : t_first;
+        t_last = t[1] > t_last ? t[1] : t_last;
+        if (t[1] - t[0] > longest_ticks) {
+            longest_ticks = t[1] - t[0];
+            longest_cycles = t[3];
+        }
+    }
+    if (wc.waves && longest_ticks) {
+        wc.sclk_hz = (double)longest_cycles / ((double)longest_ticks * 1e-8); // wall_clock64 ticks at 100 MHz
+        wc.kernel_ticks_ms = (double)(t_last - t_first) * 1e-5;
+    }
+    ctx->wave_clocks = wc;
+    if (trace_path) {
+        if (FILE *f = fopen(trace_path, "w")) {
+            for (size_t w = 0; w < trace_words / kTraceWords; ++w)
+                if (host[kTraceWords * w + 1])
+                    fprintf(f, "%zu %llu %llu %llu %llu %llu\n", w, host[kTraceWords * w], host[kTraceWords * w + 1],
+                            host[kTraceWords * w + 2], host[kTraceWords * w + 3], host[kTraceWords * w + 4]);
+            fclose(f);
+        }
+    }
+    return RANS_AMD_OK;
+}
+
+/* ---- ... and the encode entry points ---- */
+
+// the kernel-side format number of a model's encoders: the decoders', but for an alias model with LDS tables
+int encoder_kernel_format(const rans_amd_model *model)
+{
+    const int format = decoder_kernel_format(model);
+    return format == RANS_AMD_FMT_ALIAS && model->d_alias_remap16 ? kKernelFormatAliasLds : format;
+}
+
+// the model's encoder tables and what the kernels need to know about them
+void fill_encoder_model(EncParams &ep, const rans_amd_model *model)
+{
+    ep.enc_recs = model->d_enc;
+    ep.word_enc_recs = model->d_word_enc;
+    ep.word_small = model->host.word_small ? 1u : 0u;
+    ep.dense256 = model->host.dense256 ? 1u : 0u;
+    ep.alias_remap = static_cast<const uint32_t *>(model->d_remap);
+    ep.alias_recs8 = model->d_alias_recs8;
+    ep.alias_remap16 = static_cast<const uint16_t *>(model->d_alias_remap16);
+    ep.nsyms = model->host.nsyms;
+    ep.scale_bits = model->host.scale_bits;
+    ep.sym_bytes = (uint32_t)model->host.sym_bytes;
+}
+
+// The claim counters the wave / group / batch encoders hand their chunks out through, at the start of ctx->enc_status
+// (EncParams::claims): a line per pool, and two more -- sized slots keep their overflow count and the redo launch's claim
+// counter there (EncParams::ovf_ctl).
+constexpr size_t kClaimBlockBytes = (size_t)(kWorkPools + 2) * kWorkPoolStride * 4;
+
+// the offsets of chunks of these lengths laid end to end (k_layout), the total behind them; bit 1 of *flags when it exceeds out_cap
+int layout_offsets(rans_amd_ctx *ctx, hipStream_t s, uint64_t nchunks, const uint32_t *d_lengths, uint64_t *d_offsets, uint64_t out_cap,
+                   uint32_t *flags)
+{
+    LayoutParams lp;
+    lp.lengths = d_lengths;
+    lp.offsets = d_offsets;
+    lp.nchunks = nchunks;
+    lp.out_cap = out_cap;
+    lp.flags = flags;
+    lp.block_sums = nullptr;
+    if (layout_blocks(nchunks) > 1) {
+        RC_TRY(ctx->layout_sums.reserve((size_t)layout_blocks(nchunks) * 8));
+        lp.block_sums = static_cast<uint64_t *>(ctx->layout_sums.ptr);
+    }
+    HIP_TRY(launch_layout(lp, s));
+    return RANS_AMD_OK;
+}
+
+// the three-kernel placement's tail behind a coding kernel that left every chunk in its scratch slot: k_layout, k_compact
+int layout_and_compact(rans_amd_ctx *ctx, hipStream_t s, const uint8_t *scratch, uint64_t slot, uint64_t nchunks,
+                       const uint32_t *d_lengths, uint64_t *d_offsets, void *d_out, uint64_t out_cap)
+{
+    RC_TRY(layout_offsets(ctx, s, nchunks, d_lengths, d_offsets, out_cap, ctx->d_enc_flags()));
+    if (nchunks) {
+        CompactParams cp{};
+        cp.src_limit = ~0ull;
+        cp.scratch = scratch;
+        cp.slot_bytes = slot;
+        cp.lengths = d_lengths;
+        cp.offsets = d_offsets;
+        cp.out = static_cast<uint8_t *>(d_out);
+        cp.nchunks = nchunks;
+        cp.flags = ctx->d_enc_flags();
+        HIP_TRY(launch_compact(cp, ctx->num_cus, s));
+    }
+    return RANS_AMD_OK;
+}
+
+// a synchronous encode's verdict: the encode flags and the container's size (d_offsets[nchunks]), waited for
+int read_total_and_flags(rans_amd_ctx *ctx, hipStream_t s, const uint64_t *d_total, uint64_t *h_total, uint32_t *h_flags)
+{
+    uint32_t flags = 0;
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&flags, ctx->d_enc_flags(), 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *h_total = total;
+    *h_flags = flags;
+    return RANS_AMD_OK;
+}
 
 } // namespace
 
@@ -721,7 +944,6 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
     if (slots && (nchunks > (~0ull) / slot || out_cap < nchunks * slot)) // (known up front: nothing is launched)
         return fail(RANS_AMD_E_SPACE, sized ? "encode_slots_sized: out_cap does not hold n_chunks * slot_bytes"
                                             : "encode_slots: out_cap is below rans_amd_encode_slots_bound()");
-    int rc = RANS_AMD_OK;
     ZeroList zero(s); // (everything the kernels below expect to find zero: one launch)
     HIP_TRY(zero.add(ctx->d_enc_flags(), 8)); // encode flags and histogram flags (unused by an encode).  NOT the compaction's word:
                                              // a compaction's verdict stays until it has been reported (rans_amd_encode_status, or the
@@ -733,23 +955,21 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
     // 160 KiB alias model keep the three-kernel path.
     // (context option RANS_AMD_OPT_FUSED_PLACEMENT = 0 restores the three-kernel path)
     const bool unfused_env = ctx->unfused;
-    const int enc_format = model->host.r64_search ? kKernelFormatR64Search
-                           : (format == RANS_AMD_FMT_WORD && model->host.sym_bytes == 2) ? kKernelFormatWord16
-                           : (format == RANS_AMD_FMT_ALIAS && model->d_alias_remap16) ? kKernelFormatAliasLds
-                                                                                                  : format;
+    const int enc_format = encoder_kernel_format(model);
     if (enc_format == RANS_AMD_FMT_ALIAS && !encode_uses_lanes(enc_format, nchunks, n_ways))
         return fail(RANS_AMD_E_UNSUPPORTED, "encode: this alias model has no LDS tables (cannot happen for a model rans_amd_model_create accepted)");
+    // (everything but where the chunks go -- scratch, claims, the placement's fields -- is known here, and the questions
+    //  asked below about a launch that takes these arguments, encode_lanes_can_fuse and the like, read it)
     EncParams ep{};
     ep.syms = static_cast<const uint8_t *>(d_syms);
     ep.n = n;
     ep.nchunks = nchunks;
     ep.chunk_syms = chunk_syms;
     ep.n_ways = n_ways;
-    ep.scratch = static_cast<uint8_t *>(ctx->scratch.ptr);
     ep.slot_bytes = slot;
-    ep.nsyms = model->host.nsyms;
-    ep.sym_bytes = (uint32_t)model->host.sym_bytes;
-    ep.scale_bits = model->host.scale_bits;
+    ep.lengths = d_lengths;
+    fill_encoder_model(ep, model);
+    ep.flags = ctx->d_enc_flags();
     ep.variant = ctx->variant;
     // Watchdog of the placement protocols: half a minute plus what one wave may legitimately need for the call's largest
     // chunk -- a lane codes a symbol in well under a microsecond, and min(n_ways, 64) lanes share a chunk (a 2^31-symbol
@@ -788,20 +1008,14 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
             use_lanes = false;
             ep.no_lanes = 1u;
         }
-        if ((!use_lanes || groups) && nchunks > 0 && nchunks < (1ull << 32)) { // wave / group encoders hand their chunks out dynamically
-            // claim counters; sized slots: + the overflow count and the redo launch's claim counter (a line each) + the list
-            const size_t claim_bytes = (size_t)(kWorkPools + 2) * kWorkPoolStride * 4;
-            rc = ctx->enc_status.reserve(claim_bytes + (sized ? (size_t)nchunks * 4 : 0));
-            if (rc)
-                return rc;
-            HIP_TRY(zero.add(ctx->enc_status.ptr, claim_bytes));
-            ep.claims = static_cast<unsigned int *>(ctx->enc_status.ptr);
-        } else if (sized) { // lane encoders: only the overflow words
-            const size_t claim_bytes = (size_t)(kWorkPools + 2) * kWorkPoolStride * 4;
-            rc = ctx->enc_status.reserve(claim_bytes + (size_t)nchunks * 4);
-            if (rc)
-                return rc;
-            HIP_TRY(zero.add(ctx->enc_status.ptr, claim_bytes));
+        // wave / group encoders hand their chunks out dynamically: the claim counters.  Sized slots, the lane encoders'
+        // included: the overflow words in the block's last two lines, and the list of overflowed chunks behind it.
+        const bool claims = (!use_lanes || groups) && nchunks > 0 && nchunks < (1ull << 32);
+        if (claims || sized) {
+            RC_TRY(ctx->enc_status.reserve(kClaimBlockBytes + (sized ? (size_t)nchunks * 4 : 0)));
+            HIP_TRY(zero.add(ctx->enc_status.ptr, kClaimBlockBytes));
+            if (claims)
+                ep.claims = static_cast<unsigned int *>(ctx->enc_status.ptr);
         }
         if (sized) {
             ep.ovf_ctl = static_cast<unsigned int *>(ctx->enc_status.ptr) + kWorkPools * kWorkPoolStride;
@@ -810,16 +1024,11 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
         if (nchunks == 0)
             HIP_TRY(zero.add(d_offsets, 8));
     } else {
-        rc = ctx->scratch.reserve((size_t)((ring ? ring_waves * kEncRingSlots : nchunks) * slot + 64));
-        if (rc)
-            return rc;
+        RC_TRY(ctx->scratch.reserve((size_t)((ring ? ring_waves * kEncRingSlots : nchunks) * slot + 64)));
         ep.scratch = static_cast<uint8_t *>(ctx->scratch.ptr);
         if (groups && nchunks < (1ull << 32)) {
-            const size_t claim_bytes = (size_t)(kWorkPools + 2) * kWorkPoolStride * 4;
-            rc = ctx->enc_status.reserve(claim_bytes);
-            if (rc)
-                return rc;
-            HIP_TRY(zero.add(ctx->enc_status.ptr, claim_bytes));
+            RC_TRY(ctx->enc_status.reserve(kClaimBlockBytes));
+            HIP_TRY(zero.add(ctx->enc_status.ptr, kClaimBlockBytes));
             ep.claims = static_cast<unsigned int *>(ctx->enc_status.ptr);
         }
     }
@@ -828,15 +1037,11 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
         // (wave encoders: a word per chunk; lane encoders: a word per round of a block, at most one per batch of 64
         //  chunks; then the claim counters)
         const size_t status_bytes = (size_t)(nchunks + 8u * kWorkPools) * 8;
-        rc = ctx->enc_status.reserve(status_bytes);
-        if (rc)
-            return rc;
+        RC_TRY(ctx->enc_status.reserve(status_bytes));
         HIP_TRY(zero.add(static_cast<uint8_t *>(ctx->enc_status.ptr), status_bytes));
         if (fits == 2) { // the tables fill the LDS: one mailbox per block in global memory
             const size_t mb_bytes = (size_t)ctx->num_cus * kEncMailboxStride;
-            rc = ctx->enc_mailboxes.reserve(mb_bytes);
-            if (rc)
-                return rc;
+            RC_TRY(ctx->enc_mailboxes.reserve(mb_bytes));
             HIP_TRY(zero.add(ctx->enc_mailboxes.ptr, mb_bytes));
             ep.mailbox_global = static_cast<uint8_t *>(ctx->enc_mailboxes.ptr);
         }
@@ -846,24 +1051,6 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
         HIP_TRY(hipEventRecord(ctx->ev[2], s));
     HIP_TRY(zero.flush());
     if (nchunks) {
-        ep.syms = static_cast<const uint8_t *>(d_syms);
-        ep.n = n;
-        ep.nchunks = nchunks;
-        ep.chunk_syms = chunk_syms;
-        ep.n_ways = n_ways;
-        ep.slot_bytes = slot;
-        ep.lengths = d_lengths;
-        ep.enc_recs = model->d_enc;
-        ep.word_enc_recs = model->d_word_enc;
-        ep.word_small = model->host.word_small ? 1u : 0u;
-        ep.dense256 = model->host.dense256 ? 1u : 0u;
-        ep.alias_remap = static_cast<const uint32_t *>(model->d_remap);
-        ep.alias_recs8 = model->d_alias_recs8;
-        ep.alias_remap16 = static_cast<const uint16_t *>(model->d_alias_remap16);
-        ep.nsyms = model->host.nsyms;
-        ep.scale_bits = model->host.scale_bits;
-        ep.sym_bytes = (uint32_t)model->host.sym_bytes;
-        ep.flags = ctx->d_enc_flags();
         if (fused) {
             ep.status = reinterpret_cast<unsigned long long *>(static_cast<uint8_t *>(ctx->enc_status.ptr));
             ep.claims = reinterpret_cast<unsigned int *>(ep.status + nchunks); // (wave encoders; the lane encoders' scanners count behind their own status words)
@@ -888,34 +1075,8 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
             HIP_TRY(launch_encode(enc_format, redo, ctx->num_cus, s, nullptr));
         }
     }
-    if (!fused && !slots) {
-        LayoutParams lp;
-        lp.lengths = d_lengths;
-        lp.offsets = d_offsets;
-        lp.nchunks = nchunks;
-        lp.out_cap = out_cap;
-        lp.flags = ctx->d_enc_flags();
-        lp.block_sums = nullptr;
-        if (layout_blocks(nchunks) > 1) {
-            int rc = ctx->layout_sums.reserve((size_t)layout_blocks(nchunks) * 8);
-            if (rc)
-                return rc;
-            lp.block_sums = static_cast<uint64_t *>(ctx->layout_sums.ptr);
-        }
-        HIP_TRY(launch_layout(lp, s));
-        if (nchunks) {
-            CompactParams cp{};
-            cp.src_limit = ~0ull;
-            cp.scratch = ep.scratch;
-            cp.slot_bytes = slot;
-            cp.lengths = d_lengths;
-            cp.offsets = d_offsets;
-            cp.out = static_cast<uint8_t *>(d_out);
-            cp.nchunks = nchunks;
-            cp.flags = ctx->d_enc_flags();
-            HIP_TRY(launch_compact(cp, ctx->num_cus, s));
-        }
-    }
+    if (!fused && !slots)
+        RC_TRY(layout_and_compact(ctx, s, ep.scratch, slot, nchunks, d_lengths, d_offsets, d_out, out_cap));
     if (ctx->timing && !t_capturing) {
         HIP_TRY(hipEventRecord(ctx->ev[3], s));
         ctx->enc_timed = true;
@@ -923,11 +1084,7 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
 
     if (h_total_bytes) {
         uint32_t flags = 0;
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&flags, ctx->d_enc_flags(), 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&total, d_offsets + nchunks, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *h_total_bytes = total;
+        RC_TRY(read_total_and_flags(ctx, s, d_offsets + nchunks, h_total_bytes, &flags));
         return encode_flags_status(flags);
     }
     return RANS_AMD_OK;
@@ -1033,20 +1190,7 @@ int rans_amd_container_compact(rans_amd_ctx *ctx, const void *d_src, uint64_t sr
         HIP_TRY(zero.add(ctx->d_compact_flags(), 4));
         HIP_TRY(zero.flush());
     }
-    LayoutParams lp;
-    lp.lengths = d_lengths;
-    lp.offsets = d_dst_offsets;
-    lp.nchunks = n_chunks;
-    lp.out_cap = dst_cap;
-    lp.flags = ctx->d_compact_flags();
-    lp.block_sums = nullptr;
-    if (layout_blocks(n_chunks) > 1) {
-        int rc = ctx->layout_sums.reserve((size_t)layout_blocks(n_chunks) * 8);
-        if (rc)
-            return rc;
-        lp.block_sums = static_cast<uint64_t *>(ctx->layout_sums.ptr);
-    }
-    HIP_TRY(launch_layout(lp, s));
+    RC_TRY(layout_offsets(ctx, s, n_chunks, d_lengths, d_dst_offsets, dst_cap, ctx->d_compact_flags()));
     if (n_chunks) {
         CompactParams cp{};
         cp.scratch = static_cast<const uint8_t *>(d_src);
@@ -1136,76 +1280,24 @@ int rans_amd_decode(rans_amd_ctx *ctx, const rans_amd_model *model, const void *
         dp.nchunks = nchunks;
         dp.chunk_syms = chunk_syms;
         dp.n_ways = n_ways;
-        dp.table0 = model->d_table0;
-        dp.table1 = model->d_table1 ? model->d_table1 : model->d_table0;
-        dp.table0_bytes = model->table0_bytes;
-        dp.table1_bytes = model->table1_bytes;
+        fill_decoder_tables(dp, model);
         dp.packed = model->d_packed;
         dp.packed_bytes = model->d_packed ? (uint32_t)(model->host.r64_packed.size() * 4) : 0u;
-        dp.scale_bits = model->host.scale_bits;
-        dp.log2nsyms = model->host.log2nsyms;
-        if (model->host.r64_search) { // log2 of the padded cum table
-            dp.log2nsyms = 0;
-            while ((1u << dp.log2nsyms) < model->host.cum_padded.size())
-                dp.log2nsyms++;
-        }
-        dp.sym_bytes = (uint32_t)model->host.sym_bytes;
         dp.err_count = ctx->d_err();
-        // dynamic chunk hand-out: a 4-byte counter zeroed in stream order ahead of the kernel
-        // Counters form a ring of 64 slots (all zero at context creation); launch i uses slot
-        // i % 64 and re-zeroes slot (i + 32) % 64 from inside the kernel, so no memset node is
-        // needed and up to 32 decode launches of one context may be in flight at once.
-        dp.work_counter = nullptr;
-        dp.work_counter_reset = nullptr;
-        dp.span = nullptr;
-        dp.span_reset = nullptr;
-        {   // (small, allocated once, kept: not part of what rans_amd_ctx_trim drops)
-            int wrc = ctx->wave_scratch.reserve((size_t)ctx->num_cus * 2u * (kDecBlockThreads / 64) * 64u);
-            if (wrc)
-                return wrc;
-            dp.wave_scratch = static_cast<uint8_t *>(ctx->wave_scratch.ptr);
-        }
+        RC_TRY(use_wave_scratch(ctx, dp));
         dp.variant = ctx->variant;
-        if (nchunks < 0xffffffffull) {
-            unsigned int *ring = reinterpret_cast<unsigned int *>(ctx->d_words + 256);
-            const uint32_t per_slot = kWorkSlotWords;
-            if (capture.active) {
-                // A launch that becomes a graph node runs again and again with these very arguments: its counters are one
-                // of kCaptureSlots slots of their own, zeroed by a k_zero node in front of the kernel (so every replay
-                // starts from zero, and the ring of the eager launches never sees a slot a replay has used).
-                dp.work_counter = capture_counters(ctx);
-                {
-                    ZeroList zero(s);
-                    HIP_TRY(zero.add(dp.work_counter, (uint64_t)per_slot * 4));
-                    HIP_TRY(zero.flush());
-                }
-                dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
-            } else {
-                dp.work_counter = ring + (size_t)(ctx->launch_seq % kWorkSlots) * per_slot;
-                dp.work_counter_reset = ring + (size_t)((ctx->launch_seq + kWorkSlots / 2) % kWorkSlots) * per_slot;
-                // the slot's last line: first wave start / last wave end of the launch (rans_amd_launch_spans)
-                dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
-                dp.span_reset = reinterpret_cast<unsigned long long *>(dp.work_counter_reset + kWorkPools * kWorkPoolStride);
-            }
-        }
-        // wave clocks (rans_amd_set_timing(ctx, 2)) and the debug timeline (RANS_AMD_TRACE=<file>): per-wave
-        // start/end ticks, XCD, shader cycles and rounds, read back after a sync
+        if (nchunks < 0xffffffffull) // (32-bit counters; without one the kernels stride statically)
+            RC_TRY(take_counter_slot(ctx, capture, s, dp));
+        // wave clocks (rans_amd_set_timing(ctx, 2)) and the debug timeline (RANS_AMD_TRACE=<file>): read_wave_trace
         static const char *trace_path = measure_knob("RANS_AMD_TRACE");
         const bool want_trace = (trace_path || ctx->wave_clocks_on) && !capture.active; // (read back after a sync)
         const size_t trace_words = (size_t)kTraceWords * 2u * 16u * (size_t)ctx->num_cus;
-        dp.trace = nullptr;
         if (want_trace) {
-            int trc = ctx->trace.reserve(trace_words * 8);
-            if (trc)
-                return trc;
+            RC_TRY(ctx->trace.reserve(trace_words * 8));
             dp.trace = static_cast<unsigned long long *>(ctx->trace.ptr);
             HIP_TRY(hipMemsetAsync(dp.trace, 0, trace_words * 8, s));
         }
-        if (ctx->timing && !t_capturing)
-            HIP_TRY(hipEventRecord(ctx->ev[0], s));
-        int dec_format = model->host.r64_search ? kKernelFormatR64Search
-                         : (format == RANS_AMD_FMT_WORD && model->host.sym_bytes == 2) ? kKernelFormatWord16
-                                                                                     : format;
+        int dec_format = decoder_kernel_format(model);
         // 64-way alias streams with at least a pair of chunks: two chunks per wave, tables in the FMT_ALIAS2 form
         // (decode_dual.hip).  u8 symbols are stored a dword per lane: 4-byte aligned chunks of output.
         // Only models whose tables leave no room for a second block per CU: with two blocks, eight waves per SIMD and one
@@ -1227,67 +1319,14 @@ int rans_amd_decode(rans_amd_ctx *ctx, const rans_amd_model *model, const void *
         // per SIMD -- loses to eight with the two-gather tables: profiles/r04_byte_decoder_variants.log).
         // The lane-per-chunk kernels, the 2-way pair kernel (decode_groups.hip) and the two-chunk kernel keep cum2sym + records.
         if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && !lanes_applicable(nchunks, n_ways) && !decode_byte_pairs_applicable(dp) &&
-            model->host.scale_bits <= 12) {
-            dp.table0 = model->d_fused;
-            dp.table0_bytes = (uint32_t)(model->host.byte_slots.size() * sizeof(WordSlot));
-            dp.table1 = model->d_fused;
-            dp.table1_bytes = 0;
-            dec_format = kKernelFormatByteFused;
-        }
-        HIP_TRY(launch_decode(dec_format, dp, ctx->num_cus, s, &ctx->last_kernel));
-        // the launch that uses slot i zeroes slot i + 32: move on only once it really is in the stream,
-        // or a later launch would start from a counter nobody reset
-        if (dp.work_counter && !capture.active)
-            ctx->launch_seq++;
-        if (ctx->timing && !t_capturing) {
-            HIP_TRY(hipEventRecord(ctx->ev[1], s));
-            ctx->dec_timed = true;
-        }
-        if (want_trace) {
-            std::vector<unsigned long long> host(trace_words);
-            HIP_TRY(hipMemcpyAsync(host.data(), dp.trace, trace_words * 8, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            rans_amd_wave_clocks wc = {0, 0, 0, 0.0, 0.0};
-            unsigned long long t_first = ~0ull, t_last = 0, longest_ticks = 0, longest_cycles = 0;
-            for (size_t w = 0; w < trace_words / kTraceWords; ++w) {
-                const unsigned long long *t = &host[kTraceWords * w];
-                if (!t[1])
-                    continue; // this slot's wave never ran (grid smaller than the buffer) or is not instrumented
-                wc.waves++;
-                wc.shader_cycles += t[3];
-                wc.rounds += t[4];
-                t_first = t[0] < t_first ? t[0] : t_first;
-                t_last = t[1] > t_last ? t[1] : t_last;
-                if (t[1] - t[0] > longest_ticks) {
-                    longest_ticks = t[1] - t[0];
-                    longest_cycles = t[3];
-                }
-            }
-            if (wc.waves && longest_ticks) {
-                wc.sclk_hz = (double)longest_cycles / ((double)longest_ticks * 1e-8); // wall_clock64 ticks at 100 MHz
-                wc.kernel_ticks_ms = (double)(t_last - t_first) * 1e-5;
-            }
-            ctx->wave_clocks = wc;
-            if (trace_path) {
-                if (FILE *f = fopen(trace_path, "w")) {
-                    for (size_t w = 0; w < trace_words / kTraceWords; ++w)
-                        if (host[kTraceWords * w + 1])
-                            fprintf(f, "%zu %llu %llu %llu %llu %llu\n", w, host[kTraceWords * w], host[kTraceWords * w + 1],
-                                    host[kTraceWords * w + 2], host[kTraceWords * w + 3], host[kTraceWords * w + 4]);
-                    fclose(f);
-                }
-            }
-        }
+            model->host.scale_bits <= 12)
+            dec_format = use_byte_fused_tables(dp, model);
+        RC_TRY(launch_decoder(ctx, capture, s, launch_decode, dec_format, dp));
+        if (want_trace)
+            RC_TRY(read_wave_trace(ctx, s, dp.trace, trace_words, trace_path));
     }
-    if (h_bad_chunks) {
-        unsigned long long bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, ctx->d_err(), 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemsetAsync(ctx->d_err(), 0, 8, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *h_bad_chunks = bad;
-        if (bad)
-            return fail(RANS_AMD_E_CORRUPT, "decode: at least one chunk failed its integrity check");
-    }
+    if (h_bad_chunks)
+        RC_TRY(read_bad_count(ctx, s, h_bad_chunks, "decode: at least one chunk failed its integrity check"));
     return RANS_AMD_OK;
 }
 
@@ -1390,68 +1429,20 @@ int rans_amd_decode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
         dp.sym_counts = d_sym_counts;
         dp.order = d_order;
         dp.out_syms = out_syms;
-        dp.table0 = model->d_table0;
-        dp.table1 = model->d_table1 ? model->d_table1 : model->d_table0;
-        dp.table0_bytes = model->table0_bytes;
-        dp.table1_bytes = model->table1_bytes;
-        dp.scale_bits = model->host.scale_bits;
-        dp.log2nsyms = model->host.log2nsyms;
-        if (model->host.r64_search) { // log2 of the padded cum table
-            dp.log2nsyms = 0;
-            while ((1u << dp.log2nsyms) < model->host.cum_padded.size())
-                dp.log2nsyms++;
-        }
-        dp.sym_bytes = (uint32_t)model->host.sym_bytes;
+        fill_decoder_tables(dp, model);
         dp.err_count = ctx->d_err();
-        if (int wrc = ctx->wave_scratch.reserve((size_t)ctx->num_cus * 2u * (kDecBlockThreads / 64) * 64u))
-            return wrc;
-        dp.wave_scratch = static_cast<uint8_t *>(ctx->wave_scratch.ptr);
+        RC_TRY(use_wave_scratch(ctx, dp));
         dp.variant = ctx->variant;
-        // the counter ring, exactly as rans_amd_decode uses it: claim from slot i, re-zero the slot launch i + 32 will use;
-        // a captured launch takes one of the capture slots and a k_zero node in front of it
-        unsigned int *ring = reinterpret_cast<unsigned int *>(ctx->d_words + 256);
-        if (capture.active) {
-            dp.work_counter = capture_counters(ctx);
-            ZeroList zero(s);
-            HIP_TRY(zero.add(dp.work_counter, (uint64_t)kWorkSlotWords * 4));
-            HIP_TRY(zero.flush());
-            dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
-        } else {
-            dp.work_counter = ring + (size_t)(ctx->launch_seq % kWorkSlots) * kWorkSlotWords;
-            dp.work_counter_reset = ring + (size_t)((ctx->launch_seq + kWorkSlots / 2) % kWorkSlots) * kWorkSlotWords;
-            dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
-            dp.span_reset = reinterpret_cast<unsigned long long *>(dp.work_counter_reset + kWorkPools * kWorkPoolStride);
-        }
-        if (ctx->timing && !t_capturing)
-            HIP_TRY(hipEventRecord(ctx->ev[0], s));
-        int dec_format = model->host.r64_search ? kKernelFormatR64Search
-                         : (format == RANS_AMD_FMT_WORD && model->host.sym_bytes == 2) ? kKernelFormatWord16
-                                                                                     : format;
-        // byte format: the fused slot records where the model has them and they leave room for two blocks per CU (rans_amd_decode)
-        if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12) {
-            dp.table0 = model->d_fused;
-            dp.table0_bytes = (uint32_t)(model->host.byte_slots.size() * sizeof(WordSlot));
-            dp.table1 = model->d_fused;
-            dp.table1_bytes = 0;
-            dec_format = kKernelFormatByteFused;
-        }
-        HIP_TRY(launch_decode_batch(dec_format, dp, ctx->num_cus, s, &ctx->last_kernel));
-        if (!capture.active)
-            ctx->launch_seq++;
-        if (ctx->timing && !t_capturing) {
-            HIP_TRY(hipEventRecord(ctx->ev[1], s));
-            ctx->dec_timed = true;
-        }
+        RC_TRY(take_counter_slot(ctx, capture, s, dp)); // (n_streams fits the 32-bit counters: checked above)
+        int dec_format = decoder_kernel_format(model);
+        // byte format: the fused slot records where the model has them and they leave room for two blocks per CU (rans_amd_decode;
+        // every batch kernel is a wave-per-stream kernel)
+        if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12)
+            dec_format = use_byte_fused_tables(dp, model);
+        RC_TRY(launch_decoder(ctx, capture, s, launch_decode_batch, dec_format, dp));
     }
-    if (h_bad_streams) {
-        unsigned long long bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, ctx->d_err(), 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemsetAsync(ctx->d_err(), 0, 8, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *h_bad_streams = bad;
-        if (bad)
-            return fail(RANS_AMD_E_CORRUPT, "decode_batch: at least one stream failed its integrity check");
-    }
+    if (h_bad_streams)
+        RC_TRY(read_bad_count(ctx, s, h_bad_streams, "decode_batch: at least one stream failed its integrity check"));
     return RANS_AMD_OK;
 }
 
@@ -1470,10 +1461,7 @@ int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
         return fail(RANS_AMD_E_ARG, "encode_batch: d_out must be 16-byte aligned");
     if (n_streams >= 0xffffffffull)
         return fail(RANS_AMD_E_UNSUPPORTED, "encode_batch: stream indices are 32-bit");
-    const int enc_format = model->host.r64_search ? kKernelFormatR64Search
-                           : (format == RANS_AMD_FMT_WORD && model->host.sym_bytes == 2) ? kKernelFormatWord16
-                           : (format == RANS_AMD_FMT_ALIAS && model->d_alias_remap16) ? kKernelFormatAliasLds
-                                                                                                  : format;
+    const int enc_format = encoder_kernel_format(model);
     if (enc_format == RANS_AMD_FMT_ALIAS)
         return fail(RANS_AMD_E_UNSUPPORTED, "encode_batch: this alias model has no LDS tables (cannot happen for a model rans_amd_model_create accepted)");
     DeviceGuard guard(ctx->device);
@@ -1482,11 +1470,9 @@ int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
     const CaptureScope capture(s);
     ZeroList zero(s);
     HIP_TRY(zero.add(ctx->d_enc_flags(), 8)); // (encode flags and histogram flags, not the compaction's word: encode_impl)
-    const size_t claim_bytes = (size_t)(kWorkPools + 2) * kWorkPoolStride * 4;
     if (n_streams) {
-        if (int rc = ctx->enc_status.reserve(claim_bytes))
-            return rc;
-        HIP_TRY(zero.add(ctx->enc_status.ptr, claim_bytes));
+        RC_TRY(ctx->enc_status.reserve(kClaimBlockBytes));
+        HIP_TRY(zero.add(ctx->enc_status.ptr, kClaimBlockBytes));
     }
     if (ctx->timing && !t_capturing)
         HIP_TRY(hipEventRecord(ctx->ev[2], s));
@@ -1505,16 +1491,7 @@ int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
         ep.sym_offsets = d_sym_offsets;
         ep.sym_counts = d_sym_counts;
         ep.slot_offsets = d_slot_offsets;
-        ep.enc_recs = model->d_enc;
-        ep.word_enc_recs = model->d_word_enc;
-        ep.word_small = model->host.word_small ? 1u : 0u;
-        ep.dense256 = model->host.dense256 ? 1u : 0u;
-        ep.alias_remap = static_cast<const uint32_t *>(model->d_remap);
-        ep.alias_recs8 = model->d_alias_recs8;
-        ep.alias_remap16 = static_cast<const uint16_t *>(model->d_alias_remap16);
-        ep.nsyms = model->host.nsyms;
-        ep.scale_bits = model->host.scale_bits;
-        ep.sym_bytes = (uint32_t)model->host.sym_bytes;
+        fill_encoder_model(ep, model);
         ep.flags = ctx->d_enc_flags();
         ep.variant = ctx->variant;
         HIP_TRY(launch_encode_batch(enc_format, ep, ctx->num_cus, s, &ctx->last_enc_kernel));
@@ -1603,13 +1580,7 @@ int rans_amd_decode_errors(rans_amd_ctx *ctx, uint64_t *h_bad_chunks, void *stre
         return fail(RANS_AMD_E_ARG, "decode_errors: NULL argument");
     DeviceGuard guard(ctx->device);
     std::lock_guard<std::mutex> lock(ctx->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    unsigned long long bad = 0;
-    HIP_TRY(hipMemcpyAsync(&bad, ctx->d_err(), 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemsetAsync(ctx->d_err(), 0, 8, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *h_bad_chunks = bad;
-    return bad ? fail(RANS_AMD_E_CORRUPT, "decode: at least one chunk failed its integrity check") : RANS_AMD_OK;
+    return read_bad_count(ctx, static_cast<hipStream_t>(stream), h_bad_chunks, "decode: at least one chunk failed its integrity check");
 }
 
 
@@ -1661,9 +1632,7 @@ static int encode_adaptive_impl(rans_amd_ctx *ctx, const int format, const void 
     const uint64_t slot = encode_slot_bytes(format, n, n_ways, chunk_syms);
     if (slot > 0xfffffff0ull)
         return fail(RANS_AMD_E_UNSUPPORTED, "encode_adaptive: chunk_syms too large");
-    int rc = ctx->scratch.reserve((size_t)(nchunks * slot + 64));
-    if (rc)
-        return rc;
+    RC_TRY(ctx->scratch.reserve((size_t)(nchunks * slot + 64)));
     {
         ZeroList zero(s);
         HIP_TRY(zero.add(ctx->d_enc_flags(), 8)); // (encode + histogram flags; a compaction's verdict stays until reported, as in encode_impl)
@@ -1696,43 +1665,14 @@ static int encode_adaptive_impl(rans_amd_ctx *ctx, const int format, const void 
         ctx->last_enc_fused = false;
         ctx->last_enc_slots = false;
     }
-    LayoutParams lp;
-    lp.lengths = d_lengths;
-    lp.offsets = d_offsets;
-    lp.nchunks = nchunks;
-    lp.out_cap = out_cap;
-    lp.flags = ctx->d_enc_flags();
-    lp.block_sums = nullptr;
-    if (layout_blocks(nchunks) > 1) {
-        rc = ctx->layout_sums.reserve((size_t)layout_blocks(nchunks) * 8);
-        if (rc)
-            return rc;
-        lp.block_sums = static_cast<uint64_t *>(ctx->layout_sums.ptr);
-    }
-    HIP_TRY(launch_layout(lp, s));
-    if (nchunks) {
-        CompactParams cp{};
-        cp.src_limit = ~0ull;
-        cp.scratch = static_cast<const uint8_t *>(ctx->scratch.ptr);
-        cp.slot_bytes = slot;
-        cp.lengths = d_lengths;
-        cp.offsets = d_offsets;
-        cp.out = static_cast<uint8_t *>(d_out);
-        cp.nchunks = nchunks;
-        cp.flags = ctx->d_enc_flags();
-        HIP_TRY(launch_compact(cp, ctx->num_cus, s));
-    }
+    RC_TRY(layout_and_compact(ctx, s, static_cast<const uint8_t *>(ctx->scratch.ptr), slot, nchunks, d_lengths, d_offsets, d_out, out_cap));
     if (ctx->timing && !t_capturing && nchunks) { // (ev[2] is recorded in front of the coding kernel, which an empty input does not launch)
         HIP_TRY(hipEventRecord(ctx->ev[3], s));
         ctx->enc_timed = true;
     }
     if (h_total_bytes) {
         uint32_t flags = 0;
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&flags, ctx->d_enc_flags(), 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&total, d_offsets + nchunks, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *h_total_bytes = total;
+        RC_TRY(read_total_and_flags(ctx, s, d_offsets + nchunks, h_total_bytes, &flags));
         if (flags & 1u)
             return fail(RANS_AMD_E_MODEL, "encode_adaptive: a chunk's counts could not be normalised, or a symbol without a slot was met");
         if (flags & 2u)
@@ -1778,41 +1718,14 @@ static int decode_adaptive_impl(rans_amd_ctx *ctx, const int format, const void 
         dp.sym_bytes = 1;
         dp.err_count = ctx->d_err();
         dp.chunk_freqs = d_chunk_freqs;
-        if (nchunks < 0xffffffffull && capture.active) { // (as in rans_amd_decode)
-            dp.work_counter = capture_counters(ctx);
-            {
-                ZeroList zero(s);
-                HIP_TRY(zero.add(dp.work_counter, (uint64_t)kWorkSlotWords * 4));
-                HIP_TRY(zero.flush());
-            }
-            dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
-        } else if (nchunks < 0xffffffffull) {
-            unsigned int *ring = reinterpret_cast<unsigned int *>(ctx->d_words + 256);
-            dp.work_counter = ring + (size_t)(ctx->launch_seq % kWorkSlots) * kWorkSlotWords;
-            dp.work_counter_reset = ring + (size_t)((ctx->launch_seq + kWorkSlots / 2) % kWorkSlots) * kWorkSlotWords;
-            dp.span = reinterpret_cast<unsigned long long *>(dp.work_counter + kWorkPools * kWorkPoolStride);
-            dp.span_reset = reinterpret_cast<unsigned long long *>(dp.work_counter_reset + kWorkPools * kWorkPoolStride);
-        }
-        if (ctx->timing && !t_capturing)
-            HIP_TRY(hipEventRecord(ctx->ev[0], s));
-        HIP_TRY(launch_decode(format == RANS_AMD_FMT_WORD ? kKernelFormatWordAdaptive : kKernelFormatByteAdaptive, dp, ctx->num_cus, s,
-                              &ctx->last_kernel));
-        if (dp.work_counter && !capture.active)
-            ctx->launch_seq++;
-        if (ctx->timing && !t_capturing) {
-            HIP_TRY(hipEventRecord(ctx->ev[1], s));
-            ctx->dec_timed = true;
-        }
+        // (no model tables: every wave builds its chunk's from the chunk's frequency row; no wave_scratch, variant 0)
+        if (nchunks < 0xffffffffull)
+            RC_TRY(take_counter_slot(ctx, capture, s, dp));
+        const int dec_format = format == RANS_AMD_FMT_WORD ? kKernelFormatWordAdaptive : kKernelFormatByteAdaptive;
+        RC_TRY(launch_decoder(ctx, capture, s, launch_decode, dec_format, dp));
     }
-    if (h_bad_chunks) {
-        unsigned long long bad = 0;
-        HIP_TRY(hipMemcpyAsync(&bad, ctx->d_err(), 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemsetAsync(ctx->d_err(), 0, 8, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *h_bad_chunks = bad;
-        if (bad)
-            return fail(RANS_AMD_E_CORRUPT, "decode_adaptive: at least one chunk failed its integrity check");
-    }
+    if (h_bad_chunks)
+        RC_TRY(read_bad_count(ctx, s, h_bad_chunks, "decode_adaptive: at least one chunk failed its integrity check"));
     return RANS_AMD_OK;
 }
 
@@ -1858,9 +1771,7 @@ static int encode_adaptive_sized_impl(rans_amd_ctx *ctx, const int format, const
     }
     // a look-back word per chunk, then the claim counters (a line each)
     const size_t ctl_bytes = (size_t)nchunks * 8 + (size_t)kWorkPools * kWorkPoolStride * 4;
-    int rc = ctx->enc_status.reserve(ctl_bytes);
-    if (rc)
-        return rc;
+    RC_TRY(ctx->enc_status.reserve(ctl_bytes));
     {
         ZeroList zero(s);
         HIP_TRY(zero.add(ctx->d_enc_flags(), 8)); // (encode + histogram flags; a compaction's verdict stays until reported, as in encode_impl)
@@ -1901,11 +1812,7 @@ static int encode_adaptive_sized_impl(rans_amd_ctx *ctx, const int format, const
     }
     if (h_total_bytes) {
         uint32_t flags = 0;
-        uint64_t total = 0;
-        HIP_TRY(hipMemcpyAsync(&flags, ctx->d_enc_flags(), 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&total, d_offsets + nchunks, 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *h_total_bytes = total;
+        RC_TRY(read_total_and_flags(ctx, s, d_offsets + nchunks, h_total_bytes, &flags));
         if (flags & 1u)
             return fail(RANS_AMD_E_MODEL, "encode_adaptive_sized: a chunk's counts could not be normalised");
         return encode_flags_status(flags);

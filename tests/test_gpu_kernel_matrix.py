@@ -262,40 +262,67 @@ RING_DECODE_LAUNCHES = 136  # two wraps of the 64-slot ring and a bit
 @pytest.mark.gpu
 def test_counter_ring_two_wraps_on_a_fresh_context(oracle):
     """A fresh context, RING_DECODE_LAUNCHES eager decode launches without a synchronisation in between, cycling through the
-    decode rows of the matrix at their "part of one round" size in a FIXED order (launch i runs row i % rows: a failure names
-    its position in the ring).  Launch i claims from counter slot i % 64 and re-zeroes slot (i + 32) % 64 for the launch 32
-    calls later (api.cpp rans_amd_decode): a kernel family that forgot would leave a used counter to a launch of ANOTHER
-    family.  Every launch has its own pre-poisoned output; afterwards every output == its input and decode_errors() == 0.
+    decode rows of the matrix at their "part of one round" size in a FIXED order (launch i runs item i % items: a failure
+    names its position in the ring).  The three decode entry points share the one ring, so the cycle holds all of them:
+    the static rows through ctx.decode, the two per-chunk-model rows through ctx.decode_adaptive, and one ragged batch
+    (tests/test_gpu_batch.py's Batch) through ctx.decode_batch.  Launch i claims from counter slot i % 64 and re-zeroes slot
+    (i + 32) % 64 for the launch 32 calls later (api.cpp take_counter_slot): a kernel family or an entry point that forgot
+    would leave a used counter to a launch of ANOTHER one.  Every launch has its own pre-poisoned output; afterwards every
+    output == its input and decode_errors() == 0.
     Then the encoders that claim from the encode status workspace, the three placements mixed, rans_amd_encode_status after
     every call and every chunk of every container against the oracle."""
+    import numpy as np
     import torch
     assert torch.cuda.is_available(), "these tests need the GPU box"
     import bench
     import ryg_rans_amd as R
+    from test_gpu_batch import ROW as BATCH_ROW, Batch, draw_lengths
     resident = resident_waves(torch)
-    rows = [r for r in KERNEL_ROWS if r["kind"] == "static" and "H" in r["regimes"] and not r["opts"]]
-    assert len({pick(r["decode"], "H") for r in rows}) >= 10
+    rows = [r for r in KERNEL_ROWS if "H" in r["regimes"] and not r["opts"]]
+    assert len({pick(r["decode"], "H") for r in rows if r["kind"] == "static"}) >= 10
+    assert sorted(r["id"] for r in rows if r["kind"] == "adaptive") == ["byte-64-per-chunk-models", "word-64-per-chunk-models"]
     ctx = R.Context(0)
     try:
         prepared = []
         for r in rows:
             n, _ = regime_symbols(r, "H", resident)
             d_syms = bench.gen_zipf(torch, n, r["K"], 1.0, 1, "cuda")
-            freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, r["K"]), 1 << r["sb"])
-            gm = ctx.model(r["fmt"], freqs, r["sb"])
-            cont, offs, lens, total = ctx.encode(gm, d_syms, r["ways"], r["chunk"])
+            if r["kind"] == "adaptive":  # (its own container and frequency rows: one model per chunk, built by the encoder)
+                cont, offs, lens, freqs, total = ctx.encode_adaptive(d_syms, r["ways"], r["chunk"], r["sb"], fmt=r["fmt"])
+                gm = None
+            else:
+                freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, r["K"]), 1 << r["sb"])
+                gm = ctx.model(r["fmt"], freqs, r["sb"])
+                cont, offs, lens, total = ctx.encode(gm, d_syms, r["ways"], r["chunk"])
             prepared.append((r, n, d_syms, freqs, gm, cont, offs, lens, total))
+        # the ragged batch: 300 streams of 0 .. 64 Ki symbols, laid out on 4-symbol boundaries in a poison-filled buffer
+        brow = BATCH_ROW["word-64"]
+        b = Batch(R, ctx, torch, oracle, brow, draw_lengths(300, brow["ways"], 7))
+        b_buf, b_sym_offs, b_slot_offs = b.laid_out(4)
+        b_sym, b_slot = b.dev(b_sym_offs, np.int64), b.dev(b_slot_offs, np.int64)
+        b_cont, b_offs, b_lens = ctx.encode_batch(b.gm, b_buf, b_sym, b.d_counts, brow["ways"], b_slot)
+        ctx.encode_status()
+        items = prepared + [(dict(brow, kind="batch", id="batch-" + brow["id"]), None, b_buf)]
         torch.cuda.synchronize()
         outs = []
         for i in range(RING_DECODE_LAUNCHES):
-            r, n, d_syms, freqs, gm, cont, offs, lens, total = prepared[i % len(prepared)]
-            out = torch.full_like(d_syms, 0x5A)
-            ctx.decode(gm, cont, total, offs, lens, n, r["ways"], r["chunk"], d_out=out, sync=False)
+            r, n, d_syms = items[i % len(items)][:3]
+            if r["kind"] == "batch":
+                out = torch.full_like(d_syms, b.poison())
+                ctx.decode_batch(b.gm, b_cont, int(b_slot_offs[-1]), b_offs, b_lens, b_sym, b.d_counts, r["ways"], out, sync=False)
+            else:
+                freqs, gm, cont, offs, lens, total = items[i % len(items)][3:]
+                out = torch.full_like(d_syms, 0x5A)
+                if r["kind"] == "adaptive":
+                    ctx.decode_adaptive(cont, total, offs, lens, freqs, n, r["ways"], r["chunk"], r["sb"], d_out=out, sync=False, fmt=r["fmt"])
+                else:
+                    ctx.decode(gm, cont, total, offs, lens, n, r["ways"], r["chunk"], d_out=out, sync=False)
             assert ctx.last_decode_kernel() == pick(r["decode"], "H"), (i, r["id"], ctx.last_decode_kernel())
             outs.append(out)
+        assert {items[i % len(items)][0]["kind"] for i in range(RING_DECODE_LAUNCHES)} == {"static", "adaptive", "batch"}
         assert ctx.decode_errors() == 0
         for i, out in enumerate(outs):
-            r, n, d_syms = prepared[i % len(prepared)][:3]
+            r, n, d_syms = items[i % len(items)][:3]
             assert torch.equal(out, d_syms), ("launch", i, "ring slot", i % 64, r["id"])
         del outs
         # the encoders: wave encoders (status words + claims), the group encoder (claims), lane encoders -- compact, slots, sized
