@@ -985,7 +985,7 @@ static int encode_impl(rans_amd_ctx *ctx, const rans_amd_model *model, const voi
     }
     const bool lanes = encode_uses_lanes(enc_format, nchunks, n_ways);
     // context option RANS_AMD_OPT_LANE_FUSED_PLACEMENT: the lane encoders place their chunks themselves as well -- bit-exact,
-    // tested, and on config 2 no faster than k_layout + k_compact_small behind them (lanes.hip says why), hence opt-in
+    // tested, and on config 2 no faster than k_layout + k_compact_small behind them (encode_lanes.hip says why), hence opt-in
     const bool lanes_fused_env = (ctx->variant & kVarLanesFused) != 0;
     const int fits = lanes ? 0 : encode_fused_fits(enc_format, model->host.nsyms, model->host.scale_bits);
     const bool fused = !slots && nchunks > 0 && nchunks < (1ull << 31) && !unfused_env &&

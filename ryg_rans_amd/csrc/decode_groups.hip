@@ -3,7 +3,7 @@
 // cursor) with lane 8 g + i = state i of chunk g of the wave's octet, and further down k_decode_byte_pairs, the 2-way byte
 // layout of main.cpp:226-280 with lane 2 g + i.
 //
-// The lane-per-chunk kernels (lanes.hip) give every lane a whole chunk: 64 private streams per wave, a 136-byte ring
+// The lane-per-chunk kernels (decode_lanes.hip) give every lane a whole chunk: 64 private streams per wave, a 136-byte ring
 // row per lane in LDS (8.7 KiB per wave beside the 32 KiB slot table: 13..14 waves per CU), and their pace is set by
 // how few waves a CU can hold (profiles/r06_small_abs.md).  Here a chunk is decoded the way the wave-per-chunk
 // kernels do it (decode_wave.hip) -- one symbol per lane per round, "who renormalises" is a ballot, a lane's place in

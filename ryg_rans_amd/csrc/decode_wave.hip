@@ -1,6 +1,6 @@
 // decode_wave.hip -- the wave-per-chunk decoder (the headline kernel) of the hand-written gfx950
-// (CDNA4, wave64) kernels for interleaved rANS; encode_wave.hip, lanes.hip and container_kernels.hip
-// hold the rest.
+// (CDNA4, wave64) kernels for interleaved rANS; encode_wave.hip, decode_lanes.hip, encode_lanes.hip and
+// container_kernels.hip hold the rest.
 //
 // Mapping of the reference's hot loops onto the GPU
 // --------------------------------------------------

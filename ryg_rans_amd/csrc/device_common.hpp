@@ -570,7 +570,7 @@ __device__ __forceinline__ uint64_t enc_update_r64(uint64_t y, const uint4 &rec,
 }
 
 // Mailbox between the coding waves of a block and its copier wave(s) (fused placement, encode_wave.hip k_encode and
-// lanes.hip): the coder pushes {unit + 1, bytes} when its unit (chunk / batch of 64 chunks) is in the scratch slots,
+// encode_lanes.hip): the coder pushes {unit + 1, bytes} when its unit (chunk / batch of 64 chunks) is in the scratch slots,
 // a copier takes the entries in order.  Lives in the block's LDS (EncParams::mailbox_off), zeroed at kernel start.
 struct EncMailbox {
     uint32_t tail;     // entries handed out to encoders
@@ -703,7 +703,7 @@ __device__ __forceinline__ bool mailbox_pop(EncMailbox *mb, uint32_t lane, uint3
         }
     }
     // (every lane writes the same zero: a trailing `if (lane == 0)` invites the compiler to let the other lanes run ahead
-    //  into code whose readfirstlane / ballot assumes the whole wave -- see lanes.hip, lanes_scan_batch)
+    //  into code whose readfirstlane / ballot assumes the whole wave -- see encode_lanes.hip, lanes_scan_batch)
     *reinterpret_cast<volatile unsigned long long *>(e) = 0ull;
     return true;
 }

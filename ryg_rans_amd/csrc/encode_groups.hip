@@ -2,7 +2,7 @@
 // (rans_word_sse41.h:57-100, main_simd.cpp:287-300: eight states, one pointer that moves DOWN), EIGHT chunks per wave, lane
 // 8 g + i holds state i of chunk g of the wave's octet.
 //
-// The lane-per-chunk encoder (lanes.hip k_encode_lanes_staged) walks a whole chunk per lane: 10 KiB of staging rows and
+// The lane-per-chunk encoder (encode_lanes.hip k_encode_lanes_staged) walks a whole chunk per lane: 10 KiB of staging rows and
 // rings per wave, 11..13 waves per CU, 1.2 ms per GiB.  Here a round codes one symbol per lane:
 //   * symbols: sixteen rounds are one 128-byte line of the chunk, 16 bytes per lane, taken apart into per-state bytes by
 //     the inverse of the decoder's output exchange (v_cndmask_b32_dpp between the halves of the group, then the quad

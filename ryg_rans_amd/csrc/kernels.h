@@ -1,5 +1,6 @@
 // kernels.h -- launch interface between the C-ABI layer (api.cpp) and the HIP
-// kernels (decode_wave.hip, encode_wave.hip, lanes.hip, container_kernels.hip).  Internal; not installed.
+// kernels (decode_wave.hip, encode_wave.hip, decode_lanes.hip, encode_lanes.hip,
+// container_kernels.hip).  Internal; not installed.
 #pragma once
 
 #include <cstdint>
@@ -141,7 +142,7 @@ struct EncParams {
                                 // one kEncMailboxStride-byte mailbox per block in global memory (zero at launch), else NULL
     uint32_t ring_slots;        // fused wave encoders: 0 = scratch holds one slot per CHUNK (slot of chunk c at c * slot_bytes);
                                 // R > 0 = one ring of R slots per CODING WAVE (wave g's slots at (g * R + j) * slot_bytes)
-    // Lane-per-chunk encoders (lanes.hip), fused: a launch codes the batches (64 chunks each) [batch_begin, batch_end)
+    // Lane-per-chunk encoders (encode_lanes.hip), fused: a launch codes the batches (64 chunks each) [batch_begin, batch_end)
     // of the nchunks chunks; status holds one word per UNIT -- the C batches the C coding waves of a block take in one
     // round -- numbered from unit_base, then (from word ceil(nchunks / 64) on) claim counters on a 64-byte line each,
     // of which this launch uses number claim_slot.  The r64 2-way kernel and the staged kernel that takes the tail

@@ -57,7 +57,7 @@ hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t
 bool encode_word_groups_applicable(const EncParams &p);
 hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **name);
 
-// lane-per-stream kernels (N = 1, 2, 4, 8 with at least kLaneKernelMinChunks chunks): lanes.hip
+// lane-per-stream kernels (N = 1, 2, 4, 8 with at least kLaneKernelMinChunks chunks): decode_lanes.hip, encode_lanes.hip
 constexpr uint64_t kLaneKernelMinChunks = 64;
 inline bool lanes_applicable(uint64_t nchunks, uint32_t n_ways)
 {
@@ -68,7 +68,7 @@ hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipS
 // true when launch_encode_lanes would take the staged kernel for this request -- the one that can place its chunks
 // itself (EncParams::status); everything but status / offsets / out / out_cap must be filled in
 bool encode_lanes_fused(const EncParams &p, int num_cus);
-// true when launch_encode_lanes would take a staged kernel for this SIZED-slot request (EncParams::ovf_ctl): lanes.hip
+// true when launch_encode_lanes would take a staged kernel for this SIZED-slot request (EncParams::ovf_ctl): encode_lanes.hip
 bool encode_lanes_sized_ok(int format, const EncParams &p, int num_cus);
 
 } // namespace rans_amd

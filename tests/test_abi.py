@@ -50,7 +50,7 @@ def test_shipped_library_is_not_the_measure_build():
         m.rans_amd_build_flags.restype = C.c_uint32
         assert m.rans_amd_build_flags() & 1  # RANS_AMD_BUILD_MEASURE
     # the product sources read the environment only inside measure_knob() / #ifdef RANS_AMD_MEASURE
-    for fn in ("api.cpp", "dispatch.cpp", "lanes.hip", "encode_wave.hip", "decode_wave.hip", "decode_dual.hip"):
+    for fn in ("api.cpp", "dispatch.cpp", "decode_lanes.hip", "encode_lanes.hip", "encode_wave.hip", "decode_wave.hip", "decode_dual.hip"):
         text = open(os.path.join(ROOT, "ryg_rans_amd", "csrc", fn)).read()
         assert "getenv(" not in text, fn
 

@@ -81,7 +81,7 @@ KERNEL_ROWS = [
     _row("byte-2", FMT_BYTE, 14, 256, 2, 256, 32, "k_decode_byte_pairs", _by((B, 1), (ST, 0)), _by((B, 2), (ST, 2)), _by((B, 2), (ST, 2))),
     _row("byte-2-lane-fused", FMT_BYTE, 14, 256, 2, 256, 32, "k_decode_byte_pairs", _by((B, 1), (ST, 1)), _by((B, 2), (ST, 2)),
          _by((B, 2), (ST, 2)), opts=((LANE_FUSED, 1),)),
-    # ---- one chunk per lane (lanes.hip): 64 chunks per unit
+    # ---- one chunk per lane (decode_lanes.hip, encode_lanes.hip): 64 chunks per unit
     _row("r64-2-packed", FMT_R64, 14, 256, 2, 128, 64, "k_decode_lanes_r64x2<packed slots>", _by((L16, 0), (RX, 0)),
          _by((L16, 2), (RX, 2)), _by(("k_encode<r64>", 2), (RX, 2))),
     _row("r64-2-16bit", FMT_R64, 16, 256, 2, 128, 64, "k_decode_lanes_r64x2", _by((L16, 0), (RX, 0)), _by((L16, 2), (RX, 2)),

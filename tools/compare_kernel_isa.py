@@ -1,23 +1,27 @@
 #!/usr/bin/env python3
-"""Do the uniform kernels of decode_wave.hip / encode_wave.hip compile to what they compiled to at another revision?
+"""Do the kernels of a set of files compile to what they compiled to at another revision?
 
     python tools/compare_kernel_isa.py <git revision> [file.hip ...]
+    python tools/compare_kernel_isa.py <git revision> --old lanes.hip --new decode_lanes.hip encode_lanes.hip
 
-Both versions of every file are compiled for gfx950 to assembly (device side only, the Makefile's flags); every kernel of
-the old revision is paired with the kernel of the same name in the working tree -- a trailing `false` template argument
-that the tree added (RAGGED) is ignored, k_decode_word64_t<false> is k_decode_word64 -- and their opcode sequences, VGPR
-counts and scratch sizes are compared.  Prints one line per file and the kernels that differ; exit status 1 if any does.
-The revision must be one from before the RAGGED template parameter existed (norm() below maps the tree's mangled names
-back to the old ones by dropping that argument).  No GPU needed."""
+The files of the old side are compiled as they were at the revision, those of the new side as they are in the working tree
+(device side only, for gfx950, the Makefile's flags), and the kernels of each side are pooled: a kernel may have moved from
+one file to another.  Kernels are paired by their exact mangled name; of every pair the opcode sequence, next_free_vgpr,
+private_segment_fixed_size (scratch) and group_segment_fixed_size (static LDS) are compared, and kernels that only one side
+has are reported.  Prints one table row per kernel and a summary; exit status 1 unless every kernel is on both sides and
+equal.  Without --old / --new both sides take the files named (default: decode_wave.hip encode_wave.hip).  No GPU needed."""
+import argparse
 import os
 import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = "ryg_rans_amd/csrc"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-S"]
+FIELDS = ("next_free_vgpr", "private_segment_fixed_size", "group_segment_fixed_size")
 
 
 def kernels(asm):
@@ -26,44 +30,65 @@ def kernels(asm):
         ops = [ln.split()[0] for ln in m.group(2).split("\n")
                if ln.strip() and not ln.strip().startswith((";", ".")) and not ln.strip().endswith(":")]
         meta = re.search(r"\.amdhsa_kernel " + re.escape(m.group(1)) + r"\n(.*?)\.end_amdhsa_kernel", asm, re.S).group(1)
-        res = tuple(re.findall(r"\.amdhsa_(next_free_vgpr|private_segment_fixed_size)\s+(\S+)", meta))
+        res = tuple(re.search(r"\.amdhsa_%s\s+(\S+)" % f, meta).group(1) for f in FIELDS)
         out[m.group(1)] = (ops, res)
     return out
 
 
-def norm(name):
-    return name.replace("17k_decode_word64_tILb0EEEv", "15k_decode_word64E").replace("Lb0E", "")
-
-
-def compile_asm(srcdir, fn, out):
+def compile_asm(job):
+    srcdir, fn, out = job
     subprocess.run(["/opt/rocm/bin/hipcc"] + FLAGS + [fn, "-o", out], cwd=srcdir, check=True, stderr=subprocess.DEVNULL)
-    return open(out).read()
+    return kernels(open(out).read())
 
 
 def main():
-    rev = sys.argv[1]
-    files = sys.argv[2:] or ["decode_wave.hip", "encode_wave.hip"]
-    bad = 0
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("rev", help="git revision of the old side")
+    ap.add_argument("files", nargs="*", help="files of both sides (in %s)" % CSRC)
+    ap.add_argument("--old", nargs="+", help="files of the old side, at the revision")
+    ap.add_argument("--new", nargs="+", help="files of the new side, in the working tree")
+    args = ap.parse_args()
+    both = args.files or ["decode_wave.hip", "encode_wave.hip"]
+    old_files, new_files = args.old or both, args.new or both
     with tempfile.TemporaryDirectory() as tmp:
         old = os.path.join(tmp, CSRC)
         os.makedirs(old)
         os.makedirs(os.path.join(tmp, "include"))
-        listed = subprocess.run(["git", "ls-tree", "--name-only", rev, CSRC + "/", "include/ryg_rans_amd.h"], cwd=ROOT, check=True,
-                                capture_output=True, text=True).stdout.split()
+        listed = subprocess.run(["git", "ls-tree", "--name-only", args.rev, CSRC + "/", "include/ryg_rans_amd.h"], cwd=ROOT,
+                                check=True, capture_output=True, text=True).stdout.split()
         for path in listed:
-            blob = subprocess.run(["git", "show", "%s:%s" % (rev, path)], cwd=ROOT, check=True, capture_output=True).stdout
+            blob = subprocess.run(["git", "show", "%s:%s" % (args.rev, path)], cwd=ROOT, check=True, capture_output=True).stdout
             open(os.path.join(tmp, path), "wb").write(blob)
-        for fn in files:
-            a = kernels(compile_asm(old, fn, os.path.join(tmp, "old.s")))
-            b = {norm(k): v for k, v in kernels(compile_asm(os.path.join(ROOT, CSRC), fn, os.path.join(tmp, "new.s"))).items()
-                 if "Lb1E" not in k}
-            differ = [k for k in a if b.get(k) != a[k]]
-            print("%s: %d kernels at %s, %d with the same opcode sequence, VGPR count and scratch size in the tree"
-                  % (fn, len(a), rev, len(a) - len(differ)))
-            for k in differ:
-                print("   differs or missing:", k)
-            bad += len(differ)
-    sys.exit(1 if bad else 0)
+        jobs = [(old, fn, os.path.join(tmp, "old_%d.s" % i)) for i, fn in enumerate(old_files)] + \
+               [(os.path.join(ROOT, CSRC), fn, os.path.join(tmp, "new_%d.s" % i)) for i, fn in enumerate(new_files)]
+        with ThreadPoolExecutor(max_workers=4) as pool:
+            found = list(pool.map(compile_asm, jobs))
+    a, b, where = {}, {}, {}
+    for ks in found[:len(old_files)]:
+        a.update(ks)
+    for fn, ks in zip(new_files, found[len(old_files):]):
+        b.update(ks)
+        where.update((k, fn) for k in ks)
+    rev = subprocess.run(["git", "rev-parse", "--short", args.rev], cwd=ROOT, check=True, capture_output=True, text=True).stdout.strip()
+    print("old: %s at %s; new: %s in the tree\n" % (" ".join(old_files), rev, " ".join(new_files)))
+    print("| kernel | now in | instructions | %s | verdict |" % " | ".join(FIELDS))
+    print("|---|---|---|---|---|---|---|")
+    same = 0
+    for k in sorted(set(a) | set(b)):
+        if k not in b:
+            verdict = "ONLY AT THE REVISION"
+        elif k not in a:
+            verdict = "ONLY IN THE TREE"
+        elif a[k] != b[k]:
+            verdict = "DIFFERS (%d instructions, %s at the revision)" % (len(a[k][0]), " / ".join(a[k][1]))
+        else:
+            verdict = "same"
+            same += 1
+        ops, res = b.get(k) or a[k]
+        print("| `%s` | %s | %d | %s | %s |" % (k, where.get(k, "-"), len(ops), " | ".join(res), verdict))
+    print("\n%d kernels at the revision, %d in the tree, %d on both sides with the same opcode sequence, VGPR count, scratch "
+          "size and static LDS size" % (len(a), len(b), same))
+    sys.exit(0 if same == len(a) == len(b) else 1)
 
 
 if __name__ == "__main__":
