@@ -60,7 +60,8 @@ extern "C" {
  * (0.4.0); rans_amd_encode_slots_sized + rans_amd_tight_slot_bytes / rans_amd_encode_sized_bound, rans_amd_probe_placement,
  * rans_amd_encode_adaptive_fmt / rans_amd_decode_adaptive_fmt (0.5.0); rans_amd_encode_adaptive_sized,
  * rans_amd_container_pack_indexed[_adaptive] (0.6.0); ragged batches -- rans_amd_batch_layout, rans_amd_encode_batch,
- * rans_amd_decode_batch, rans_amd_batch_order, rans_amd_batch_slice (still 0.6.0: additions only).  A caller built
+ * rans_amd_decode_batch, rans_amd_batch_order, rans_amd_batch_slice, rans_amd_encode_batch_adaptive[_bound],
+ * rans_amd_decode_batch_adaptive (still 0.6.0: additions only).  A caller built
  * against an older header keeps working, with two behaviour changes it can observe: since 0.4.0
  * rans_amd_container_parse[_adaptive] want a 4-byte aligned `src` (RANS_AMD_E_ARG otherwise; an mmap at an odd offset must
  * be copied first), and since 0.5.0 rans_amd_container_compact checks its SOURCE index against src_bytes
@@ -481,6 +482,50 @@ int rans_amd_encode_adaptive_sized(rans_amd_ctx *ctx, int format, const void *d_
                                    uint64_t *d_offsets, uint32_t *d_lengths, uint16_t *d_chunk_freqs, uint64_t *h_total_bytes,
                                    void *stream);
 uint64_t rans_amd_encode_adaptive_sized_bound(int format, uint64_t n, uint32_t n_ways, uint32_t chunk_syms);
+
+/* ---- ragged batches with one model per stream (still 0.6.0: additions only) -----------------
+ *
+ * Independent reference streams each come with their own frequency table: the reference builds its model from the input
+ * it is about to code (main.cpp:139-162, main_simd.cpp:138-143).  These calls are the ragged batch calls above with that
+ * model per STREAM: stream c is the d_sym_counts[c] symbols at d_syms / d_out + d_sym_offsets[c], its row is
+ * d_stream_freqs[256 c .. 256 c + 255] = normalize_freqs(count_freqs(those symbols), 1 << scale_bits) exactly, and its
+ * stream is byte for byte the reference's stream of those symbols under that row.  Formats, scale_bits and n_ways as the
+ * per-chunk-model calls take them (byte format at 8..12 bits, word format at 12, u8 symbols over 256 values, n_ways
+ * 1..512; RANS_AMD_E_UNSUPPORTED otherwise); one scale_bits for the whole batch.  d_stream_freqs must be 8-byte aligned.
+ *   - A word-format stream that holds ONE symbol value (every stream of count 1 among them) has frequency 4096 = M and
+ *     leaves a word per symbol, as the reference does (see rans_amd_encode_adaptive_fmt).
+ *   - A stream of 0 symbols has no histogram: the encoder writes an all-zero row and the n_ways flushed initial states;
+ *     the decoder neither reads nor validates the row of such a stream.  Any other row that does not sum to
+ *     1 << scale_bits counts its stream as failed.
+ *
+ * Encoder: rans_amd_encode_adaptive_sized's placement, per stream.  Stream c gets a piece of whole 64-byte lines sized from
+ * its own histogram (never more than the worst case of its own count); piece c lies behind pieces 0 .. c-1, the stream is
+ * the LAST d_lengths[c] bytes of its piece, d_offsets[n_streams] = bytes of d_out in use.  The layout is the same from run
+ * to run.  out_cap: rans_amd_encode_batch_adaptive_bound() -- the sum of the per-stream worst cases, host, no GPU; 0 for
+ * arguments the encoder would refuse -- can never be exceeded; with less, streams whose piece does not fit are not coded
+ * (d_lengths[c] = 0) and the call, or rans_amd_encode_status, reports RANS_AMD_E_SPACE.
+ * The encoder takes NO d_order: a stream finds its place by a look-back over the pieces of its index predecessors, so
+ * streams are claimed in ascending index order and nothing else.
+ * in_syms: the number of symbols d_syms holds.  d_sym_offsets / d_sym_counts are data, and a device pointer does not say
+ * how much memory lies behind it, so the range of every stream is checked against [0, in_syms) before a symbol of it is
+ * read: a stream outside it (or longer than 0x7fff0000 symbols) is coded as an EMPTY stream -- zero row, flushed states,
+ * so that the index stays whole -- and the call, or rans_amd_encode_status, reports RANS_AMD_E_ARG.  Nothing outside the
+ * caller's buffers is ever read or written.  h_total_bytes as in rans_amd_encode_adaptive_sized (NULL: asynchronous); the
+ * first call of a context uploads a 32 KiB table: make one call outside a hipGraph capture first. */
+uint64_t rans_amd_encode_batch_adaptive_bound(int format, const uint32_t *sym_counts, uint64_t n_streams, uint32_t n_ways);
+int rans_amd_encode_batch_adaptive(rans_amd_ctx *ctx, int format, const void *d_syms, uint64_t in_syms,
+                                   const uint64_t *d_sym_offsets, const uint32_t *d_sym_counts, uint64_t n_streams,
+                                   uint32_t n_ways, uint32_t scale_bits, void *d_out, uint64_t out_cap, uint64_t *d_offsets,
+                                   uint32_t *d_lengths, uint16_t *d_stream_freqs, uint64_t *h_total_bytes, void *stream);
+/* Decoder: everything rans_amd_decode_batch promises -- d_order (the row index is the stream index AFTER the order), a
+ * symbol range outside [0, out_syms) skipped and counted, h_bad_streams, hipGraph capture after one eager call, element
+ * stores for outputs that are not 4-byte aligned -- with stream c's tables built from d_stream_freqs[256 c ..] by the
+ * wavefront that decodes it. */
+int rans_amd_decode_batch_adaptive(rans_amd_ctx *ctx, int format, const void *d_container, uint64_t container_bytes,
+                                   const uint64_t *d_offsets, const uint32_t *d_lengths, const uint16_t *d_stream_freqs,
+                                   const uint64_t *d_sym_offsets, const uint32_t *d_sym_counts, uint64_t n_streams,
+                                   uint32_t n_ways, uint32_t scale_bits, const uint32_t *d_order, void *d_out,
+                                   uint64_t out_syms, uint64_t *h_bad_streams, void *stream);
 
 /* ---- host-buffer convenience: one raw reference-format stream -------------- */
 

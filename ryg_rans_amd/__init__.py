@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "rans_amd_packed_payload_bytes", "rans_amd_container_pack_indexed", "rans_amd_container_pack_indexed_adaptive",
     "rans_amd_container_parse", "rans_amd_encode_workspace_bytes", "rans_amd_build_model_o0",
     "rans_amd_batch_layout", "rans_amd_encode_batch", "rans_amd_decode_batch", "rans_amd_batch_order", "rans_amd_batch_slice",
+    "rans_amd_encode_batch_adaptive_bound", "rans_amd_encode_batch_adaptive", "rans_amd_decode_batch_adaptive",
 ]
 
 
@@ -147,6 +148,9 @@ def _load():
         "rans_amd_decode_adaptive_fmt": (i32, [vp, i32, vp, u64, vp, vp, vp, u64, u32, u32, u32, vp, u64p, vp]),
         "rans_amd_encode_adaptive_sized": (i32, [vp, i32, vp, u64, u32, u32, u32, vp, u64, vp, vp, vp, u64p, vp]),
         "rans_amd_encode_adaptive_sized_bound": (u64, [i32, u64, u32, u32]),
+        "rans_amd_encode_batch_adaptive_bound": (u64, [i32, u32p, u64, u32]),
+        "rans_amd_encode_batch_adaptive": (i32, [vp, i32, vp, u64, vp, vp, u64, u32, u32, vp, u64, vp, vp, vp, u64p, vp]),
+        "rans_amd_decode_batch_adaptive": (i32, [vp, i32, vp, u64, vp, vp, vp, vp, vp, u64, u32, u32, vp, vp, u64, u64p, vp]),
         "rans_amd_encode_workspace_bytes": (u64, [i32, u64, u32, u32]),
         "rans_amd_build_model_o0": (i32, [vp, i32, vp, u64, i32, u32, u32, u32p, C.POINTER(vp), vp]),
         "rans_amd_offsets_from_lengths": (i32, [u32p, u64, u64p]),
@@ -259,6 +263,12 @@ def batch_slice(lengths, n_ranks):
     _check(_lib.rans_amd_batch_slice(lengths.ctypes.data_as(C.POINTER(C.c_uint32)), lengths.size, n_ranks,
                                      bounds.ctypes.data_as(C.POINTER(C.c_uint64))), "batch_slice")
     return bounds
+
+
+def encode_batch_adaptive_bound(fmt, sym_counts, n_ways):
+    """rans_amd_encode_batch_adaptive_bound: the capacity encode_batch_adaptive can never exceed (0: unsupported arguments)."""
+    counts = np.ascontiguousarray(sym_counts, dtype=np.uint32)
+    return int(_lib.rans_amd_encode_batch_adaptive_bound(fmt, counts.ctypes.data_as(C.POINTER(C.c_uint32)), counts.size, n_ways))
 
 
 class Context:
@@ -500,6 +510,51 @@ class Context:
                                         _torch_stream())
         if rc != OK:
             err = RansAmdError(rc, "decode_batch", _lib.rans_amd_last_error().decode())
+            err.bad_streams = int(bad.value)
+            raise err
+        return d_out
+
+    # -- ... each with its own model
+    def encode_batch_adaptive(self, d_syms, d_sym_offsets, d_sym_counts, n_ways, scale_bits, fmt=FMT_WORD, cap=None, d_out=None,
+                              sync=True, d_offsets=None, d_lengths=None, d_freqs=None, in_syms=None):
+        """rans_amd_encode_batch_adaptive: stream c = the d_sym_counts[c] symbols at d_sym_offsets[c] of d_syms (in_syms
+        symbols, default all of it), coded under its own model into a piece sized from its own histogram.  cap: bytes of the
+        container buffer (default: encode_batch_adaptive_bound, which reads the counts back).  Returns (d_container,
+        d_offsets[n_streams + 1], d_lengths, d_stream_freqs, total_bytes); without sync encode_status() reports."""
+        import torch
+        n_streams = d_sym_counts.numel()
+        dev = d_sym_counts.device
+        if d_out is None:
+            if cap is None:
+                cap = encode_batch_adaptive_bound(fmt, d_sym_counts.cpu().numpy().view(np.uint32), n_ways)
+            d_out = torch.empty(max(cap, 16), dtype=torch.uint8, device=dev)
+        if d_offsets is None:
+            d_offsets = torch.zeros(n_streams + 1, dtype=torch.int64, device=dev)
+        if d_lengths is None:
+            d_lengths = torch.zeros(max(n_streams, 1), dtype=torch.int32, device=dev)
+        if d_freqs is None:
+            d_freqs = torch.zeros(max(n_streams, 1) * 256, dtype=torch.int16, device=dev)
+        total = C.c_uint64(0)
+        _check(_lib.rans_amd_encode_batch_adaptive(self._h, fmt, d_syms.data_ptr(), d_syms.numel() if in_syms is None else in_syms,
+                                                   d_sym_offsets.data_ptr(), d_sym_counts.data_ptr(), n_streams, n_ways, scale_bits,
+                                                   d_out.data_ptr(), d_out.numel() if cap is None else cap, d_offsets.data_ptr(),
+                                                   d_lengths.data_ptr(), d_freqs.data_ptr(), C.byref(total) if sync else None,
+                                                   _torch_stream()), "encode_batch_adaptive")
+        return d_out, d_offsets, d_lengths, d_freqs, (total.value if sync else None)
+
+    def decode_batch_adaptive(self, d_container, container_bytes, d_offsets, d_lengths, d_freqs, d_sym_offsets, d_sym_counts,
+                              n_ways, scale_bits, d_out, fmt=FMT_WORD, d_order=None, out_syms=None, sync=True, n_streams=None):
+        """rans_amd_decode_batch_adaptive into d_out (out_syms symbols, default all of it); errors as decode_batch."""
+        n_streams = d_sym_counts.numel() if n_streams is None else n_streams
+        bad = C.c_uint64(0)
+        rc = _lib.rans_amd_decode_batch_adaptive(self._h, fmt, d_container.data_ptr(), container_bytes, d_offsets.data_ptr(),
+                                                 d_lengths.data_ptr(), d_freqs.data_ptr(), d_sym_offsets.data_ptr(),
+                                                 d_sym_counts.data_ptr(), n_streams, n_ways, scale_bits,
+                                                 d_order.data_ptr() if d_order is not None else None, d_out.data_ptr(),
+                                                 d_out.numel() if out_syms is None else out_syms, C.byref(bad) if sync else None,
+                                                 _torch_stream())
+        if rc != OK:
+            err = RansAmdError(rc, "decode_batch_adaptive", _lib.rans_amd_last_error().decode())
             err.bad_streams = int(bad.value)
             raise err
         return d_out

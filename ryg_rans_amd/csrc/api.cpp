@@ -175,6 +175,8 @@ int encode_flags_status(uint32_t flags)
         return fail(RANS_AMD_E_SPACE, "encode: container does not fit out_cap");
     if (flags & 4u) // (a kernel that addresses its LDS tables by raw offsets found them elsewhere: never code on that)
         return fail(RANS_AMD_E_HIP, "encode: internal error (dynamic LDS does not start at offset 0)");
+    if (flags & 2048u) // rans_amd_encode_batch_adaptive: such a stream was coded as an empty one, nothing of it was read
+        return fail(RANS_AMD_E_ARG, "encode_batch_adaptive: a stream's symbol range lies outside [0, in_syms), or holds more than 0x7fff0000 symbols");
     if (flags & 512u) // rans_amd_container_compact: an index entry (offset, length) does not lie inside the source buffer
         return fail(RANS_AMD_E_CORRUPT, "container_compact: a chunk of the source index lies outside [0, src_bytes)");
     if (flags & ~7u) { // a wait of the fused placement gave up (device_common.hpp SpinWatch; 256: a coder waiting for its scratch slot)
@@ -1729,6 +1731,24 @@ static int decode_adaptive_impl(rans_amd_ctx *ctx, const int format, const void 
     return RANS_AMD_OK;
 }
 
+// reciprocals by frequency (model.cpp adapt_rcp_tables) for the one-kernel per-chunk-model encoders: built once per context
+static int ensure_adapt_rcp(rans_amd_ctx *ctx, const CaptureScope &capture, const char *first_outside_capture)
+{
+    if (ctx->adapt_rcp.ptr)
+        return RANS_AMD_OK;
+    if (capture.active)
+        return fail(RANS_AMD_E_ARG, first_outside_capture);
+    std::vector<uint32_t> t;
+    adapt_rcp_tables(t);
+    RC_TRY(ctx->adapt_rcp.reserve(t.size() * 4));
+    const hipError_t e = hipMemcpy(ctx->adapt_rcp.ptr, t.data(), t.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        ctx->adapt_rcp.release();
+        return hip_fail(e, "per-chunk-model encoder: table upload");
+    }
+    return RANS_AMD_OK;
+}
+
 // rans_amd_encode_adaptive_sized: the whole per-chunk-model encode as ONE kernel (encode_adaptive.hip)
 static int encode_adaptive_sized_impl(rans_amd_ctx *ctx, const int format, const void *d_syms, uint64_t n, uint32_t n_ways,
                                       uint32_t chunk_syms, uint32_t scale_bits, void *d_out, uint64_t out_cap,
@@ -1755,20 +1775,7 @@ static int encode_adaptive_sized_impl(rans_amd_ctx *ctx, const int format, const
     const uint64_t worst = encode_slot_bytes(format, n, n_ways, chunk_syms);
     if (worst > 0xfffffff0ull || nchunks >= (1ull << 32))
         return fail(RANS_AMD_E_UNSUPPORTED, "encode_adaptive_sized: chunk_syms too large, or 2^32 chunks and more");
-    if (!ctx->adapt_rcp.ptr) { // reciprocals by frequency (model.cpp adapt_rcp_tables): built once per context
-        if (capture.active)
-            return fail(RANS_AMD_E_ARG, "encode_adaptive_sized: make the same call once outside the capture first (a table is uploaded on first use)");
-        std::vector<uint32_t> t;
-        adapt_rcp_tables(t);
-        int rc = ctx->adapt_rcp.reserve(t.size() * 4);
-        if (rc)
-            return rc;
-        const hipError_t e = hipMemcpy(ctx->adapt_rcp.ptr, t.data(), t.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            ctx->adapt_rcp.release();
-            return hip_fail(e, "encode_adaptive_sized: table upload");
-        }
-    }
+    RC_TRY(ensure_adapt_rcp(ctx, capture, "encode_adaptive_sized: make the same call once outside the capture first (a table is uploaded on first use)"));
     // a look-back word per chunk, then the claim counters (a line each)
     const size_t ctl_bytes = (size_t)nchunks * 8 + (size_t)kWorkPools * kWorkPoolStride * 4;
     RC_TRY(ctx->enc_status.reserve(ctl_bytes));
@@ -1868,6 +1875,147 @@ int rans_amd_decode_adaptive_fmt(rans_amd_ctx *ctx, int format, const void *d_co
 {
     return decode_adaptive_impl(ctx, format, d_container, container_bytes, d_offsets, d_lengths, d_chunk_freqs, n, n_ways, chunk_syms,
                                 scale_bits, d_out, h_bad_chunks, stream);
+}
+
+/* ---- ragged batches with one model per stream ------------------------------ */
+
+uint64_t rans_amd_encode_batch_adaptive_bound(int format, const uint32_t *sym_counts, uint64_t n_streams, uint32_t n_ways)
+{
+    if ((format != RANS_AMD_FMT_BYTE && format != RANS_AMD_FMT_WORD) || !ways_supported(format, n_ways) || (n_streams && !sym_counts))
+        return 0;
+    // every stream in the worst-case piece of its own count (a stream's own bound is never larger), whole 64-byte lines
+    uint64_t total = 0;
+    for (uint64_t c = 0; c < n_streams; ++c)
+        total += (rans_amd_chunk_bound(format, sym_counts[c], n_ways) + 63) & ~uint64_t(63);
+    return n_streams ? total : 16;
+}
+
+int rans_amd_encode_batch_adaptive(rans_amd_ctx *ctx, int format, const void *d_syms, uint64_t in_syms, const uint64_t *d_sym_offsets,
+                                   const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, uint32_t scale_bits, void *d_out,
+                                   uint64_t out_cap, uint64_t *d_offsets, uint32_t *d_lengths, uint16_t *d_stream_freqs,
+                                   uint64_t *h_total_bytes, void *stream)
+{
+    if (!ctx || !d_out || !d_offsets || (in_syms && !d_syms) || (n_streams && (!d_sym_offsets || !d_sym_counts || !d_lengths || !d_stream_freqs)))
+        return fail(RANS_AMD_E_ARG, "encode_batch_adaptive: NULL argument");
+    if (int rc = adaptive_format_check(format, scale_bits, "encode_batch_adaptive"))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(d_stream_freqs) & 7u) != 0) // (a row is written with 8-byte stores per lane)
+        return fail(RANS_AMD_E_ARG, "encode_batch_adaptive: d_stream_freqs must be 8-byte aligned");
+    if (!ways_supported(format, n_ways))
+        return fail(RANS_AMD_E_UNSUPPORTED, "encode_batch_adaptive: n_ways must be in 1..512");
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15u) != 0)
+        return fail(RANS_AMD_E_ARG, "encode_batch_adaptive: d_out must be 16-byte aligned");
+    if (n_streams >= 0xffffffffull)
+        return fail(RANS_AMD_E_UNSUPPORTED, "encode_batch_adaptive: stream indices are 32-bit");
+    DeviceGuard guard(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CaptureScope capture(s);
+    if (capture.active && h_total_bytes)
+        return fail(RANS_AMD_E_ARG, "encode_batch_adaptive: h_total_bytes must be NULL while the stream is capturing");
+    RC_TRY(ensure_adapt_rcp(ctx, capture, "encode_batch_adaptive: make the same call once outside the capture first (a table is uploaded on first use)"));
+    // a look-back word per stream, then the claim counters (a line each)
+    const size_t ctl_bytes = (size_t)n_streams * 8 + (size_t)kWorkPools * kWorkPoolStride * 4;
+    RC_TRY(ctx->enc_status.reserve(ctl_bytes));
+    {
+        ZeroList zero(s);
+        HIP_TRY(zero.add(ctx->d_enc_flags(), 8)); // (encode + histogram flags; a compaction's verdict stays until reported, as in encode_impl)
+        HIP_TRY(zero.add(ctx->enc_status.ptr, ctl_bytes));
+        if (n_streams == 0)
+            HIP_TRY(zero.add(d_offsets, 8));
+        HIP_TRY(zero.flush());
+    }
+    if (n_streams) {
+        if (ctx->timing && !t_capturing)
+            HIP_TRY(hipEventRecord(ctx->ev[2], s));
+        AdaptEncParams ap{};
+        ap.syms = static_cast<const uint8_t *>(d_syms);
+        ap.n = in_syms;
+        ap.nchunks = n_streams;
+        ap.n_ways = n_ways;
+        ap.scale_bits = scale_bits;
+        ap.out = static_cast<uint8_t *>(d_out);
+        ap.out_cap = out_cap;
+        ap.offsets = d_offsets;
+        ap.lengths = d_lengths;
+        ap.chunk_freqs = d_stream_freqs;
+        ap.flags = ctx->d_enc_flags();
+        ap.status = static_cast<unsigned long long *>(ctx->enc_status.ptr);
+        ap.claims = reinterpret_cast<unsigned int *>(ap.status + n_streams);
+        // (watchdog of the look-back: half a minute plus what ONE wave may need to count a stream as long as the whole input)
+        ap.wait_ticks = 30ull * 100000000ull + (in_syms / 64u) * 100ull;
+        ap.rcp = static_cast<const uint32_t *>(ctx->adapt_rcp.ptr);
+        ap.sym_offsets = d_sym_offsets;
+        ap.sym_counts = d_sym_counts;
+        HIP_TRY(launch_encode_batch_models(format, ap, ctx->num_cus, s, &ctx->last_enc_kernel));
+        ctx->last_enc_fused = false;
+        ctx->last_enc_slots = true;
+        if (ctx->timing && !t_capturing) {
+            HIP_TRY(hipEventRecord(ctx->ev[3], s));
+            ctx->enc_timed = true;
+        }
+    }
+    if (h_total_bytes) {
+        uint32_t flags = 0;
+        RC_TRY(read_total_and_flags(ctx, s, d_offsets + n_streams, h_total_bytes, &flags));
+        if (flags & 1u)
+            return fail(RANS_AMD_E_MODEL, "encode_batch_adaptive: a stream's counts could not be normalised");
+        return encode_flags_status(flags);
+    }
+    return RANS_AMD_OK;
+}
+
+int rans_amd_decode_batch_adaptive(rans_amd_ctx *ctx, int format, const void *d_container, uint64_t container_bytes,
+                                   const uint64_t *d_offsets, const uint32_t *d_lengths, const uint16_t *d_stream_freqs,
+                                   const uint64_t *d_sym_offsets, const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways,
+                                   uint32_t scale_bits, const uint32_t *d_order, void *d_out, uint64_t out_syms,
+                                   uint64_t *h_bad_streams, void *stream)
+{
+    if (!ctx || (n_streams && (!d_container || !d_offsets || !d_lengths || !d_stream_freqs || !d_sym_offsets || !d_sym_counts ||
+                               (out_syms && !d_out))))
+        return fail(RANS_AMD_E_ARG, "decode_batch_adaptive: NULL argument");
+    if (int rc = adaptive_format_check(format, scale_bits, "decode_batch_adaptive"))
+        return rc;
+    if ((reinterpret_cast<uintptr_t>(d_stream_freqs) & 7u) != 0)
+        return fail(RANS_AMD_E_ARG, "decode_batch_adaptive: d_stream_freqs must be 8-byte aligned");
+    if (!ways_supported(format, n_ways))
+        return fail(RANS_AMD_E_UNSUPPORTED, "decode_batch_adaptive: n_ways must be in 1..512");
+    if ((reinterpret_cast<uintptr_t>(d_container) & 15u) != 0)
+        return fail(RANS_AMD_E_ARG, "decode_batch_adaptive: d_container must be 16-byte aligned");
+    if (n_streams >= 0xffffffffull)
+        return fail(RANS_AMD_E_UNSUPPORTED, "decode_batch_adaptive: stream indices are 32-bit");
+    DeviceGuard guard(ctx->device);
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const CaptureScope capture(s);
+    if (capture.active && h_bad_streams)
+        return fail(RANS_AMD_E_ARG, "decode_batch_adaptive: h_bad_streams must be NULL while the stream is capturing (rans_amd_decode_errors after the replay)");
+    if (n_streams) {
+        DecParams dp{};
+        dp.container = static_cast<const uint8_t *>(d_container);
+        dp.container_bytes = container_bytes;
+        dp.offsets = d_offsets;
+        dp.lengths = d_lengths;
+        dp.out = static_cast<uint8_t *>(d_out);
+        dp.nchunks = n_streams;
+        dp.n_ways = n_ways;
+        dp.scale_bits = scale_bits;
+        dp.log2nsyms = 8;
+        dp.sym_bytes = 1;
+        dp.err_count = ctx->d_err();
+        dp.chunk_freqs = d_stream_freqs;
+        dp.sym_offsets = d_sym_offsets;
+        dp.sym_counts = d_sym_counts;
+        dp.order = d_order;
+        dp.out_syms = out_syms;
+        // (no model tables: every wave builds its stream's from the stream's frequency row; no wave_scratch, variant 0)
+        RC_TRY(take_counter_slot(ctx, capture, s, dp)); // (n_streams fits the 32-bit counters: checked above)
+        const int dec_format = format == RANS_AMD_FMT_WORD ? kKernelFormatWordAdaptive : kKernelFormatByteAdaptive;
+        RC_TRY(launch_decoder(ctx, capture, s, launch_decode_batch_models, dec_format, dp));
+    }
+    if (h_bad_streams)
+        RC_TRY(read_bad_count(ctx, s, h_bad_streams, "decode_batch_adaptive: at least one stream failed its integrity check"));
+    return RANS_AMD_OK;
 }
 
 /* ---- host-buffer wrappers: one raw reference-format stream ----------------- */

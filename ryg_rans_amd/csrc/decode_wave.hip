@@ -155,10 +155,11 @@ __device__ __forceinline__ void decode_group_word(uint32_t &x, uint32_t &pa, uin
 // RAGGED (rans_amd_decode_batch): the symbol side of a stream is data as well -- claim k takes stream order[k] (or k), its
 // output position and symbol count come from sym_offsets[] / sym_counts[] instead of c * chunk_syms, and the dword store
 // path is chosen per stream from the output address.  The uniform instantiations never read those fields.
+// RAGGED with per-chunk models (rans_amd_decode_batch_adaptive): the row of a stream is chunk_freqs[256 c] with c the stream
+// index AFTER `order`; a stream of 0 symbols has no histogram, so its row is neither read nor validated.
 template <int FMT, int K, int OUT, bool RAGGED = false>
 __global__ void __launch_bounds__(kDecBlockThreads, (K <= 2 ? 8 : 4)) k_decode(const DecParams p)
 {
-    static_assert(!RAGGED || !kIsAdaptive<FMT>, "per-chunk models have no ragged form");
     using Tr = FmtTraits<FMT>;
     using state_t = typename Tr::state_t;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -278,7 +279,10 @@ __global__ void __launch_bounds__(kDecBlockThreads, (K <= 2 ? 8 : 4)) k_decode(c
         }
 
         if constexpr (kIsAdaptive<FMT>) { // this chunk's model -> this wave's tables (main.cpp:139-162 / main_simd.cpp:138-143 per chunk)
-            if (!adapt_build_dec(p.chunk_freqs + chunk * 256u, p.scale_bits, lane, const_cast<uint8_t *>(T.t0),
+            bool has_row = true;
+            if constexpr (RAGGED)
+                has_row = nsym != 0; // (wave-uniform; nothing is looked up for such a stream, the tables may be stale)
+            if (has_row && !adapt_build_dec(p.chunk_freqs + chunk * 256u, p.scale_bits, lane, const_cast<uint8_t *>(T.t0),
                                  reinterpret_cast<uint32_t *>(const_cast<uint8_t *>(T.t1)))) {
                 if (lane == 0)
                     atomicAdd(p.err_count, 1ull);
@@ -904,6 +908,24 @@ hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus,
     case FMT_R64S: return launch_decode_batch_f<FMT_R64S>(p, num_cus, stream);
     case FMT_WORD16: return launch_decode_batch_f<FMT_WORD16>(p, num_cus, stream);
     case FMT_ALIAS: return launch_decode_batch_f<FMT_ALIAS>(p, num_cus, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+// ... with one model per stream (rans_amd_decode_batch_adaptive): the uniform adaptive decoder's four-wave workgroups
+hipError_t launch_decode_batch_models_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel)
+{
+    if (!p.sym_offsets || !p.sym_counts || p.sym_bytes != 1)
+        return hipErrorInvalidValue;
+    switch (format) {
+    case FMT_WORDA:
+        if (models_batch_kernel)
+            *models_batch_kernel = "k_decode_batch_models<word>";
+        return launch_decode_batch_f<FMT_WORDA>(p, num_cus, stream);
+    case FMT_BYTEA:
+        if (models_batch_kernel)
+            *models_batch_kernel = "k_decode_batch_models<byte>";
+        return launch_decode_batch_f<FMT_BYTEA>(p, num_cus, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -36,6 +36,11 @@ hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipS
     return launch_decode_batch_wave(format, p, num_cus, stream, batch_kernel);
 }
 
+hipError_t launch_decode_batch_models(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel)
+{
+    return launch_decode_batch_models_wave(format, p, num_cus, stream, models_batch_kernel);
+}
+
 hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
 {
     return launch_encode_batch_wave(format == kKernelFormatWord16 ? (int)RANS_AMD_FMT_WORD : format, p, num_cus, stream, batch_kernel);

@@ -98,11 +98,19 @@ __device__ __forceinline__ void adapt_substep(uint32_t &x, const u32x4 rec, bool
 //  at RR = 16 three spill-free waves beat four that spill 22 registers, 0.874 against 0.984 ms for the word format)
 constexpr int adapt_waves_per_simd(int K, int RR) { return K != 1 ? (K <= 4 ? 4 : 2) : RR >= 16 ? 3 : RR >= 4 ? 4 : kAdaptWavesPerSimd; }
 
-template <int FMT, int K, int RR>
+// RAGGED (rans_amd_encode_batch_adaptive): a "chunk" is a stream of the batch -- its symbols are the sym_counts[c] at syms +
+// sym_offsets[c] (caller data: a range that does not lie inside [0, n) is not read, see below), always in the two-pass form;
+// the 16-byte count path and the staged coding loop are chosen per stream from the stream's own first address, the worst
+// case a piece is capped by follows from the stream's own count, and a stream of 0 symbols -- no histogram to normalise --
+// gets an all-zero row and the flushed initial states.  The uniform instantiations never read those fields.
+constexpr uint32_t kAdaptMaxStreamSyms = 0x7fff0000u; // ragged: a stream's worst case (2 bytes a symbol + the states) stays a 32-bit size
+
+template <int FMT, int K, int RR, bool RAGGED = false>
 __global__ void __launch_bounds__(64, adapt_waves_per_simd(K, RR)) k_encode_adaptive(const AdaptEncParams p)
 {
     static_assert(FMT == FMT_WORD || FMT == FMT_BYTE, "per-chunk models: the byte and the word format");
     static_assert(RR == 0 || K == 1, "register-resident chunks: one state per lane");
+    static_assert(!RAGGED || RR == 0, "register-resident chunks have no ragged form");
     constexpr bool kRR = RR > 0;
     using Tr = FmtTraits<FMT>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -127,8 +135,20 @@ __global__ void __launch_bounds__(64, adapt_waves_per_simd(K, RR)) k_encode_adap
         const uint64_t chunk = (uint64_t)uniform(got) * npools + pool;
         if (chunk >= p.nchunks)
             break;
-        const uint64_t first = chunk * p.chunk_syms;
-        const uint32_t nsym = (uint32_t)((p.n - first) < p.chunk_syms ? (p.n - first) : p.chunk_syms);
+        uint64_t first = chunk * p.chunk_syms;
+        uint32_t nsym = (uint32_t)((p.n - first) < p.chunk_syms ? (p.n - first) : p.chunk_syms);
+        if constexpr (RAGGED) {
+            // the symbol index is the caller's data: a range outside [0, n) (or too long for a 32-bit piece) is never read --
+            // the stream is coded as an empty one, so that its successors' look-back still finds a piece, and bit 11 is set
+            first = uniform64(p.sym_offsets[chunk]);
+            nsym = uniform(p.sym_counts[chunk]);
+            if (!(first <= p.n && nsym <= p.n - first && nsym <= kAdaptMaxStreamSyms)) { // wave-uniform
+                if (lane == 0)
+                    atomicOr(p.flags, 2048u);
+                first = 0;
+                nsym = 0;
+            }
+        }
         const uint8_t RANS_GLOBAL *src = (const uint8_t RANS_GLOBAL *)p.syms + first;
 
         // (register-resident form: the whole chunk, in the coding loop's layout -- lane l holds row 4 j + (l & 3), columns
@@ -231,8 +251,15 @@ __global__ void __launch_bounds__(64, adapt_waves_per_simd(K, RR)) k_encode_adap
         }
 
         // ---- 2. normalise (normalize_freqs, main.cpp:75-129) and hand the row out
-        if (!adapt_normalize(cnt, nsym, M, lane, width))
-            failed = true;
+        if constexpr (RAGGED) {
+            if (nsym == 0u) // (wave-uniform) nothing to normalise: the all-zero row
+                width[0] = width[1] = width[2] = width[3] = 0u;
+            else if (!adapt_normalize(cnt, nsym, M, lane, width))
+                failed = true;
+        } else {
+            if (!adapt_normalize(cnt, nsym, M, lane, width))
+                failed = true;
+        }
         const u32x2 packed = {width[0] | (width[1] << 16), width[2] | (width[3] << 16)};
         *reinterpret_cast<u32x2 RANS_GLOBAL *>(reinterpret_cast<uint64_t>(p.chunk_freqs) + chunk * 512u + 8u * lane) = packed;
         adapt_cum(width, lane, cum);
@@ -264,7 +291,12 @@ __global__ void __launch_bounds__(64, adapt_waves_per_simd(K, RR)) k_encode_adap
         const uint64_t slack = (FMT == FMT_WORD ? ((uint64_t)nsym * 23u) >> 11 : (uint64_t)nsym >> 12) + N * Tr::kStateBytes + 64u;
         uint64_t need = (est < 4.0e9f ? (uint64_t)est : 0xffffffffull) + slack;
         need = (need + 63u) & ~63ull;
-        need = (need < p.worst_slot && !always) ? need : p.worst_slot;
+        if constexpr (RAGGED) { // the worst case of THIS stream's count (rans_amd_chunk_bound in whole 64-byte lines)
+            const uint64_t worst = ((uint64_t)nsym * 2u + N * Tr::kStateBytes + 63u) & ~63ull;
+            need = (need < worst && !always) ? need : worst;
+        } else {
+            need = (need < p.worst_slot && !always) ? need : p.worst_slot;
+        }
         if (lane == 0) // (the successors' look-back adds this up while the records below are being built)
             __hip_atomic_store(p.status + chunk, kStAggregate | need, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
@@ -294,7 +326,11 @@ __global__ void __launch_bounds__(64, adapt_waves_per_simd(K, RR)) k_encode_adap
         // ---- 5. code: rounds last to first, into the place the bound bought
         const uint32_t rounds = uniform(nsym / N);
         const uint32_t tail = uniform(nsym - rounds * N);
-        const bool fast_in = K == 1 && N == 64u && lds_at_zero && ((reinterpret_cast<uintptr_t>(p.syms) | p.chunk_syms) & 3u) == 0;
+        bool fast_in = K == 1 && N == 64u && lds_at_zero;
+        if constexpr (RAGGED)
+            fast_in = fast_in && (reinterpret_cast<uintptr_t>(src) & 3u) == 0;
+        else
+            fast_in = fast_in && ((reinterpret_cast<uintptr_t>(p.syms) | p.chunk_syms) & 3u) == 0;
         const uint32_t fast_rounds = (fast_in && !always) ? (rounds & ~15u) : 0u;
         {
             unsigned long long base = 0;
@@ -531,13 +567,13 @@ __global__ void __launch_bounds__(64, adapt_waves_per_simd(K, RR)) k_encode_adap
         atomicOr(p.flags, 1u);
 }
 
-template <int FMT, int K, int RR> hipError_t launch_t(const AdaptEncParams &p, int num_cus, hipStream_t stream)
+template <int FMT, int K, int RR, bool RAGGED = false> hipError_t launch_t(const AdaptEncParams &p, int num_cus, hipStream_t stream)
 {
     // workgroups per CU: 6 KiB of LDS each allow 25 (profiles/r06_wg_residency.log), the registers kAdaptPerCu and fewer
     const uint64_t per_cu = K != 1 ? (K <= 4 ? 16 : 8) : (uint64_t)adapt_waves_per_simd(K, RR) * 4;
     const uint64_t cap = (uint64_t)num_cus * (per_cu < (uint64_t)kAdaptPerCu ? per_cu : (uint64_t)kAdaptPerCu);
     const uint32_t grid = (uint32_t)(p.nchunks < cap ? (p.nchunks ? p.nchunks : 1) : cap);
-    RANS_LAUNCH((k_encode_adaptive<FMT, K, RR>), dim3(grid), dim3(64), kAdaptEncLds, stream, p);
+    RANS_LAUNCH((k_encode_adaptive<FMT, K, RR, RAGGED>), dim3(grid), dim3(64), kAdaptEncLds, stream, p);
     return hipGetLastError();
 }
 
@@ -562,7 +598,39 @@ template <int FMT> hipError_t launch_f(const AdaptEncParams &p, int num_cus, hip
     return hipErrorInvalidValue;
 }
 
+// ragged batches: the two-pass form for every stream, by the interleave alone
+template <int FMT> hipError_t launch_batch_f(const AdaptEncParams &p, int num_cus, hipStream_t s)
+{
+    if (p.n_ways >= 1 && p.n_ways <= 64)
+        return launch_t<FMT, 1, 0, true>(p, num_cus, s);
+    if (p.n_ways <= 128)
+        return launch_t<FMT, 2, 0, true>(p, num_cus, s);
+    if (p.n_ways <= 256)
+        return launch_t<FMT, 4, 0, true>(p, num_cus, s);
+    if (p.n_ways <= 512)
+        return launch_t<FMT, 8, 0, true>(p, num_cus, s);
+    return hipErrorInvalidValue;
+}
+
 } // namespace
+
+hipError_t launch_encode_batch_models(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel)
+{
+    if (!p.rcp || !p.claims || !p.status || !p.sym_offsets || !p.sym_counts || p.scale_bits < 8 || p.scale_bits > kAdaptMaxScaleBits ||
+        (format == FMT_WORD && p.scale_bits != 12))
+        return hipErrorInvalidValue;
+    switch (format) {
+    case FMT_WORD:
+        if (models_batch_kernel)
+            *models_batch_kernel = "k_encode_batch_models<word>";
+        return launch_batch_f<FMT_WORD>(p, num_cus, stream);
+    case FMT_BYTE:
+        if (models_batch_kernel)
+            *models_batch_kernel = "k_encode_batch_models<byte>";
+        return launch_batch_f<FMT_BYTE>(p, num_cus, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
 
 hipError_t launch_encode_adaptive(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **name)
 {

@@ -89,7 +89,8 @@ struct DecParams {
     unsigned long long *err_count; // failed chunks (device counter)
     unsigned int *work_counter;    // next chunk to hand out (zero at launch); NULL = static striding
     unsigned int *work_counter_reset; // a counter slot of a LATER launch that this launch zeroes
-    const uint16_t *chunk_freqs;      // FMT_BYTEA: normalised frequencies, u16[256] per chunk (else NULL)
+    const uint16_t *chunk_freqs;      // FMT_BYTEA / FMT_WORDA: normalised frequencies, u16[256] per chunk -- per STREAM in a ragged
+                                      // batch (rans_amd_decode_batch_adaptive), indexed by the stream index after `order` (else NULL)
     uint8_t *wave_scratch;            // one 64-byte line per resident wave (marker stores of the window refills), or NULL
     uint32_t variant;                 // kVar* bits
     unsigned long long *span;         // this launch's {max of ~(wave start), max of wave end} in 100 MHz ticks, or NULL
@@ -285,9 +286,20 @@ struct AdaptEncParams {
     unsigned long long *status; // one look-back word per chunk (AGGREGATE | piece size, then PREFIX | end of the piece); zero at launch
     unsigned long long wait_ticks; // how long a look-back may wait (device_common.hpp SpinWatch); 0 = the default half minute
     const uint32_t *rcp;     // [2][kAdaptRcpEntries]: Alverson reciprocals by frequency, then the round-up ones (model.cpp adapt_rcp_tables)
+    // Ragged batches with one model per stream (rans_amd_encode_batch_adaptive; k_encode_adaptive's RAGGED form, nobody else
+    // reads these): stream c is the sym_counts[c] symbols at syms + sym_offsets[c]; n is then the number of symbols `syms`
+    // holds -- a range outside [0, n) is not read, the stream is coded as an empty one and bit 11 of *flags is set.
+    // chunk_syms and worst_slot are not read (a stream's worst case follows from its own count); status holds one word
+    // per stream
+    const uint64_t *sym_offsets;
+    const uint32_t *sym_counts;
 };
 constexpr uint32_t kAdaptRcpEntries = 4097; // frequencies 0 .. 4096 (per-chunk models: scale_bits <= 12)
 hipError_t launch_encode_adaptive(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **name);
+// ... its ragged form and the ragged decoder with one model per stream (decode_wave.hip); *models_batch_kernel receives the
+// name of the kernel that was launched.  The decoder's `format` is kKernelFormatByteAdaptive / kKernelFormatWordAdaptive.
+hipError_t launch_encode_batch_models(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel);
+hipError_t launch_decode_batch_models(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel);
 
 // (format, n_ways) combinations with a kernel.
 bool ways_supported(int format, uint32_t n_ways);

@@ -40,6 +40,8 @@ hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipSt
 // ... their ragged forms (one stream per wave, per-stream symbol ranges): the names go to *batch_kernel
 hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
 hipError_t launch_encode_batch_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
+// ... and the ragged decoder with one model per stream (format: kKernelFormatByteAdaptive / kKernelFormatWordAdaptive)
+hipError_t launch_decode_batch_models_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel);
 
 // two chunks per wave, 64-way, byte-stream formats (decode_dual.hip); format: kKernelFormatAlias2[W] or RANS_AMD_FMT_BYTE
 hipError_t launch_decode_dual(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name);

@@ -9,7 +9,11 @@ The files of the old side are compiled as they were at the revision, those of th
 one file to another.  Kernels are paired by their exact mangled name; of every pair the opcode sequence, next_free_vgpr,
 private_segment_fixed_size (scratch) and group_segment_fixed_size (static LDS) are compared, and kernels that only one side
 has are reported.  Prints one table row per kernel and a summary; exit status 1 unless every kernel is on both sides and
-equal.  Without --old / --new both sides take the files named (default: decode_wave.hip encode_wave.hip).  No GPU needed."""
+equal.  Without --old / --new both sides take the files named (default: decode_wave.hip encode_wave.hip).  No GPU needed.
+
+--new-default-false: the kernel templates of the tree gained a trailing `bool = false` template argument since the revision
+(a RAGGED form, say).  A kernel of the tree whose last template argument is `false` is then paired under the name it had
+without that argument; the instantiations with `true` stay what they are, kernels only the tree has."""
 import argparse
 import os
 import re
@@ -47,6 +51,8 @@ def main():
     ap.add_argument("files", nargs="*", help="files of both sides (in %s)" % CSRC)
     ap.add_argument("--old", nargs="+", help="files of the old side, at the revision")
     ap.add_argument("--new", nargs="+", help="files of the new side, in the working tree")
+    ap.add_argument("--new-default-false", action="store_true",
+                    help="pair a kernel of the tree whose last template argument is `false` with the old kernel without that argument")
     args = ap.parse_args()
     both = args.files or ["decode_wave.hip", "encode_wave.hip"]
     old_files, new_files = args.old or both, args.new or both
@@ -67,6 +73,8 @@ def main():
     for ks in found[:len(old_files)]:
         a.update(ks)
     for fn, ks in zip(new_files, found[len(old_files):]):
+        if args.new_default_false:  # (Itanium mangling: I<args>Lb0EE..Ev -- drop the Lb0E in front of the closing E's and the return type)
+            ks = {re.sub(r"Lb0E(E+v)", r"\1", k, count=1): v for k, v in ks.items()}
         b.update(ks)
         where.update((k, fn) for k in ks)
     rev = subprocess.run(["git", "rev-parse", "--short", args.rev], cwd=ROOT, check=True, capture_output=True, text=True).stdout.strip()
