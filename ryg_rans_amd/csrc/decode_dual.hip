@@ -8,7 +8,7 @@
 // consecutive chunks (2j, 2j + 1): two states per lane, two stream windows, the D steps of both issued back to back
 // and the renormalisation reads of both in flight together -- twice the independent work per wave at the same
 // occupancy.  Two more things change against k_decode<alias>:
-//   * alias tables in the FMT_ALIAS2 form (device_common.hpp): 9 VALU instructions per D step instead of 11, and the
+//   * alias tables in the FMT_ALIAS2 form (kernel_formats.hpp): 9 VALU instructions per D step instead of 11, and the
 //     symbol is the low half of the record's first word;
 //   * u16 symbols are stored per round (buffer_store_short, 128 contiguous bytes per wave) -- no packing of two
 //     rounds, no exchange between lane pairs: these decoders are bound by VALU issue (~4.3 cycles per wave64

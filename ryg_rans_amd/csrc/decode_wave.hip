@@ -729,159 +729,57 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64_t(const Dec
     record_span(p, t_start, smem);
 }
 
-constexpr auto k_decode_word64 = k_decode_word64_t<false>;
-constexpr auto k_decode_batch_word64 = k_decode_word64_t<true>;
-
-template <bool RAGGED = false>
-hipError_t launch_decode_word64(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+// ---- launch: wave_shape.hpp says which instance and with what geometry, this turns its answer into the template ----------
+template <int FMT, int K, int OUT, bool RAGGED> hipError_t launch_decode_t(const WaveLaunch &g, hipStream_t stream, const DecParams &p)
 {
-    auto kern = RAGGED ? k_decode_batch_word64 : k_decode_word64;
-    const uint32_t t0 = (p.table0_bytes + 15u) & ~15u;
-    const uint32_t waves = kWord64Threads / 64;
-    const size_t lds = (size_t)t0 + (size_t)waves * kRingStride;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
-        return e;
-    const uint64_t want = (p.nchunks + waves - 1) / waves;
-    const uint64_t cap = (uint64_t)num_cus * 2u;
-    const uint32_t grid = (uint32_t)(want < cap ? (want ? want : 1) : cap);
-    if (name)
-        *name = "k_decode_word64";
-    RANS_LAUNCH(kern, dim3(grid), dim3(kWord64Threads), lds, stream, p);
-    return hipGetLastError();
+    if constexpr (decode_is_word64(FMT, K, OUT))
+        return launch_wave_kernel<k_decode_word64_t<RAGGED>>(g, kCuLdsBytes, stream, p);
+    else if constexpr (decode_has(FMT, K, OUT, RAGGED))
+        return launch_wave_kernel<k_decode<FMT, K, OUT, RAGGED>>(g, kCuLdsBytes, stream, p);
+    else
+        return hipErrorInvalidValue; // (no such kernel, and decode_shape never asks for it)
 }
 
-template <int FMT, int K, int OUT, bool RAGGED = false>
-hipError_t launch_decode_t(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+// `name`: the uniform launcher's; the ragged launchers report names of their own and pass nullptr
+template <int FMT, bool RAGGED> hipError_t launch_decode_f(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {
-    // per-chunk models: every wave owns its tables (5 KiB) and window, nothing is shared -- workgroups of FOUR waves, five of
-    // them per CU: 20 waves where one 16-wave workgroup held 16, and one wave per SIMD from every workgroup (one- and two-wave
-    // workgroups spread unevenly over the CUs when the grid does not fill them: 0.84 / 0.80 ms against 0.73 for the word
-    // format, profiles/r06_adaptive_decoder.md)
-    constexpr uint32_t kAdaptDecThreads = 256;
-    const uint32_t threads = kIsAdaptive<FMT> ? kAdaptDecThreads : kDecBlockThreads;
-    const uint32_t waves = threads / 64;
-    const uint32_t t0 = kIsAdaptive<FMT> ? waves * kAdaptDecWaveLds : (p.table0_bytes + 15u) & ~15u;
-    const uint32_t t1 = kIsAdaptive<FMT> ? 0u : (p.table1_bytes + 15u) & ~15u;
+    const bool aligned = decode_out_aligned(FMT, reinterpret_cast<uintptr_t>(p.out), p.chunk_syms);
+    const DecodeShape s = decode_shape(FMT, p.n_ways, p.sym_bytes, aligned, RAGGED);
+    const WaveLaunch g = decode_launch(s.word64, kIsAdaptive<FMT>, p.table0_bytes, p.table1_bytes, p.nchunks, num_cus);
+    if (!s.K || !g.threads)
+        return hipErrorInvalidValue;
     if (kIsAdaptive<FMT> && (!p.chunk_freqs || p.scale_bits > kAdaptMaxScaleBits || p.scale_bits < 8 || (FMT == FMT_WORDA && p.scale_bits != 12)))
         return hipErrorInvalidValue;
-    const size_t lds = (size_t)t0 + t1 + (size_t)waves * kRingStride;
-    if (lds > 160 * 1024)
-        return hipErrorInvalidValue;
-    auto kern = k_decode<FMT, K, OUT, RAGGED>;
-    static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
-        return e;
-    int blocks_per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
-    if (kIsAdaptive<FMT> && threads < kDecBlockThreads) { // small workgroups: what the LDS allows, within 32 waves per CU
-        blocks_per_cu = (int)((160 * 1024) / ((lds + 255) & ~(size_t)255));
-        blocks_per_cu = blocks_per_cu * (int)waves > 32 ? 32 / (int)waves : blocks_per_cu;
-    }
-    uint64_t want = (p.nchunks + waves - 1) / waves;
-    uint64_t cap = (uint64_t)num_cus * blocks_per_cu;
-    const uint32_t grid = (uint32_t)(want < cap ? (want ? want : 1) : cap);
-    if (name && !RAGGED) // (the batch launcher reports its own names: launch_decode_batch_wave)
-        *name = FMT == FMT_WORD ? "k_decode<word>" : FMT == FMT_BYTE ? "k_decode<byte>" : FMT == FMT_BYTEF ? "k_decode<byte, slot records>"
+    if (name)
+        *name = s.word64 ? "k_decode_word64"
+                : FMT == FMT_WORD ? "k_decode<word>" : FMT == FMT_BYTE ? "k_decode<byte>" : FMT == FMT_BYTEF ? "k_decode<byte, slot records>"
                 : FMT == FMT_R64 ? "k_decode<r64>" : FMT == FMT_R64S ? "k_decode<r64 search>"
                 : FMT == FMT_WORD16 ? "k_decode<word, u16 symbols>"
                 : FMT == FMT_BYTEA ? "k_decode<byte, per-chunk models>" : FMT == FMT_WORDA ? "k_decode<word, per-chunk models>" : "k_decode<alias>";
-    RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, p);
-    return hipGetLastError();
+    return with_states_per_lane(s.K, [&](auto k) {
+        constexpr int K = decltype(k)::value;
+        switch (s.out) {
+        case OUT_FAST8: return launch_decode_t<FMT, K, OUT_FAST8, RAGGED>(g, stream, p);
+        case OUT_FAST16: return launch_decode_t<FMT, K, OUT_FAST16, RAGGED>(g, stream, p);
+        default: return launch_decode_t<FMT, K, OUT_SLOW, RAGGED>(g, stream, p);
+        }
+    });
 }
 
-template <int FMT> hipError_t launch_decode_f(const DecParams &p, int num_cus, hipStream_t s, const char **name)
+template <bool RAGGED> hipError_t launch_decode_fmt(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {
-    const bool aligned = ((reinterpret_cast<uintptr_t>(p.out) | (uintptr_t)p.chunk_syms) & 3u) == 0;
-    const bool fast = aligned && p.sym_bytes == 1;
-    if (aligned && p.sym_bytes == 2) {
-        switch (p.n_ways) {
-        case 64: return launch_decode_t<FMT, 1, OUT_FAST16>(p, num_cus, s, name);
-        case 128: return launch_decode_t<FMT, 2, OUT_FAST16>(p, num_cus, s, name);
-        case 256: return launch_decode_t<FMT, 4, OUT_FAST16>(p, num_cus, s, name);
-        default: break;
-        }
+    switch (format) {
+    case FMT_WORD: return launch_decode_f<FMT_WORD, RAGGED>(p, num_cus, stream, name);
+    case FMT_BYTE: return launch_decode_f<FMT_BYTE, RAGGED>(p, num_cus, stream, name);
+    case FMT_BYTEF: return launch_decode_f<FMT_BYTEF, RAGGED>(p, num_cus, stream, name);
+    case FMT_R64: return launch_decode_f<FMT_R64, RAGGED>(p, num_cus, stream, name);
+    case FMT_R64S: return launch_decode_f<FMT_R64S, RAGGED>(p, num_cus, stream, name);
+    case FMT_WORD16: return launch_decode_f<FMT_WORD16, RAGGED>(p, num_cus, stream, name);
+    case FMT_BYTEA: return launch_decode_f<FMT_BYTEA, RAGGED>(p, num_cus, stream, name);
+    case FMT_WORDA: return launch_decode_f<FMT_WORDA, RAGGED>(p, num_cus, stream, name);
+    case FMT_ALIAS: return launch_decode_f<FMT_ALIAS, RAGGED>(p, num_cus, stream, name);
+    default: return hipErrorInvalidValue;
     }
-    // (alternatives that were measured and lost -- compiler-scheduled renormalisation -2 %, output through an LDS tile -7 %,
-    //  per-round byte stores -5 %, groups without the pipelined chunk hand-over, the byte format's byte stores: HISTORY.md,
-    //  profiles/r04_byte_decoder_variants.log -- are no longer in the sources)
-    if constexpr (FMT == FMT_WORD) {
-        if (fast && p.n_ways == 64)
-            return launch_decode_word64(p, num_cus, s, name);
-    }
-    switch (p.n_ways) {
-    case 64:
-        return fast ? launch_decode_t<FMT, 1, OUT_FAST8>(p, num_cus, s, name)
-                    : launch_decode_t<FMT, 1, OUT_SLOW>(p, num_cus, s, name);
-    case 128:
-        return fast ? launch_decode_t<FMT, 2, OUT_FAST8>(p, num_cus, s, name)
-                    : launch_decode_t<FMT, 2, OUT_SLOW>(p, num_cus, s, name);
-    case 256:
-        return fast ? launch_decode_t<FMT, 4, OUT_FAST8>(p, num_cus, s, name)
-                    : launch_decode_t<FMT, 4, OUT_SLOW>(p, num_cus, s, name);
-    case 512:
-        return fast ? launch_decode_t<FMT, 8, OUT_FAST8>(p, num_cus, s, name)
-                    : launch_decode_t<FMT, 8, OUT_SLOW>(p, num_cus, s, name);
-    default:
-        // any other lane count: K = ceil(N / 64) states per lane, the unused tail lanes idle
-        if (p.n_ways >= 1 && p.n_ways < 64)
-            return launch_decode_t<FMT, 1, OUT_SLOW>(p, num_cus, s, name);
-        if (p.n_ways < 128)
-            return launch_decode_t<FMT, 2, OUT_SLOW>(p, num_cus, s, name);
-        if (p.n_ways < 256)
-            return launch_decode_t<FMT, 4, OUT_SLOW>(p, num_cus, s, name);
-        if (p.n_ways < 512)
-            return launch_decode_t<FMT, 8, OUT_SLOW>(p, num_cus, s, name);
-        return hipErrorInvalidValue;
-    }
-}
-
-
-// Ragged batches: the store path is chosen per stream inside the kernel, so the launcher goes by the interleave and the
-// symbol width alone -- full waves get the kernel with the transposed dword stores, every other lane count the general one.
-template <int FMT> hipError_t launch_decode_batch_f(const DecParams &p, int num_cus, hipStream_t s)
-{
-    constexpr bool kHasFast = FMT != FMT_R64S; // (the search decoder exists in its general form only)
-    if constexpr (FMT == FMT_ALIAS) { // (u16 symbols: the paired-round stores for the alias format and, below, the word format)
-        if (p.sym_bytes == 2) {
-            switch (p.n_ways) {
-            case 64: return launch_decode_t<FMT, 1, OUT_FAST16, true>(p, num_cus, s, nullptr);
-            case 128: return launch_decode_t<FMT, 2, OUT_FAST16, true>(p, num_cus, s, nullptr);
-            default: break;
-            }
-        }
-    }
-    if constexpr (FMT == FMT_WORD16) {
-        switch (p.n_ways) {
-        case 64: return launch_decode_t<FMT, 1, OUT_FAST16, true>(p, num_cus, s, nullptr);
-        case 128: return launch_decode_t<FMT, 2, OUT_FAST16, true>(p, num_cus, s, nullptr);
-        default: break;
-        }
-    }
-    const bool fast = kHasFast && p.sym_bytes == 1;
-    if constexpr (kHasFast && FMT != FMT_WORD16) {
-        if (fast) {
-            switch (p.n_ways) {
-            case 64:
-                if constexpr (FMT == FMT_WORD)
-                    return launch_decode_word64<true>(p, num_cus, s, nullptr);
-                else
-                    return launch_decode_t<FMT, 1, OUT_FAST8, true>(p, num_cus, s, nullptr);
-            case 128: return launch_decode_t<FMT, 2, OUT_FAST8, true>(p, num_cus, s, nullptr);
-            case 256: return launch_decode_t<FMT, 4, OUT_FAST8, true>(p, num_cus, s, nullptr);
-            case 512: return launch_decode_t<FMT, 8, OUT_FAST8, true>(p, num_cus, s, nullptr);
-            default: break;
-            }
-        }
-    }
-    if (p.n_ways >= 1 && p.n_ways <= 64)
-        return launch_decode_t<FMT, 1, OUT_SLOW, true>(p, num_cus, s, nullptr);
-    if (p.n_ways <= 128)
-        return launch_decode_t<FMT, 2, OUT_SLOW, true>(p, num_cus, s, nullptr);
-    if (p.n_ways <= 256)
-        return launch_decode_t<FMT, 4, OUT_SLOW, true>(p, num_cus, s, nullptr);
-    if (p.n_ways <= 512)
-        return launch_decode_t<FMT, 8, OUT_SLOW, true>(p, num_cus, s, nullptr);
-    return hipErrorInvalidValue;
 }
 
 } // namespace
@@ -900,16 +798,9 @@ hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus,
                         : format == FMT_R64S  ? "k_decode_batch<r64 search>"
                         : format == FMT_WORD16 ? "k_decode_batch<word, u16 symbols>"
                                               : "k_decode_batch<alias>";
-    switch (format) {
-    case FMT_WORD: return launch_decode_batch_f<FMT_WORD>(p, num_cus, stream);
-    case FMT_BYTE: return launch_decode_batch_f<FMT_BYTE>(p, num_cus, stream);
-    case FMT_BYTEF: return launch_decode_batch_f<FMT_BYTEF>(p, num_cus, stream);
-    case FMT_R64: return launch_decode_batch_f<FMT_R64>(p, num_cus, stream);
-    case FMT_R64S: return launch_decode_batch_f<FMT_R64S>(p, num_cus, stream);
-    case FMT_WORD16: return launch_decode_batch_f<FMT_WORD16>(p, num_cus, stream);
-    case FMT_ALIAS: return launch_decode_batch_f<FMT_ALIAS>(p, num_cus, stream);
-    default: return hipErrorInvalidValue;
-    }
+    if (format == FMT_BYTEA || format == FMT_WORDA) // (one model per stream: launch_decode_batch_models_wave)
+        return hipErrorInvalidValue;
+    return launch_decode_fmt<true>(format, p, num_cus, stream, nullptr);
 }
 
 // ... with one model per stream (rans_amd_decode_batch_adaptive): the uniform adaptive decoder's four-wave workgroups
@@ -921,53 +812,18 @@ hipError_t launch_decode_batch_models_wave(int format, const DecParams &p, int n
     case FMT_WORDA:
         if (models_batch_kernel)
             *models_batch_kernel = "k_decode_batch_models<word>";
-        return launch_decode_batch_f<FMT_WORDA>(p, num_cus, stream);
+        return launch_decode_f<FMT_WORDA, true>(p, num_cus, stream, nullptr);
     case FMT_BYTEA:
         if (models_batch_kernel)
             *models_batch_kernel = "k_decode_batch_models<byte>";
-        return launch_decode_batch_f<FMT_BYTEA>(p, num_cus, stream);
+        return launch_decode_f<FMT_BYTEA, true>(p, num_cus, stream, nullptr);
     default: return hipErrorInvalidValue;
     }
 }
 
 hipError_t launch_decode_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {
-    switch (format) {
-    case FMT_WORD: return launch_decode_f<FMT_WORD>(p, num_cus, stream, name);
-    case FMT_BYTE: return launch_decode_f<FMT_BYTE>(p, num_cus, stream, name);
-    case FMT_BYTEF: return launch_decode_f<FMT_BYTEF>(p, num_cus, stream, name);
-    case FMT_R64: return launch_decode_f<FMT_R64>(p, num_cus, stream, name);
-    case FMT_BYTEA: return launch_decode_f<FMT_BYTEA>(p, num_cus, stream, name);
-    case FMT_WORDA: return launch_decode_f<FMT_WORDA>(p, num_cus, stream, name);
-    case FMT_WORD16: { // u16 symbols: paired-round stores for full waves, element stores otherwise
-        const bool aligned = ((reinterpret_cast<uintptr_t>(p.out) | (uintptr_t)p.chunk_syms * 2u) & 3u) == 0;
-        if (aligned && p.n_ways == 64)
-            return launch_decode_t<FMT_WORD16, 1, OUT_FAST16>(p, num_cus, stream, name);
-        if (aligned && p.n_ways == 128)
-            return launch_decode_t<FMT_WORD16, 2, OUT_FAST16>(p, num_cus, stream, name);
-        if (p.n_ways >= 1 && p.n_ways <= 64)
-            return launch_decode_t<FMT_WORD16, 1, OUT_SLOW>(p, num_cus, stream, name);
-        if (p.n_ways <= 128)
-            return launch_decode_t<FMT_WORD16, 2, OUT_SLOW>(p, num_cus, stream, name);
-        if (p.n_ways <= 256)
-            return launch_decode_t<FMT_WORD16, 4, OUT_SLOW>(p, num_cus, stream, name);
-        if (p.n_ways <= 512)
-            return launch_decode_t<FMT_WORD16, 8, OUT_SLOW>(p, num_cus, stream, name);
-        return hipErrorInvalidValue;
-    }
-    case FMT_R64S: // the search decoder exists in its general form only (any N, element stores)
-        if (p.n_ways >= 1 && p.n_ways <= 64)
-            return launch_decode_t<FMT_R64S, 1, OUT_SLOW>(p, num_cus, stream, name);
-        if (p.n_ways <= 128)
-            return launch_decode_t<FMT_R64S, 2, OUT_SLOW>(p, num_cus, stream, name);
-        if (p.n_ways <= 256)
-            return launch_decode_t<FMT_R64S, 4, OUT_SLOW>(p, num_cus, stream, name);
-        if (p.n_ways <= 512)
-            return launch_decode_t<FMT_R64S, 8, OUT_SLOW>(p, num_cus, stream, name);
-        return hipErrorInvalidValue;
-    case FMT_ALIAS: return launch_decode_f<FMT_ALIAS>(p, num_cus, stream, name);
-    default: return hipErrorInvalidValue;
-    }
+    return launch_decode_fmt<false>(format, p, num_cus, stream, name);
 }
 
 } // namespace rans_amd

@@ -33,13 +33,8 @@ namespace {
 
 #include "encode_common.hpp"
 
-// six waves per SIMD (80 registers), 24 one-wave workgroups per CU (the LDS would allow 25): measured the same from 20 to 25
-// per CU, and with 1, 4 or 8 count loads in flight (profiles/r06_adaptive_encoder.md: the launch is bound by the LDS pipe --
-// one ds_add per symbol on top of the coder's record gather -- not by latency)
-constexpr int kAdaptWavesPerSimd = 6, kAdaptPerCu = 24;
-constexpr uint32_t kAdaptRecBytes = 256u * 16u;                     // the records, at LDS address 0
+// (kAdaptWavesPerSimd, kAdaptPerCu, kAdaptRecBytes -- the records, at LDS address 0 --, kAdaptEncLds, adapt_waves_per_simd: wave_shape.hpp)
 constexpr uint32_t kAdaptWinBase = kAdaptRecBytes;                  // the stream staging window behind them
-constexpr uint32_t kAdaptEncLds = kAdaptRecBytes + kEncStageBytes; // 6 KiB; the counters of step 1 lie over the records
 
 // One sub-step for any lane mask on the FAST records (compiler-scheduled; the rounds in front of the first whole
 // super-group of sixteen, interleaves other than 64, unaligned inputs), units stored straight to memory.
@@ -94,9 +89,6 @@ __device__ __forceinline__ void adapt_substep(uint32_t &x, const u32x4 rec, bool
 // input) and one-symbol word chunks take the two-pass form inside the same kernel.  The word format codes with the round-up
 // reciprocals here whatever the frequencies (exact for every frequency; 3 VALU more than Alverson's, in a launch the LDS pipe
 // bounds): one unrolled loop instead of two.
-// (waves per SIMD by the registers a resident chunk needs -- 64 / 32 / 16 VGPRs of symbols beside ~90 of working set, no spills:
-//  at RR = 16 three spill-free waves beat four that spill 22 registers, 0.874 against 0.984 ms for the word format)
-constexpr int adapt_waves_per_simd(int K, int RR) { return K != 1 ? (K <= 4 ? 4 : 2) : RR >= 16 ? 3 : RR >= 4 ? 4 : kAdaptWavesPerSimd; }
 
 // RAGGED (rans_amd_encode_batch_adaptive): a "chunk" is a stream of the batch -- its symbols are the sym_counts[c] at syms +
 // sym_offsets[c] (caller data: a range that does not lie inside [0, n) is not read, see below), always in the two-pass form;
@@ -567,49 +559,20 @@ __global__ void __launch_bounds__(64, adapt_waves_per_simd(K, RR)) k_encode_adap
         atomicOr(p.flags, 1u);
 }
 
-template <int FMT, int K, int RR, bool RAGGED = false> hipError_t launch_t(const AdaptEncParams &p, int num_cus, hipStream_t stream)
+// wave_shape.hpp says which instance and with what geometry; this turns its answer into the template
+template <int FMT, bool RAGGED> hipError_t launch_f(const AdaptEncParams &p, int num_cus, hipStream_t stream)
 {
-    // workgroups per CU: 6 KiB of LDS each allow 25 (profiles/r06_wg_residency.log), the registers kAdaptPerCu and fewer
-    const uint64_t per_cu = K != 1 ? (K <= 4 ? 16 : 8) : (uint64_t)adapt_waves_per_simd(K, RR) * 4;
-    const uint64_t cap = (uint64_t)num_cus * (per_cu < (uint64_t)kAdaptPerCu ? per_cu : (uint64_t)kAdaptPerCu);
-    const uint32_t grid = (uint32_t)(p.nchunks < cap ? (p.nchunks ? p.nchunks : 1) : cap);
-    RANS_LAUNCH((k_encode_adaptive<FMT, K, RR, RAGGED>), dim3(grid), dim3(64), kAdaptEncLds, stream, p);
-    return hipGetLastError();
-}
-
-template <int FMT> hipError_t launch_f(const AdaptEncParams &p, int num_cus, hipStream_t s)
-{
-    if (p.n_ways == 64 && (reinterpret_cast<uintptr_t>(p.syms) & 3u) == 0 && p.n >= p.chunk_syms) { // register-resident chunks
-        if (p.chunk_syms == 16384u)
-            return launch_t<FMT, 1, 16>(p, num_cus, s);
-        if (p.chunk_syms == 8192u)
-            return launch_t<FMT, 1, 8>(p, num_cus, s);
-        if (p.chunk_syms == 4096u)
-            return launch_t<FMT, 1, 4>(p, num_cus, s);
+    const AdaptShape s = adapt_shape(p.n_ways, (reinterpret_cast<uintptr_t>(p.syms) & 3u) == 0, p.n >= p.chunk_syms, p.chunk_syms, RAGGED);
+    const WaveLaunch g = adapt_launch(s.K, s.RR, p.nchunks, num_cus);
+    if constexpr (!RAGGED) { // register-resident chunks: one state per lane, no ragged form
+        switch (s.RR) {
+        case 16: return launch_wave_kernel<k_encode_adaptive<FMT, 1, 16, false>>(g, 0, stream, p);
+        case 8: return launch_wave_kernel<k_encode_adaptive<FMT, 1, 8, false>>(g, 0, stream, p);
+        case 4: return launch_wave_kernel<k_encode_adaptive<FMT, 1, 4, false>>(g, 0, stream, p);
+        default: break;
+        }
     }
-    if (p.n_ways >= 1 && p.n_ways <= 64)
-        return launch_t<FMT, 1, 0>(p, num_cus, s);
-    if (p.n_ways <= 128)
-        return launch_t<FMT, 2, 0>(p, num_cus, s);
-    if (p.n_ways <= 256)
-        return launch_t<FMT, 4, 0>(p, num_cus, s);
-    if (p.n_ways <= 512)
-        return launch_t<FMT, 8, 0>(p, num_cus, s);
-    return hipErrorInvalidValue;
-}
-
-// ragged batches: the two-pass form for every stream, by the interleave alone
-template <int FMT> hipError_t launch_batch_f(const AdaptEncParams &p, int num_cus, hipStream_t s)
-{
-    if (p.n_ways >= 1 && p.n_ways <= 64)
-        return launch_t<FMT, 1, 0, true>(p, num_cus, s);
-    if (p.n_ways <= 128)
-        return launch_t<FMT, 2, 0, true>(p, num_cus, s);
-    if (p.n_ways <= 256)
-        return launch_t<FMT, 4, 0, true>(p, num_cus, s);
-    if (p.n_ways <= 512)
-        return launch_t<FMT, 8, 0, true>(p, num_cus, s);
-    return hipErrorInvalidValue;
+    return with_states_per_lane(s.K, [&](auto k) { return launch_wave_kernel<k_encode_adaptive<FMT, decltype(k)::value, 0, RAGGED>>(g, 0, stream, p); });
 }
 
 } // namespace
@@ -623,11 +586,11 @@ hipError_t launch_encode_batch_models(int format, const AdaptEncParams &p, int n
     case FMT_WORD:
         if (models_batch_kernel)
             *models_batch_kernel = "k_encode_batch_models<word>";
-        return launch_batch_f<FMT_WORD>(p, num_cus, stream);
+        return launch_f<FMT_WORD, true>(p, num_cus, stream);
     case FMT_BYTE:
         if (models_batch_kernel)
             *models_batch_kernel = "k_encode_batch_models<byte>";
-        return launch_batch_f<FMT_BYTE>(p, num_cus, stream);
+        return launch_f<FMT_BYTE, true>(p, num_cus, stream);
     default: return hipErrorInvalidValue;
     }
 }
@@ -640,8 +603,8 @@ hipError_t launch_encode_adaptive(int format, const AdaptEncParams &p, int num_c
     if (name)
         *name = format == FMT_WORD ? "k_encode_adaptive<word>" : "k_encode_adaptive<byte>";
     switch (format) {
-    case FMT_WORD: return launch_f<FMT_WORD>(p, num_cus, stream);
-    case FMT_BYTE: return launch_f<FMT_BYTE>(p, num_cus, stream);
+    case FMT_WORD: return launch_f<FMT_WORD, false>(p, num_cus, stream);
+    case FMT_BYTE: return launch_f<FMT_BYTE, false>(p, num_cus, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -18,7 +18,7 @@ namespace {
 
 #include "encode_common.hpp"
 
-constexpr int kEncAliasLdsThreads = 1024; // FMT_ALIAS_LDS: 16 waves share the (up to 160 KiB) tables of a CU
+static_assert(sizeof(EncRec) == kEncRecBytes, "wave_shape.hpp sizes the record tables");
 
 // ---------------------------------------------------------------------------
 // Fused placement (EncParams::status).  The container's layout is the oracle's: chunk c starts at the sum of the
@@ -76,10 +76,6 @@ __device__ __forceinline__ void place_and_copy(const EncParams &p, uint64_t chun
             }
     }
 }
-
-// waves per SIMD the fused kernel is compiled for: 8 (64 VGPRs: 4 blocks of 8 waves per CU) with one state per lane, 4 and 2
-// with 2-4 and 8 states per lane -- at 64 VGPRs those spilled 20 to 785 registers (the 512-way rans64 encoder)
-constexpr int enc_fused_waves_per_simd(int K) { return K == 1 ? 8 : (K <= 4 ? 4 : 2); }
 
 // MODE 0: static chunk striding into scratch slots (k_layout + k_compact follow; or, with EncParams::slot_layout, nothing
 //         follows: the slots ARE the container).
@@ -721,115 +717,36 @@ __global__ void __launch_bounds__(FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (
     }
 }
 
-template <int FMT, int K> hipError_t launch_encode_t(const EncParams &p, int num_cus, hipStream_t stream)
+// wave_shape.hpp says which MODE and with what geometry; this turns its answer into the template instance
+template <int FMT> hipError_t launch_encode_t(const EncParams &p, int num_cus, hipStream_t stream)
 {
-    const bool fused = p.status != nullptr;
-    const bool slots = !fused && p.slot_layout && p.claims; // MODE 2: dynamic claims, no copiers
-    const bool ragged = slots && p.slot_offsets;            // MODE 4: ... per-stream symbol ranges and slots
-    const bool sized = slots && p.ovf_ctl;                  // MODE 3: ... slots of the caller's size
-    const bool dynamic = fused || slots;
-    const uint32_t threads = FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (dynamic ? kEncFusedThreads : kEncBlockThreads);
-    const uint32_t waves = threads / 64;
-    const uint32_t enc_waves = fused ? waves - (waves >= 16 ? kEncFusedCopiers16 : 1) : waves;
-    const size_t nrecs = p.nsyms < 256 ? 256 : p.nsyms;
-    size_t lds = FMT == FMT_ALIAS_LDS ? nrecs * 8 + ((size_t)2 << p.scale_bits)
-                 : ((FMT == FMT_BYTE && p.chunk_freqs) || FMT == FMT_WORDA) ? (size_t)waves * kAdaptEncWaveLds
-                                                      : nrecs * sizeof(EncRec) + ((FMT == FMT_WORD || FMT == FMT_BYTE) ? 256 * 16 : 0);
-    if ((FMT == FMT_WORD || (FMT == FMT_BYTE && !p.chunk_freqs)) && K == 1 && p.sym_bytes == 1 && nrecs == 256)
-        lds += (size_t)waves * kEncStageBytes; // stream staging windows (4 + 4 KiB of tables in front)
+    const int K = wave_states_per_lane(p.n_ways);
+    const int mode = encode_mode(p.status != nullptr, p.slot_layout != 0, p.claims != nullptr, p.slot_offsets != nullptr, p.ovf_ctl != nullptr,
+                                 p.sym_offsets && p.sym_counts, FMT == FMT_WORDA);
+    if (!K || mode < 0)
+        return hipErrorInvalidValue;
+    const WaveLaunch g = encode_launch(FMT, K, mode, p.redo != 0, p.nsyms, p.scale_bits, p.sym_bytes, p.chunk_freqs != nullptr,
+                                       p.mailbox_global != nullptr, p.nchunks, num_cus);
+    if (!g.threads || (FMT == FMT_WORD && !p.word_enc_recs && p.sym_bytes == 1) || (FMT == FMT_ALIAS_LDS && (!p.alias_recs8 || !p.alias_remap16)))
+        return hipErrorInvalidValue;
     EncParams q = p;
-    if (fused && !p.mailbox_global) {
-        lds = (lds + 15) & ~(size_t)15;
-        q.mailbox_off = (uint32_t)lds;
-        lds += kEncFusedLdsBytes;
-    }
-    q.stage_off = 0;
-    if (FMT == FMT_ALIAS_LDS && K == 1 && p.sym_bytes == 1) { // windows of the coding waves, where there is room
-        const size_t at = (lds + 15) & ~(size_t)15;
-        if (at + (size_t)enc_waves * kEncStageBytes <= 160 * 1024) {
-            q.stage_off = (uint32_t)at;
-            lds = at + (size_t)enc_waves * kEncStageBytes;
+    if (mode == 1 && !p.mailbox_global)
+        q.mailbox_off = g.mailbox_off;
+    q.stage_off = g.stage_off;
+    return with_states_per_lane(K, [&](auto k) {
+        constexpr int K_ = decltype(k)::value;
+        if constexpr (FMT != FMT_WORDA) { // (per-chunk word models: MODE 0 only, encode_mode)
+            switch (mode) {
+            case 1: return launch_wave_kernel<k_encode<FMT, K_, 1>>(g, encode_lds_cap(FMT), stream, q);
+            case 2: return launch_wave_kernel<k_encode<FMT, K_, 2>>(g, encode_lds_cap(FMT), stream, q);
+            case 3: return launch_wave_kernel<k_encode<FMT, K_, 3>>(g, encode_lds_cap(FMT), stream, q);
+            case 4: return launch_wave_kernel<k_encode<FMT, K_, 4>>(g, encode_lds_cap(FMT), stream, q);
+            default: break;
+            }
         }
-    }
-    const size_t lds_cap = FMT == FMT_ALIAS_LDS ? 160 * 1024 : 128 * 1024;
-    if (lds > lds_cap || (FMT == FMT_WORD && !p.word_enc_recs && p.sym_bytes == 1) ||
-        (FMT == FMT_ALIAS_LDS && (!p.alias_recs8 || !p.alias_remap16)))
-        return hipErrorInvalidValue;
-    uint64_t want = (p.nchunks + enc_waves - 1) / enc_waves;
-    // blocks per CU: what the LDS allows, within the 32 resident waves of a CU
-    uint64_t per_cu = lds ? (160 * 1024) / lds : 8;
-    per_cu = per_cu < 1 ? 1 : per_cu;
-    per_cu = per_cu * waves > 32 ? 32 / waves : per_cu;
-    if (dynamic && FMT != FMT_ALIAS_LDS) { // ... and within the waves per SIMD the kernel's register budget was chosen for
-        const uint64_t fit = (uint64_t)enc_fused_waves_per_simd(K) * 4 / waves;
-        per_cu = per_cu > fit ? (fit ? fit : 1) : per_cu;
-    }
-    uint64_t cap = (uint64_t)num_cus * (FMT == FMT_ALIAS_LDS || dynamic ? per_cu : 8);
-    if (sized && p.redo) // (a handful of chunks at most, usually none: one block per CU finds that out quickly)
-        cap = (uint64_t)num_cus;
-    const uint32_t grid = (uint32_t)(want < cap ? (want ? want : 1) : cap);
-    if constexpr (FMT != FMT_WORDA) { // (per-chunk word models: the scratch-slot mode only, as rans_amd_encode_adaptive launches it)
-    if (fused) {
-        auto kern = k_encode<FMT, K, 1>;
-        static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), (int)lds_cap, lds_ok); e != hipSuccess)
-            return e;
-        RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, q);
-        return hipGetLastError();
-    }
-    if (ragged) {
-        if (!p.sym_offsets || !p.sym_counts || p.ovf_ctl)
-            return hipErrorInvalidValue;
-        auto kern = k_encode<FMT, K, 4>;
-        static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), (int)lds_cap, lds_ok); e != hipSuccess)
-            return e;
-        RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, q);
-        return hipGetLastError();
-    }
-    if (sized) {
-        auto kern = k_encode<FMT, K, 3>;
-        static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), (int)lds_cap, lds_ok); e != hipSuccess)
-            return e;
-        RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, q);
-        return hipGetLastError();
-    }
-    if (slots) {
-        auto kern = k_encode<FMT, K, 2>;
-        static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
-        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), (int)lds_cap, lds_ok); e != hipSuccess)
-            return e;
-        RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, q);
-        return hipGetLastError();
-    }
-    } else if (fused || slots) {
-        return hipErrorInvalidValue;
-    }
-    if (p.slot_offsets) // (a ragged request that did not reach MODE 4)
-        return hipErrorInvalidValue;
-    auto kern = k_encode<FMT, K, 0>;
-    static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), (int)lds_cap, lds_ok); e != hipSuccess)
-        return e;
-    RANS_LAUNCH(kern, dim3(grid), dim3(threads), lds, stream, q);
-    return hipGetLastError();
+        return launch_wave_kernel<k_encode<FMT, K_, 0>>(g, encode_lds_cap(FMT), stream, q);
+    });
 }
-
-template <int FMT> hipError_t launch_encode_f(const EncParams &p, int num_cus, hipStream_t s)
-{
-    // K = ceil(N / 64) states per lane; lane counts that are not a multiple of 64 leave lanes idle
-    if (p.n_ways >= 1 && p.n_ways <= 64)
-        return launch_encode_t<FMT, 1>(p, num_cus, s);
-    if (p.n_ways <= 128)
-        return launch_encode_t<FMT, 2>(p, num_cus, s);
-    if (p.n_ways <= 256)
-        return launch_encode_t<FMT, 4>(p, num_cus, s);
-    if (p.n_ways <= 512)
-        return launch_encode_t<FMT, 8>(p, num_cus, s);
-    return hipErrorInvalidValue;
-}
-
 
 } // namespace
 
@@ -843,12 +760,12 @@ hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipSt
                 : format == FMT_R64S  ? "k_encode<r64 full-width>"
                                       : "k_encode<alias, LDS remap>";
     switch (format) {
-    case FMT_WORD: return launch_encode_f<FMT_WORD>(p, num_cus, stream);
-    case FMT_WORDA: return p.chunk_freqs ? launch_encode_f<FMT_WORDA>(p, num_cus, stream) : hipErrorInvalidValue;
-    case FMT_BYTE: return launch_encode_f<FMT_BYTE>(p, num_cus, stream);
-    case FMT_R64: return launch_encode_f<FMT_R64>(p, num_cus, stream);
-    case FMT_R64S: return launch_encode_f<FMT_R64S>(p, num_cus, stream);
-    case FMT_ALIAS_LDS: return launch_encode_f<FMT_ALIAS_LDS>(p, num_cus, stream);
+    case FMT_WORD: return launch_encode_t<FMT_WORD>(p, num_cus, stream);
+    case FMT_WORDA: return p.chunk_freqs ? launch_encode_t<FMT_WORDA>(p, num_cus, stream) : hipErrorInvalidValue;
+    case FMT_BYTE: return launch_encode_t<FMT_BYTE>(p, num_cus, stream);
+    case FMT_R64: return launch_encode_t<FMT_R64>(p, num_cus, stream);
+    case FMT_R64S: return launch_encode_t<FMT_R64S>(p, num_cus, stream);
+    case FMT_ALIAS_LDS: return launch_encode_t<FMT_ALIAS_LDS>(p, num_cus, stream);
     // (FMT_ALIAS, alias_remap gathered from global memory: retired in round 6 -- every alias model the library can create has
     //  its encoder tables in LDS form, model.cpp; the lane encoders keep their own gather for narrow interleaves)
     default: return hipErrorInvalidValue;

@@ -8,6 +8,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "wave_shape.hpp" // block sizes, LDS windows and the shapes of the wave-per-chunk launches (host-only)
+
 namespace rans_amd {
 
 // Measurement knobs.  The shipped library reads NO environment variable: every A/B switch and every knob that changes
@@ -28,41 +30,33 @@ constexpr uint32_t kVarNoDual = 8u;        // alias decoders: always one chunk p
 constexpr uint32_t kVarDualAlways = 16u;   // ... two chunks per wave (k_decode_dual) whenever the tables fit, not only when
                                            //     they leave no room for a second block per CU
 
-// Per-wave LDS stream window (see decode_wave.hip "stream window").
-constexpr uint32_t kRingBytes = 2048;   // two 1 KiB blocks
-constexpr uint32_t kRingBlock = 1024;   // 64 lanes x 16 B
-constexpr uint32_t kRingMirror = 768;   // copy of ring[0..768) after the end: no wrap between checkpoints
-constexpr uint32_t kRingStride = kRingBytes + kRingMirror;
-
-constexpr int kDecBlockThreads = 1024; // 16 waves share one table image
 constexpr uint32_t kWorkPools = 8;       // chunk hand-out counters per launch (one per XCD)
 constexpr uint32_t kWorkPoolStride = 16; // in uint32: every counter on its own 64-byte line
 constexpr uint32_t kWorkSlots = 64;      // launches that may reuse the counter ring before wrap
 constexpr uint32_t kCaptureSlots = 8;    // counter slots behind the ring for launches captured into a hipGraph (api.cpp)
 // one ring slot = kWorkPools counters (a 64-byte line each) + one line for the launch's wave span record
 constexpr uint32_t kWorkSlotWords = (kWorkPools + 1) * kWorkPoolStride;
-constexpr int kEncBlockThreads = 256;
 // Kernel-side format number of rans64 with a binary search over the cumulative frequencies instead of the cum2sym
-// table (scale_bits 1..6 and 17..31; device_common.hpp FMT_R64S).  launch_decode / launch_encode take it in place
+// table (scale_bits 1..6 and 17..31; kernel_formats.hpp FMT_R64S).  launch_decode / launch_encode take it in place
 // of RANS_AMD_FMT_R64; DecParams::table0 is then the cum table padded with ~0 to 2^log2nsyms words.
 constexpr int kKernelFormatR64Search = 4;
-// Kernel-side format number of the alias ENCODER with alias_remap in LDS (device_common.hpp FMT_ALIAS_LDS);
+// Kernel-side format number of the alias ENCODER with alias_remap in LDS (kernel_formats.hpp FMT_ALIAS_LDS);
 // EncParams::alias_recs8 / alias_remap16 are then set.
 constexpr int kKernelFormatAliasLds = 5;
-// Kernel-side format number of the word-format DECODER over more than 256 symbols (device_common.hpp FMT_WORD16):
+// Kernel-side format number of the word-format DECODER over more than 256 symbols (kernel_formats.hpp FMT_WORD16):
 // DecParams::table0 holds {freq, bias | sym << 16} per slot, symbols are u16.
 constexpr int kKernelFormatWord16 = 6;
-// Kernel-side format number of the byte-format DECODER with one model per chunk (device_common.hpp FMT_BYTEA):
+// Kernel-side format number of the byte-format DECODER with one model per chunk (kernel_formats.hpp FMT_BYTEA):
 // DecParams::chunk_freqs holds u16[256] per chunk; no table0/table1.
 constexpr int kKernelFormatByteAdaptive = 7;
-// Kernel-side format numbers of the two-chunks-per-wave alias DECODER (device_common.hpp FMT_ALIAS2 / FMT_ALIAS2W):
+// Kernel-side format numbers of the two-chunks-per-wave alias DECODER (kernel_formats.hpp FMT_ALIAS2 / FMT_ALIAS2W):
 // DecParams::table0 = {sym | (M - freq) << 16, adjust} per half bucket, table1 = own-slot count per bucket (u8 / u16).
 constexpr int kKernelFormatAlias2 = 8;
 constexpr int kKernelFormatAlias2W = 9;
-// Kernel-side format number of the byte-format DECODER with one fused 8-byte record per slot (device_common.hpp FMT_BYTEF):
+// Kernel-side format number of the byte-format DECODER with one fused 8-byte record per slot (kernel_formats.hpp FMT_BYTEF):
 // DecParams::table0 = {freq | sym << 24, slot - start}[1 << scale_bits], no table1.
 constexpr int kKernelFormatByteFused = 11;
-// Kernel-side format number of the WORD format with one model per chunk (device_common.hpp FMT_WORDA), decoder and encoder:
+// Kernel-side format number of the WORD format with one model per chunk (kernel_formats.hpp FMT_WORDA), decoder and encoder:
 // DecParams / EncParams::chunk_freqs holds u16[256] per chunk, scale_bits is 12.
 constexpr int kKernelFormatWordAdaptive = 12;
 constexpr uint32_t kTraceWords = 5;      // per-wave record of DecParams::trace
@@ -179,16 +173,6 @@ struct EncParams {
     const uint32_t *sym_counts;
     const uint64_t *slot_offsets; // [nchunks + 1], multiples of 16
 };
-constexpr uint32_t kEncFusedThreads = 512; // 7 encoder waves + 1 copier wave; 4 blocks per CU
-constexpr uint32_t kEncFusedCopiers16 = 2; // copier waves of a 16-wave block
-constexpr uint32_t kEncMailboxBytes = 16 + 64 * 8;
-// Wave-per-chunk encoders, fused placement: behind the mailbox, one "drained" counter per coding wave of the block (the
-// scratch ring protocol, EncParams::ring_slots)
-constexpr uint32_t kEncDrainBytes = 64;
-constexpr uint32_t kEncFusedLdsBytes = kEncMailboxBytes + kEncDrainBytes;
-// word encoder, one state per lane: the emitted words of sixteen rounds are staged in a window of LDS per wave
-// (encode_wave.hip, enc_word_full_staged); the windows follow the 8 KiB of record tables
-constexpr uint32_t kEncStageBytes = 2048;
 constexpr uint32_t kEncMailboxStride = 640; // a block's mailbox in global memory (EncParams::mailbox_global): whole 128-byte lines
 // Scratch ring of the fused wave encoders: every coding wave owns kEncRingSlots worst-case slots and codes its chunks
 // into them in turn (a slot is reused once the block's copier has moved its previous occupant to the container), so the

@@ -13,6 +13,7 @@
     } while (0)
 
 #include <atomic>
+#include <type_traits>
 
 namespace rans_amd {
 
@@ -31,6 +32,30 @@ inline hipError_t allow_large_lds(const void *kernel, int bytes, std::atomic<uin
     if (e == hipSuccess)
         done.fetch_or(bit, std::memory_order_release);
     return e;
+}
+
+// The launch tail of the wave-per-chunk kernels, one instantiation per kernel: raise its dynamic-LDS limit to lds_cap (0: the
+// kernel stays within the default), launch it with the geometry wave_shape.hpp worked out, report this launch's status.
+template <auto KERN, class Params> hipError_t launch_wave_kernel(const WaveLaunch &g, uint64_t lds_cap, hipStream_t stream, const Params &p)
+{
+    static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
+    if (lds_cap)
+        if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(KERN), (int)lds_cap, lds_ok); e != hipSuccess)
+            return e;
+    RANS_LAUNCH(KERN, dim3(g.grid), dim3(g.threads), (size_t)g.lds, stream, p);
+    return hipGetLastError();
+}
+
+// wave_states_per_lane's K as a template argument: f(std::integral_constant<int, K>)
+template <class F> hipError_t with_states_per_lane(int K, F &&f)
+{
+    switch (K) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return hipErrorInvalidValue;
+    }
 }
 
 // wave-per-chunk kernels (N-way streams with N = 64 K lanes): decode_wave.hip, encode_wave.hip

@@ -152,7 +152,7 @@ struct HostModel {
     // {freq | start << 16, floor(2^32 / freq)} per symbol (zero records up to 256) and alias_remap as u16
     std::vector<uint64_t> alias_recs8;
     std::vector<uint16_t> alias_remap16;
-    // FMT_ALIAS, decoder tables of the two-chunks-per-wave kernel (device_common.hpp FMT_ALIAS2): per half bucket
+    // FMT_ALIAS, decoder tables of the two-chunks-per-wave kernel (kernel_formats.hpp FMT_ALIAS2): per half bucket
     // {sym | (M - freq) << 16, adjust}; per bucket the number of slots its own symbol keeps -- divider[b] - b * tgt,
     // main_alias.cpp:209 -- as u8 (tgt <= 255) or, alias2_wide, as u16.  Empty when the model cannot take that
     // form (a single bucket, or a 65536-wide symbol).
