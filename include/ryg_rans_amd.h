@@ -158,9 +158,14 @@ enum rans_amd_option {
     RANS_AMD_OPT_DUAL_DECODE = 3,          /* 64-way alias decoders: 1 = two chunks per wavefront for the models whose tables
                                               leave room for one block per CU only (default), 0 = always one chunk per
                                               wavefront, 2 = two chunks per wavefront whenever the tables fit */
-    RANS_AMD_OPT_ENC_SCRATCH_RING = 4      /* 1 = the fused wave encoders code into a ring of scratch slots per coding
+    RANS_AMD_OPT_ENC_SCRATCH_RING = 4,     /* 1 = the fused wave encoders code into a ring of scratch slots per coding
                                               wave, reused once drained (half the workspace of a large encode, 2-4 %
                                               slower); default 0: one scratch slot per chunk */
+    RANS_AMD_OPT_BATCH_GROUPS = 5          /* 1 = rans_amd_decode_batch decodes EIGHT streams per wavefront where the batch
+                                              is the reference's 8-way word layout (word format, u8 symbols, n_ways 8,
+                                              scale_bits 12, at least eight streams): k_decode_batch_word_groups; every
+                                              other shape takes the wave-per-stream kernels as before.  Default 0: one
+                                              stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
 };
 int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value);
 
@@ -361,8 +366,14 @@ int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, u
  *
  * beside the stream index (d_offsets[c], d_lengths[c]) every decoder already takes.  One wavefront codes one stream,
  * whatever the interleave: n_ways is anything rans_amd_ways_supported accepts (word 8-way, byte 2-way, rans64 2-way and
- * alias streams of the reference included -- narrow interleaves leave lanes idle, but across the whole GPU; kernels that
- * pack several ragged streams into a wave are later work).  A stream of 0 symbols is the n_ways flushed initial states.
+ * alias streams of the reference included -- narrow interleaves leave lanes idle, but across the whole GPU).  One shape
+ * can pack eight streams into a wavefront, one state per lane: the 8-way word layout main_simd.cpp writes (word format,
+ * u8 symbols, n_ways 8, scale_bits 12) in a batch of at least eight streams, decoded by rans_amd_decode_batch on a context
+ * with rans_amd_ctx_set_option(ctx, RANS_AMD_OPT_BATCH_GROUPS, 1).  A wavefront then lasts as long as the longest of its
+ * eight streams: pass the d_order of rans_amd_batch_order, which puts streams of one length bucket next to each other, and
+ * lay the symbols out with sym_align = 4 (a stream whose output is not 4-byte aligned is decoded a round at a time).  The
+ * encoder and every other interleave stay one stream per wavefront; ragged forms of their group and lane kernels are later
+ * work.  A stream of 0 symbols is the n_ways flushed initial states.
  * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
  * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).
  *

@@ -634,6 +634,11 @@ int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value)
         ctx->variant &= ~(kVarNoDual | kVarDualAlways);
         ctx->variant |= value == 0 ? kVarNoDual : value == 2 ? kVarDualAlways : 0u;
         return RANS_AMD_OK;
+    case RANS_AMD_OPT_BATCH_GROUPS:
+        if (value != 0 && value != 1)
+            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_GROUPS takes 0 (one stream per wave) or 1 (eight 8-way word streams per wave)");
+        ctx->variant = value ? (ctx->variant | kVarBatchGroups) : (ctx->variant & ~kVarBatchGroups);
+        return RANS_AMD_OK;
     default:
         return fail(RANS_AMD_E_ARG, "set_option: unknown option");
     }

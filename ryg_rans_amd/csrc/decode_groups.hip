@@ -22,7 +22,8 @@
 //     one dword per lane every four rounds, 0.51 with whole lines).
 // Chunks of a multiple of 4 symbols -- the output is stored in dwords -- (the launcher hands everything else to the lane
 // kernel); a ragged last chunk sends the input's last octet one round at a time; what a chunk size off 128 leaves goes four rounds, then one round
-// at a time.  The mirror image, the 8-way encoder: encode_groups.hip.
+// at a time.  The mirror image, the 8-way encoder: encode_groups.hip.  The ragged form for rans_amd_decode_batch -- eight
+// STREAMS per wave, each with its own symbol count -- is k_decode_batch_word_groups, behind the uniform kernel.
 //
 // No MFMA: integer, table-driven, serial per state.
 
@@ -37,6 +38,7 @@ constexpr uint32_t kGrpRing = 2 * kGrpBlock;    // per group
 constexpr uint32_t kGrpWaveLds = 8 * kGrpRing;  // per wave
 constexpr uint32_t kGrpThreads = 1024;
 constexpr uint32_t kGrpClaimSyms = 8192;        // symbols one claim of the work counter covers, at least
+typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes on the 4-byte grid (the ragged kernel's lines)
 
 __device__ __forceinline__ uint32_t lds_u16(uint32_t addr)
 {
@@ -379,6 +381,247 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
     }
     if (nbad)
         atomicAdd(p.err_count, (unsigned long long)nbad);
+}
+
+// ---------------------------------------------------------------------------
+// k_decode_batch_word_groups -- the ragged form of k_decode_word_groups (rans_amd_decode_batch under
+// RANS_AMD_OPT_BATCH_GROUPS): a wave's eight groups hold eight STREAMS, each with its own symbol count and its own output
+// address.  The unit of work is one octet of the hand-out order: lane 8 g + i holds state i of the stream at position
+// 8 o + g -- stream order[8 o + g], or 8 o + g without an order; a position at or past nchunks has no stream.  The rounds,
+// the ring and its refills, the transposes and the half-group exchange are k_decode_word_groups'; what is new is that the
+// groups' loop counts differ:
+//   * the wave runs the 16-round sequence max_g(blocks_g) times with FULL exec, blocks_g = count_g >> 7 whole 128-byte
+//     lines.  The sequence sets exec = -1 itself, and the DPP moves of the exchange read zeros from lanes an exec mask has
+//     switched off, so a group that has run out of lines cannot be masked off: it is PARKED.  Its bits of the ballot are
+//     zeroed (gm_lo = gm_hi = 0): its cursor then stands still, checkpoint() never fires for it, and its ring, pend, ld,
+//     left, wr and thr stay as they are; its state is put back from a copy behind every block (one select); its line is
+//     not stored.
+//     A parked group keeps running the rounds on whatever its state becomes, and that is safe: a round reads the slot
+//     table at 8 (x & 4095), inside the 32 KiB table whatever x is, and the ring at (position & 255) | ring, inside the
+//     group's own 256 bytes whatever the position is; it reads no global memory (refills are checkpoint()'s) and writes
+//     nothing but its own registers.  The same holds for a group without a stream or with a rejected one, which is parked
+//     from the start and whose ring is never filled from memory.
+//   * behind the common loop every group decodes its count_g & 127 remaining symbols one round at a time, lanes without a
+//     symbol sitting out, a byte store per lane (the uniform kernel's path for a ragged last chunk).
+// Every lane addresses its output in 64 bits (out_syms is 64-bit, and the eight streams of a wave may lie anywhere in it).
+// A stream whose output is not 4-byte aligned takes the round-by-round path for all of its symbols (blocks_g = 0): the
+// rule of the wave kernels -- sym_align = 4 is the fast layout, anything else is correct and slower.
+// Index entries are the caller's data and checked as k_decode's RAGGED form and the kernel above check theirs: the order
+// entry names a stream, the offset is even, the stream holds its eight states and lies inside the container, the symbol
+// range lies inside [0, out_syms).  A stream that fails is counted once; nothing of it is fetched, nothing stored.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_word_groups(const DecParams p)
+{
+    using Tr = FmtTraits<FMT_WORD>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const unsigned long long t_start = p.span ? wall_clock64() : 0ull;
+    const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // WordSlot[4096]: 32 KiB, a multiple of the ring size
+    {
+        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.table0);
+        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
+        for (uint32_t i = threadIdx.x; i < t0_bytes / 16u; i += blockDim.x)
+            l0[i] = g0[i];
+    }
+    __syncthreads();
+    DecTables<FMT_WORD> T;
+    T.init(smem, smem + t0_bytes, p.scale_bits, p.log2nsyms);
+    if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never decode on a wrong assumption
+        if (threadIdx.x == 0)
+            atomicAdd(p.err_count, 1ull << 32);
+        return;
+    }
+    if (p.work_counter_reset && blockIdx.x == 0 && threadIdx.x < kWorkPools)
+        p.work_counter_reset[threadIdx.x * kWorkPoolStride] = 0u;
+    if (p.span_reset && blockIdx.x == 0 && threadIdx.x < 2)
+        p.span_reset[threadIdx.x] = 0ull;
+
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t g = lane >> 3, i = lane & 7u;
+    const uint32_t ring = t0_bytes + wave * kGrpWaveLds + g * kGrpRing; // (as in k_decode_word_groups, the bias as well)
+    const uint32_t bias = 16u * g;
+    uint32_t gm_lo = g < 4 ? 0xffu << (8u * g) : 0u, gm_hi = g >= 4 ? 0xffu << (8u * (g - 4u)) : 0u;
+    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_lo));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_hi));
+    uint32_t k255 = 255u, k65536 = 0x10000u;
+    uint32_t sel_a = 0x03020703u, sel_b = 0x03070100u, sel_c = 0x07020100u;
+    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_a));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_b));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_c));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(k255));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(k65536));
+
+    const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
+    const uint64_t glo = cbase & ~uint64_t(15), glimit = (cbase + p.container_bytes + 15u) & ~uint64_t(15);
+    const uint32_t sel1 = (lane & 1u) ? 0x03070105u : 0x06020400u;
+    const uint32_t sel2 = (lane & 2u) ? 0x03020706u : 0x05040100u;
+    const uint64_t octets = (p.nchunks + 7u) >> 3; // one per claim (the last one may hold fewer than eight streams)
+
+    auto load16 = [&](uint64_t a) -> u32x4 { // 16 bytes of the container, zeros beyond its granules
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (a >= glo && a < glimit)
+            v = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(a));
+        return v;
+    };
+    auto wave_max = [&](uint32_t v) -> uint32_t { // over the eight groups (v is the same in a group's lanes)
+        uint32_t m = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t t = __builtin_amdgcn_readlane(v, 8 * k);
+            m = t > m ? t : m;
+        }
+        return m;
+    };
+
+    uint32_t nbad = 0;
+    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
+    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
+    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
+    const uint32_t pool = blockIdx.x % npools;
+    for (;;) {
+        uint64_t octet; // (handed out as in k_decode_word_groups: the pooled counter, or a static stride without one)
+        if (p.work_counter) {
+            uint32_t got = 0;
+            if (lane == 0)
+                got = atomicAdd(p.work_counter + pool * kWorkPoolStride, 1u);
+            octet = (uint64_t)uniform(got) * npools + pool;
+        } else {
+            octet = uniform64(claim_v);
+            claim_v += total_waves;
+        }
+        if (octet >= octets)
+            break;
+        // ---- this group's stream: its index entries, all of them the caller's data
+        const uint64_t pos = octet * 8u + g;
+        const bool exists = pos < p.nchunks;
+        uint64_t s = pos;
+        if (exists && p.order)
+            s = p.order[pos];
+        bool valid = exists && s < p.nchunks;
+        uint64_t off = 0, first = 0;
+        uint32_t len = 0, count = 0;
+        if (valid) {
+            off = p.offsets[s];
+            len = p.lengths[s];
+            first = p.sym_offsets[s];
+            count = p.sym_counts[s];
+        }
+        valid = valid && (off & 1u) == 0 && len >= 8u * 4u && off <= p.container_bytes && len <= p.container_bytes - off &&
+                first <= p.out_syms && count <= p.out_syms - first;
+        if (exists && !valid && i == 0)
+            nbad++;
+        const uint64_t src = cbase + (valid ? off : 0u);
+        uint32_t x = Tr::kL;
+        if (valid) // RansDecInit order: state 0 first (rans_word_sse41.h:104-113)
+            x = reinterpret_cast<const uint32_t RANS_GLOBAL *>(src)[i];
+        // the ring, its positions and its refills: k_decode_word_groups' (a group without a valid stream fetches nothing)
+        const uint64_t abase = src & ~uint64_t(kGrpBlock - 1u);
+        const uint32_t start = (uint32_t)(src - abase) + 8u * 4u; // < 160
+        uint32_t curw = (start + bias) >> 1;
+        uint64_t ld = abase + 16u * i;
+        u32x4 b0 = {0u, 0u, 0u, 0u}, b1 = b0, pend = b0;
+        if (valid) {
+            b0 = load16(ld);
+            b1 = load16(ld + kGrpBlock);
+            pend = load16(ld + 2u * kGrpBlock);
+        }
+        ld += 3u * kGrpBlock;
+        uint32_t left = 0;
+        if (valid && ld < glimit) {
+            const uint64_t pieces = (glimit - ld + (kGrpBlock - 1u)) / kGrpBlock;
+            left = pieces < 0x7fffffffu ? (uint32_t)pieces : 0x7fffffffu;
+        }
+        *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)(ring | ((16u * i + bias) & 255u))) = b0;
+        *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)(ring | ((kGrpBlock + 16u * i + bias) & 255u))) = b1;
+        uint32_t wr = ring | ((16u * i + bias) & 255u);
+        uint32_t thr = (kGrpBlock + bias) >> 1;
+        auto checkpoint = [&]() {
+            if (curw >= thr) { // (the same for the eight lanes of a group; never true for a parked group: its cursor stands still)
+                *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)wr) = pend;
+                wr ^= kGrpBlock;
+                thr += kGrpBlock / 2u;
+                if (left) {
+                    pend = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(ld));
+                    left--;
+                }
+                ld += kGrpBlock;
+            }
+        };
+        checkpoint(); // the states may end in block 1
+        const uint32_t end2 = len + bias + (start - 8u * 4u); // twice the (biased) cursor at the end of the stream
+
+        // ---- the group's own counts: whole lines through the common loop, the rest a round at a time
+        const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + first; // (valid: [dst, dst + count) lies inside the output)
+        const uint32_t blocks = (valid && (dst & 3u) == 0) ? count >> 7 : 0u;
+        const uint32_t tail = valid ? count - (blocks << 7) : 0u;
+        const uint32_t max_blocks = wave_max(blocks), max_tail = wave_max(tail);
+        uint64_t line = dst + 16u * i; // this lane's 16 bytes of the group's next line
+        uint32_t m_lo = gm_lo, m_hi = gm_hi;
+        for (uint32_t q = 0; q < max_blocks; ++q) {
+            const bool run = q < blocks;
+            if (!run) // parked: no bit of the ballot is this group's
+                m_lo = m_hi = 0u;
+            const uint32_t x_keep = x;
+            uint32_t a0, a1, a2, a3;
+            decode_octet_8rounds(x, curw, a0, a1, T.mask12v, k65536, m_lo, m_hi, k255, ring, sel_a, sel_b, sel_c);
+            checkpoint();
+            decode_octet_8rounds(x, curw, a2, a3, T.mask12v, k65536, m_lo, m_hi, k255, ring, sel_a, sel_b, sel_c);
+            checkpoint();
+            a0 = quad_transpose(a0, sel1, sel2);
+            a1 = quad_transpose(a1, sel1, sel2);
+            a2 = quad_transpose(a2, sel1, sel2);
+            a3 = quad_transpose(a3, sel1, sel2);
+            u32x4 v; // (the half-group exchange of k_decode_word_groups, under full exec: see there)
+            asm volatile("s_nop 1\n\t"
+                         "s_mov_b64 vcc, %[lower]\n\t"
+                         "v_cndmask_b32_dpp %[vx], %[a2], %[a0], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                         "v_cndmask_b32_dpp %[vz], %[a3], %[a1], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                         "s_mov_b64 vcc, %[upper]\n\t"
+                         "v_cndmask_b32_dpp %[vy], %[a0], %[a2], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                         "v_cndmask_b32_dpp %[vw], %[a1], %[a3], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                         : [vx] "=&v"(v.x), [vy] "=&v"(v.y), [vz] "=&v"(v.z), [vw] "=&v"(v.w)
+                         : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [lower] "s"(0x0f0f0f0f0f0f0f0full),
+                           [upper] "s"(0xf0f0f0f0f0f0f0f0ull)
+                         : "vcc");
+            // (plain stores: a stream starts anywhere on the 4-byte grid, so its lines straddle the memory's -- the case in which
+            //  k_decode_word_groups leaves it to L2 to put the pieces together)
+            if (run) {
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line) = v;
+                line += kGrpBlock;
+            }
+            x = run ? x : x_keep;
+        }
+        // ---- count & 127 symbols (all of them where the output is not 4-byte aligned): one round at a time
+        const uint64_t tail_dst = line - 16u * i; // (`line` has moved on by the group's own blocks, no further)
+        const uint32_t tail_rounds = (uint32_t)(((uint64_t)max_tail + 7u) >> 3);
+        for (uint32_t rr = 0; rr < tail_rounds; ++rr) {
+            if ((rr & 7u) == 0)
+                checkpoint();
+            const uint32_t r0 = rr << 3; // < max_tail
+            const bool active = r0 < tail && i < tail - r0;
+            uint32_t raw = 0;
+            if (active)
+                raw = dec_step<FMT_WORD>(T, x);
+            const bool need = active && x < k65536;
+            const uint64_t m = __builtin_amdgcn_ballot_w64(need);
+            const uint32_t t_lo = (uint32_t)m & gm_lo, t_hi = (uint32_t)(m >> 32) & gm_hi;
+            const uint32_t at = __builtin_amdgcn_mbcnt_hi(t_hi, __builtin_amdgcn_mbcnt_lo(t_lo, curw));
+            curw += __builtin_popcount(t_lo) + __builtin_popcount(t_hi);
+            if (need)
+                x = (x << 16) | lds_u16(((at << 1) & k255) | ring);
+            if (active)
+                *reinterpret_cast<uint8_t RANS_GLOBAL *>(tail_dst + r0 + i) = (uint8_t)(raw >> 24);
+        }
+        // integrity: every state back at L, the cursor exactly at the end of the stream
+        const bool bad = valid && (x != Tr::kL || 2u * curw != end2);
+        const uint64_t bm = __builtin_amdgcn_ballot_w64(bad);
+        if (i == 0 && ((bm >> (8u * g)) & 0xffu) != 0)
+            nbad++;
+    }
+    if (nbad)
+        atomicAdd(p.err_count, (unsigned long long)nbad);
+    record_span(p, t_start, smem);
 }
 
 // ---------------------------------------------------------------------------
@@ -791,6 +1034,32 @@ hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_
     const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
     if (name)
         *name = "k_decode_word_groups";
+    RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
+    return hipGetLastError();
+}
+
+// The ragged form: word format over u8 symbols (the caller has checked the format: the u16 kernel format is another one),
+// from eight streams on; any symbol count, any output address.
+bool decode_batch_word_groups_applicable(const DecParams &p)
+{
+    return p.n_ways == 8 && p.sym_bytes == 1 && p.scale_bits == 12 && p.nchunks >= 8 && p.sym_offsets && p.sym_counts && !p.trace &&
+           ((p.table0_bytes + 15u) & ~15u) % kGrpRing == 0;
+}
+
+hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **group_batch_kernel)
+{
+    const size_t table_lds = (p.table0_bytes + 15u) & ~15u;
+    const size_t lds = table_lds + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
+    auto kern = k_decode_batch_word_groups;
+    static std::atomic<uint64_t> lds_ok{0};
+    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
+        return e;
+    const uint32_t per_cu = 2u * lds <= 160u * 1024u ? 2u : 1u;
+    const uint64_t want_blocks = ((p.nchunks + 7u) / 8u + kGrpThreads / 64 - 1) / (kGrpThreads / 64); // one octet per wave
+    const uint64_t cap = (uint64_t)num_cus * per_cu;
+    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
+    if (group_batch_kernel)
+        *group_batch_kernel = "k_decode_batch_word_groups";
     RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
     return hipGetLastError();
 }

@@ -30,9 +30,14 @@ hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_
     return launch_decode_wave(format, p, num_cus, stream, kernel_name);
 }
 
-// ragged batches: the wave-per-stream kernels, whatever the interleave (ragged group / lane kernels are later work)
+// ragged batches: the wave-per-stream kernels, whatever the interleave -- unless the context asked for eight streams per wave
+// (RANS_AMD_OPT_BATCH_GROUPS) and the batch is the reference's 8-way word layout over u8 symbols, from eight streams on:
+// decode_groups.hip's ragged kernel.  Every other shape takes the wave kernels under that option as well (the ragged forms
+// of the group ENCODER, of k_decode_byte_pairs and of the lane kernels are later work).
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
 {
+    if ((p.variant & kVarBatchGroups) && format == (int)RANS_AMD_FMT_WORD && decode_batch_word_groups_applicable(p))
+        return launch_decode_batch_word_groups(p, num_cus, stream, batch_kernel);
     return launch_decode_batch_wave(format, p, num_cus, stream, batch_kernel);
 }
 

@@ -29,6 +29,7 @@ constexpr uint32_t kVarLanesFused = 4u;    // lane-per-chunk encoders place thei
 constexpr uint32_t kVarNoDual = 8u;        // alias decoders: always one chunk per wave (k_decode)
 constexpr uint32_t kVarDualAlways = 16u;   // ... two chunks per wave (k_decode_dual) whenever the tables fit, not only when
                                            //     they leave no room for a second block per CU
+constexpr uint32_t kVarBatchGroups = 32u;  // ragged batches of the 8-way word layout: eight streams per wave (k_decode_batch_word_groups)
 
 constexpr uint32_t kWorkPools = 8;       // chunk hand-out counters per launch (one per XCD)
 constexpr uint32_t kWorkPoolStride = 16; // in uint32: every counter on its own 64-byte line
@@ -233,8 +234,9 @@ bool encode_lanes_can_fuse(int format, const EncParams &p, int num_cus); // lane
 hipError_t launch_layout(const LayoutParams &p, hipStream_t stream);
 uint32_t layout_blocks(uint64_t nchunks); // blocks (and block_sums entries) launch_layout uses
 hipError_t launch_compact(const CompactParams &p, int num_cus, hipStream_t stream);
-// Ragged batches (rans_amd_decode_batch / rans_amd_encode_batch): always one stream per wave, whatever the interleave;
-// *batch_kernel receives the name of the kernel that was launched.  `format` is the kernel-side format number.
+// Ragged batches (rans_amd_decode_batch / rans_amd_encode_batch): one stream per wave, whatever the interleave -- but for the
+// decoder of the 8-way word layout under kVarBatchGroups, eight streams per wave; *batch_kernel receives the name of the
+// kernel that was launched.  `format` is the kernel-side format number.
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
 hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
 // rans_amd_batch_order: a permutation of the stream indices in which floor(log2(count + 1)) never increases.

@@ -75,6 +75,10 @@ hipError_t launch_decode_dual(int format, const DecParams &p, int num_cus, hipSt
 // symbols on a 4-byte aligned output, a partial last octet and a ragged last chunk included
 bool decode_word_groups_applicable(const DecParams &p);
 hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **name);
+// ... its ragged form (rans_amd_decode_batch under kVarBatchGroups): eight STREAMS per wave, each with its own symbol count
+// and output address, from eight streams on; the name goes to *group_batch_kernel
+bool decode_batch_word_groups_applicable(const DecParams &p);
+hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **group_batch_kernel);
 // 32 chunks per wave, the byte format's 2-way layout over u8 symbols (cum2sym tables), same file
 bool decode_byte_pairs_applicable(const DecParams &p);
 hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **name);
