@@ -76,9 +76,11 @@ def resident_waves(torch):
 
 
 class Batch:
-    """The symbols of a batch (dense, bench.gen_zipf seed 1), its models and the oracle's stream of every stream."""
+    """The symbols of a batch (dense, bench.gen_zipf seed 1), its models and the oracle's stream of every stream.
+    contents: {stream: its symbols} in place of the generator's (tests/test_gpu_rate_extremes.py); freqs: a normalised model
+    in place of the one counted from the generator's sample."""
 
-    def __init__(self, R, ctx, torch, oracle, row, counts, seed=1):
+    def __init__(self, R, ctx, torch, oracle, row, counts, seed=1, contents=None, freqs=None):
         import bench
         self.R, self.ctx, self.torch, self.row = R, ctx, torch, row
         self.counts = np.ascontiguousarray(counts, dtype=np.uint32)
@@ -86,9 +88,18 @@ class Batch:
         self.dense_offs = np.concatenate(([0], np.cumsum(self.counts.astype(np.int64))))
         total = int(self.dense_offs[-1])
         self.d_dense = bench.gen_zipf(torch, max(total, 1), row["K"], 1.0, seed, "cuda")[:total]
-        # (the model comes from a fixed 1 Mi-symbol sample of the same generator: every symbol of the alphabet is in it)
-        sample = bench.gen_zipf(torch, 1 << 20, row["K"], 1.0, seed, "cuda")
-        self.freqs, _ = R.normalize_freqs(ctx.count_freqs_device(sample, row["K"]), 1 << row["sb"])
+        if contents:
+            h = self.d_dense.cpu().numpy()
+            for c, content in contents.items():
+                assert content.size == self.counts[c]
+                h[self.dense_offs[c]:self.dense_offs[c + 1]] = np.asarray(content).astype(np.uint16).astype(h.dtype)
+            self.d_dense = torch.from_numpy(h).cuda()
+        if freqs is not None:
+            self.freqs = np.ascontiguousarray(freqs, dtype=np.uint32)
+        else:
+            # (the model comes from a fixed 1 Mi-symbol sample of the same generator: every symbol of the alphabet is in it)
+            sample = bench.gen_zipf(torch, 1 << 20, row["K"], 1.0, seed, "cuda")
+            self.freqs, _ = R.normalize_freqs(ctx.count_freqs_device(sample, row["K"]), 1 << row["sb"])
         self.gm = ctx.model(row["fmt"], self.freqs, row["sb"])
         self.om = oracle.model(self.freqs, row["sb"], with_alias=(row["fmt"] == FMT_ALIAS))
         h = self.d_dense.cpu().numpy()
