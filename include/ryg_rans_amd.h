@@ -61,7 +61,7 @@ extern "C" {
  * rans_amd_encode_adaptive_fmt / rans_amd_decode_adaptive_fmt (0.5.0); rans_amd_encode_adaptive_sized,
  * rans_amd_container_pack_indexed[_adaptive] (0.6.0); ragged batches -- rans_amd_batch_layout, rans_amd_encode_batch,
  * rans_amd_decode_batch, rans_amd_batch_order, rans_amd_batch_slice, rans_amd_encode_batch_adaptive[_bound],
- * rans_amd_decode_batch_adaptive (still 0.6.0: additions only).  A caller built
+ * rans_amd_decode_batch_adaptive, rans_amd_encode_batch_ordered (still 0.6.0: additions only).  A caller built
  * against an older header keeps working, with two behaviour changes it can observe: since 0.4.0
  * rans_amd_container_parse[_adaptive] want a 4-byte aligned `src` (RANS_AMD_E_ARG otherwise; an mmap at an odd offset must
  * be copied first), and since 0.5.0 rans_amd_container_compact checks its SOURCE index against src_bytes
@@ -161,11 +161,17 @@ enum rans_amd_option {
     RANS_AMD_OPT_ENC_SCRATCH_RING = 4,     /* 1 = the fused wave encoders code into a ring of scratch slots per coding
                                               wave, reused once drained (half the workspace of a large encode, 2-4 %
                                               slower); default 0: one scratch slot per chunk */
-    RANS_AMD_OPT_BATCH_GROUPS = 5          /* 1 = rans_amd_decode_batch decodes EIGHT streams per wavefront where the batch
+    RANS_AMD_OPT_BATCH_GROUPS = 5,         /* 1 = rans_amd_decode_batch decodes EIGHT streams per wavefront where the batch
                                               is the reference's 8-way word layout (word format, u8 symbols, n_ways 8,
                                               scale_bits 12, at least eight streams): k_decode_batch_word_groups; every
                                               other shape takes the wave-per-stream kernels as before.  Default 0: one
                                               stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
+    RANS_AMD_OPT_BATCH_ENCODE_GROUPS = 6   /* 1 = rans_amd_encode_batch[_ordered] codes EIGHT streams per wavefront where the
+                                              batch is that same shape (word format, u8 symbols, n_ways 8, scale_bits 12,
+                                              at least eight streams): k_encode_batch_word_groups, the same bytes; every
+                                              other shape takes the wave-per-stream kernels as before.  Default 0: one
+                                              stream per wavefront (RANS_AMD_OPT_BATCH_GROUPS is the decoder's alone).
+                                              Any other value is RANS_AMD_E_ARG. */
 };
 int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value);
 
@@ -368,12 +374,14 @@ int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, u
  * whatever the interleave: n_ways is anything rans_amd_ways_supported accepts (word 8-way, byte 2-way, rans64 2-way and
  * alias streams of the reference included -- narrow interleaves leave lanes idle, but across the whole GPU).  One shape
  * can pack eight streams into a wavefront, one state per lane: the 8-way word layout main_simd.cpp writes (word format,
- * u8 symbols, n_ways 8, scale_bits 12) in a batch of at least eight streams, decoded by rans_amd_decode_batch on a context
- * with rans_amd_ctx_set_option(ctx, RANS_AMD_OPT_BATCH_GROUPS, 1).  A wavefront then lasts as long as the longest of its
- * eight streams: pass the d_order of rans_amd_batch_order, which puts streams of one length bucket next to each other, and
- * lay the symbols out with sym_align = 4 (a stream whose output is not 4-byte aligned is decoded a round at a time).  The
- * encoder and every other interleave stay one stream per wavefront; ragged forms of their group and lane kernels are later
- * work.  A stream of 0 symbols is the n_ways flushed initial states.
+ * u8 symbols, n_ways 8, scale_bits 12) in a batch of at least eight streams -- decoded by rans_amd_decode_batch on a context
+ * with rans_amd_ctx_set_option(ctx, RANS_AMD_OPT_BATCH_GROUPS, 1), coded by rans_amd_encode_batch[_ordered] on a context with
+ * RANS_AMD_OPT_BATCH_ENCODE_GROUPS = 1; the two options are independent, and the bytes are the same with and without them.
+ * A wavefront then lasts as long as the longest of its eight streams: pass the d_order of rans_amd_batch_order, which puts
+ * streams of one length bucket next to each other, and lay the symbols out with sym_align = 4 (a stream whose symbols are
+ * not 4-byte aligned is decoded, and coded, a round at a time).  Every other interleave stays one stream per wavefront in
+ * both directions; ragged forms of the lane kernels and of the 2-way byte pairs are later work.  A stream of 0 symbols is
+ * the n_ways flushed initial states.
  * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
  * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).
  *
@@ -395,6 +403,16 @@ int rans_amd_batch_layout(const uint32_t *sym_counts, uint64_t n_streams, int fo
 int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_syms, const uint64_t *d_sym_offsets,
                           const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint64_t *d_slot_offsets,
                           void *d_out, uint64_t out_cap, uint64_t *d_offsets, uint32_t *d_lengths, void *stream);
+/* The same call with a hand-out order (rans_amd_encode_batch is this call with d_order = NULL).  d_order: NULL, or a
+ * permutation of the stream indices, e.g. from rans_amd_batch_order: the k-th claim of the launch takes stream d_order[k].
+ * Every stream, whatever its position, lands in its OWN slot with its OWN index entry: the order changes which wavefront
+ * codes a stream and when, never a byte of the result.  It keeps a long stream from being claimed last, and under
+ * RANS_AMD_OPT_BATCH_ENCODE_GROUPS it decides which eight streams share a wavefront.  An entry that names no stream
+ * (>= n_streams) codes nothing and writes no index entry; rans_amd_encode_status reports RANS_AMD_E_ARG. */
+int rans_amd_encode_batch_ordered(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_syms, const uint64_t *d_sym_offsets,
+                                  const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint64_t *d_slot_offsets,
+                                  const uint32_t *d_order, void *d_out, uint64_t out_cap, uint64_t *d_offsets, uint32_t *d_lengths,
+                                  void *stream);
 /* Decode stream c to d_out + d_sym_offsets[c] (d_out holds out_syms symbols).  The checks of rans_amd_decode apply to every
  * stream; the symbol index is data as well: a stream whose [sym_offset, sym_offset + count) does not lie inside
  * [0, out_syms) is skipped and counted as failed -- nothing outside d_out is ever written.  d_order (NULL, or a permutation

@@ -22,6 +22,7 @@ FMT_BYTE, FMT_WORD, FMT_R64, FMT_ALIAS = 0, 1, 2, 3
 FORMAT_NAMES = {FMT_BYTE: "byte", FMT_WORD: "word", FMT_R64: "r64", FMT_ALIAS: "alias"}
 
 OPT_LANE_KERNELS, OPT_LANE_FUSED_PLACEMENT, OPT_FUSED_PLACEMENT, OPT_DUAL_DECODE, OPT_ENC_SCRATCH_RING, OPT_BATCH_GROUPS = range(6)
+OPT_BATCH_ENCODE_GROUPS = 6
 
 OK, E_ARG, E_MODEL, E_SPACE, E_CORRUPT, E_UNSUPPORTED, E_HIP, E_NOMEM = range(8)
 
@@ -50,7 +51,7 @@ ABI_SYMBOLS = [
     "rans_amd_offsets_from_lengths", "rans_amd_container_bytes", "rans_amd_container_pack",
     "rans_amd_packed_payload_bytes", "rans_amd_container_pack_indexed", "rans_amd_container_pack_indexed_adaptive",
     "rans_amd_container_parse", "rans_amd_encode_workspace_bytes", "rans_amd_build_model_o0",
-    "rans_amd_batch_layout", "rans_amd_encode_batch", "rans_amd_decode_batch", "rans_amd_batch_order", "rans_amd_batch_slice",
+    "rans_amd_batch_layout", "rans_amd_encode_batch", "rans_amd_encode_batch_ordered", "rans_amd_decode_batch", "rans_amd_batch_order", "rans_amd_batch_slice",
     "rans_amd_encode_batch_adaptive_bound", "rans_amd_encode_batch_adaptive", "rans_amd_decode_batch_adaptive",
 ]
 
@@ -128,6 +129,7 @@ def _load():
         "rans_amd_decode_errors": (i32, [vp, u64p, vp]),
         "rans_amd_batch_layout": (i32, [u32p, u64, i32, u32, u32, u64p, u64p]),
         "rans_amd_encode_batch": (i32, [vp, vp, vp, vp, vp, u64, u32, vp, vp, u64, vp, vp, vp]),
+        "rans_amd_encode_batch_ordered": (i32, [vp, vp, vp, vp, vp, u64, u32, vp, vp, vp, u64, vp, vp, vp]),
         "rans_amd_decode_batch": (i32, [vp, vp, vp, u64, vp, vp, vp, vp, u64, u32, vp, vp, u64, u64p, vp]),
         "rans_amd_batch_order": (i32, [vp, vp, u64, vp, vp]),
         "rans_amd_batch_slice": (i32, [u32p, u64, u32, u64p]),
@@ -476,10 +478,11 @@ class Context:
 
     # -- ragged batches: many independent streams, each with its own symbol count
     def encode_batch(self, model, d_syms, d_sym_offsets, d_sym_counts, n_ways, d_slot_offsets, d_out=None, d_offsets=None,
-                     d_lengths=None, out_cap=None):
-        """rans_amd_encode_batch (asynchronous; encode_status() reports): stream c = the d_sym_counts[c] symbols at
+                     d_lengths=None, out_cap=None, d_order=None):
+        """rans_amd_encode_batch_ordered (asynchronous; encode_status() reports): stream c = the d_sym_counts[c] symbols at
         d_sym_offsets[c], coded to the end of slot [d_slot_offsets[c], d_slot_offsets[c + 1]).  d_sym_offsets / d_slot_offsets:
-        int64 tensors (batch_layout), d_sym_counts: int32.  Returns (d_container, d_offsets, d_lengths)."""
+        int64 tensors (batch_layout), d_sym_counts: int32; d_order: int32 tensor (batch_order) or None -- the hand-out order,
+        which never changes a byte of the result.  Returns (d_container, d_offsets, d_lengths)."""
         import torch
         n_streams = d_sym_counts.numel()
         dev = d_sym_counts.device
@@ -490,10 +493,11 @@ class Context:
             d_offsets = torch.zeros(max(n_streams, 1), dtype=torch.int64, device=dev)
         if d_lengths is None:
             d_lengths = torch.zeros(max(n_streams, 1), dtype=torch.int32, device=dev)
-        _check(_lib.rans_amd_encode_batch(self._h, model._h, d_syms.data_ptr(), d_sym_offsets.data_ptr(), d_sym_counts.data_ptr(),
-                                          n_streams, n_ways, d_slot_offsets.data_ptr(), d_out.data_ptr(),
-                                          d_out.numel() if out_cap is None else out_cap, d_offsets.data_ptr(),
-                                          d_lengths.data_ptr(), _torch_stream()), "encode_batch")
+        _check(_lib.rans_amd_encode_batch_ordered(self._h, model._h, d_syms.data_ptr(), d_sym_offsets.data_ptr(),
+                                                  d_sym_counts.data_ptr(), n_streams, n_ways, d_slot_offsets.data_ptr(),
+                                                  d_order.data_ptr() if d_order is not None else None, d_out.data_ptr(),
+                                                  d_out.numel() if out_cap is None else out_cap, d_offsets.data_ptr(),
+                                                  d_lengths.data_ptr(), _torch_stream()), "encode_batch")
         return d_out, d_offsets, d_lengths
 
     def decode_batch(self, model, d_container, container_bytes, d_offsets, d_lengths, d_sym_offsets, d_sym_counts, n_ways,

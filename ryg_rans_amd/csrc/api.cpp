@@ -175,8 +175,11 @@ int encode_flags_status(uint32_t flags)
         return fail(RANS_AMD_E_SPACE, "encode: container does not fit out_cap");
     if (flags & 4u) // (a kernel that addresses its LDS tables by raw offsets found them elsewhere: never code on that)
         return fail(RANS_AMD_E_HIP, "encode: internal error (dynamic LDS does not start at offset 0)");
-    if (flags & 2048u) // rans_amd_encode_batch_adaptive: such a stream was coded as an empty one, nothing of it was read
-        return fail(RANS_AMD_E_ARG, "encode_batch_adaptive: a stream's symbol range lies outside [0, in_syms), or holds more than 0x7fff0000 symbols");
+    // rans_amd_encode_batch_adaptive: such a stream was coded as an empty one, nothing of it was read;
+    // rans_amd_encode_batch_ordered: nothing was coded for that position of the order
+    if (flags & 2048u)
+        return fail(RANS_AMD_E_ARG, "encode_batch_adaptive: a stream's symbol range lies outside [0, in_syms), or holds more than 0x7fff0000 "
+                                    "symbols; encode_batch_ordered: an entry of d_order names no stream");
     if (flags & 512u) // rans_amd_container_compact: an index entry (offset, length) does not lie inside the source buffer
         return fail(RANS_AMD_E_CORRUPT, "container_compact: a chunk of the source index lies outside [0, src_bytes)");
     if (flags & ~7u) { // a wait of the fused placement gave up (device_common.hpp SpinWatch; 256: a coder waiting for its scratch slot)
@@ -638,6 +641,11 @@ int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value)
         if (value != 0 && value != 1)
             return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_GROUPS takes 0 (one stream per wave) or 1 (eight 8-way word streams per wave)");
         ctx->variant = value ? (ctx->variant | kVarBatchGroups) : (ctx->variant & ~kVarBatchGroups);
+        return RANS_AMD_OK;
+    case RANS_AMD_OPT_BATCH_ENCODE_GROUPS:
+        if (value != 0 && value != 1)
+            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_ENCODE_GROUPS takes 0 (one stream per wave) or 1 (eight 8-way word streams per wave)");
+        ctx->variant = value ? (ctx->variant | kVarBatchEncGroups) : (ctx->variant & ~kVarBatchEncGroups);
         return RANS_AMD_OK;
     default:
         return fail(RANS_AMD_E_ARG, "set_option: unknown option");
@@ -1457,6 +1465,15 @@ int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
                           const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint64_t *d_slot_offsets,
                           void *d_out, uint64_t out_cap, uint64_t *d_offsets, uint32_t *d_lengths, void *stream)
 {
+    return rans_amd_encode_batch_ordered(ctx, model, d_syms, d_sym_offsets, d_sym_counts, n_streams, n_ways, d_slot_offsets, nullptr, d_out,
+                                         out_cap, d_offsets, d_lengths, stream);
+}
+
+int rans_amd_encode_batch_ordered(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_syms, const uint64_t *d_sym_offsets,
+                                  const uint32_t *d_sym_counts, uint64_t n_streams, uint32_t n_ways, const uint64_t *d_slot_offsets,
+                                  const uint32_t *d_order, void *d_out, uint64_t out_cap, uint64_t *d_offsets, uint32_t *d_lengths,
+                                  void *stream)
+{
     if (!ctx || !model || (n_streams && (!d_sym_offsets || !d_sym_counts || !d_slot_offsets || !d_out || !d_offsets || !d_lengths)))
         return fail(RANS_AMD_E_ARG, "encode_batch: NULL argument");
     if (model->ctx != ctx)
@@ -1498,6 +1515,7 @@ int rans_amd_encode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
         ep.sym_offsets = d_sym_offsets;
         ep.sym_counts = d_sym_counts;
         ep.slot_offsets = d_slot_offsets;
+        ep.order = d_order;
         fill_encoder_model(ep, model);
         ep.flags = ctx->d_enc_flags();
         ep.variant = ctx->variant;

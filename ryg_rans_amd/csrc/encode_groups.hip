@@ -21,7 +21,9 @@
 // sized slots -- a store that would start below the slot's first byte is dropped, and a chunk whose stream turns out longer
 // than its slot is listed for the redo launch exactly as the lane encoders list theirs (EncParams::ovf_ctl).
 // Chunks of a multiple of 4 symbols (launcher: the symbol loads are dword-aligned); what a chunk size off 128 leaves, and the
-// input's last octet when its last chunk is a ragged one, go round by round.
+// input's last octet when its last chunk is a ragged one, go round by round.  The ragged form for rans_amd_encode_batch --
+// eight STREAMS per wave, each with its own symbol count, symbol address and slot -- is k_encode_batch_word_groups, behind the
+// uniform kernel.
 //
 // No MFMA: integer, table-driven, serial per state.
 
@@ -300,6 +302,250 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_word_groups(const 
         atomicOr(p.flags, 1u);
 }
 
+// ---------------------------------------------------------------------------
+// k_encode_batch_word_groups -- the ragged form of k_encode_word_groups (rans_amd_encode_batch[_ordered] under
+// RANS_AMD_OPT_BATCH_ENCODE_GROUPS): a wave's eight groups hold eight STREAMS, each with its own symbol count, symbol address
+// and slot.  The unit of work is one octet of the hand-out order: lane 8 g + i holds state i of the stream at position
+// 8 o + g -- stream order[8 o + g], or 8 o + g without an order; a position at or past nchunks has no stream.  The rounds, the
+// record table, the ring and its blocks, the transposes and the half-group exchange are k_encode_word_groups'.  The coder
+// works from a stream's last symbol to its first, so the eight groups START together and finish at different times:
+//   * tail first: the count_g - 128 blocks_g symbols behind the stream's last whole 128-byte line (all of them where the
+//     stream's first symbol is not 4-byte aligned: blocks_g = 0) go one round at a time, a byte load per lane, lanes without a
+//     symbol sitting out; the wave runs max_g(ceil(tail_g / 8)) iterations, iteration k is round ceil(tail_g / 8) - 1 - k of
+//     group g.  Nothing of a group that sits out is touched: one_round emits and tracks under `active` only;
+//   * then lines: the wave runs the sixteen-round sequence max_g(blocks_g) times with FULL exec (the sequence sets exec = -1
+//     itself, and the DPP moves of the exchange read zeros from lanes an exec mask has switched off); iteration q is line
+//     blocks_g - 1 - q of group g while q < blocks_g.
+// A group is FINALISED -- its last block check, the eight flushed states, the last one or two blocks, lengths[s] and
+// offsets[s] -- at the top of the iteration q == blocks_g: right behind its last round (behind the tail when it has no whole
+// line), before the wave runs another round.  From then on it is DEAD, and so is, from the start, a group without a stream
+// or with a rejected one.  That answers the two hazards of a group that has to ride along under full exec:
+//   1. the sequence's ds_write_b16 runs under exec = vcc, the whole wave's emitters, whatever the group's bits of the ballot
+//      are.  A dead group's bits are zeroed (its c stands still, its rank is 0), but its lanes still write, at
+//      ring | (-2 c & 255): the place of the word the stream emitted last.  Because the group was finalised before the first
+//      such round, that word has left; flush_block and the index stores are closed to a dead group for good, so what its ring,
+//      its x and its c become is of no consequence: the record address comes from the symbol byte (zero: inside the table),
+//      the ring address is masked into the group's own 256 bytes, and it reads and writes no global memory;
+//   2. TRACK ORs the record's third word into `worst`, and a dead group is fed the record of byte value 0, which a model
+//      need not have: `worst` is put back from a copy behind every line for the groups that did not run it.
+// Index entries are the caller's data and checked exactly as k_encode's MODE 4 checks them (encode_wave.hip): a slot that
+// fails is not written, lengths[s] = 0, offsets[s] = the slot's end, bit 1 of the flags; an order entry that names no stream
+// codes nothing, writes no index entry and sets bit 11 (RANS_AMD_E_ARG).  Every lane addresses symbols and slots in 64 bits.
+// ---------------------------------------------------------------------------
+typedef uint32_t u32x4_sym __attribute__((ext_vector_type(4), aligned(4))); // a line piece on the 4-byte grid
+
+template <bool SMALL, bool TRACK>
+__global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_batch_word_groups(const EncParams p)
+{
+    using Tr = FmtTraits<FMT_WORD>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    {
+        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.word_enc_recs);
+        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
+        for (uint32_t i = threadIdx.x; i < kEncGrpTable / 16u; i += blockDim.x)
+            l0[i] = g0[i];
+    }
+    __syncthreads();
+    if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never code on a wrong assumption
+        if (threadIdx.x == 0)
+            atomicOr(p.flags, 4u);
+        return;
+    }
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t g = lane >> 3, i = lane & 7u;
+    const uint32_t ring_c = kEncGrpTable + wave * kEncGrpWaveLds + g * kEncGrpRing; // (as in k_encode_word_groups)
+    uint32_t ring = ring_c;
+    uint32_t gm_lo = g < 4 ? 0xffu << (8u * g) : 0u, gm_hi = g >= 4 ? 0xffu << (8u * (g - 4u)) : 0u;
+    uint32_t k255 = 255u, k4 = 4u;
+    asm volatile("v_mov_b32 %0, %0" : "+v"(ring)); // opaque: keep them in VGPRs
+    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_lo));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_hi));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(k255));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(k4));
+    const uint32_t sel1 = (lane & 1u) ? 0x03070105u : 0x06020400u;
+    const uint32_t sel2 = (lane & 2u) ? 0x03020706u : 0x05040100u;
+    const uint64_t octets = (p.nchunks + 7u) >> 3; // one per claim (the last one may hold fewer than eight streams)
+
+    auto wave_max = [&](uint32_t v) -> uint32_t { // over the eight groups (v is the same in a group's lanes)
+        uint32_t m = 0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const uint32_t t = __builtin_amdgcn_readlane(v, 8 * k);
+            m = t > m ? t : m;
+        }
+        return m;
+    };
+
+    uint32_t worst = 0;
+    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
+    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
+    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
+    const uint32_t pool = blockIdx.x % npools;
+    for (;;) {
+        uint64_t octet; // (handed out as in k_encode_word_groups: the pooled counters, or a static stride without them)
+        if (p.claims) {
+            uint32_t got = 0;
+            if (lane == 0)
+                got = atomicAdd(p.claims + pool * kWorkPoolStride, 1u);
+            octet = (uint64_t)uniform(got) * npools + pool;
+        } else {
+            octet = uniform64(claim_v);
+            claim_v += total_waves;
+        }
+        if (octet >= octets)
+            break;
+        // ---- this group's stream: its index entries, all of them the caller's data
+        const uint64_t pos = octet * 8u + g;
+        const bool exists = pos < p.nchunks;
+        uint64_t s = pos;
+        if (exists && p.order)
+            s = p.order[pos];
+        const bool named = exists && s < p.nchunks;
+        if (exists && !named && i == 0) // an order entry that names no stream: nothing coded, no index entry
+            atomicOr(p.flags, 2048u);
+        uint64_t first = 0, slot_at = 0, slot_end = 0;
+        uint32_t count = 0;
+        if (named) {
+            first = p.sym_offsets[s];
+            count = p.sym_counts[s];
+            slot_at = p.slot_offsets[s];
+            slot_end = p.slot_offsets[s + 1];
+        }
+        // what rans_amd_chunk_bound() asks for this stream: two bytes per symbol + the eight flushed states
+        const uint64_t need = ((uint64_t)count * 2u + 8u * 4u + 15u) & ~15ull;
+        const uint64_t slot_size = slot_end - slot_at;
+        const bool fits = ((slot_at | slot_end) & 15u) == 0 && slot_end >= slot_at && slot_end <= p.out_cap && slot_size >= need &&
+                          slot_size <= 0xfffffff0ull;
+        if (named && !fits && i == 0) { // nothing of this stream is written
+            atomicOr(p.flags, 2u);
+            p.lengths[s] = 0u;
+            p.offsets[s] = slot_end;
+        }
+        bool live = named && fits; // the group holds a stream that is still being coded
+        const uint32_t slot = (uint32_t)slot_size;
+        const uint64_t out_end = reinterpret_cast<uint64_t>(p.scratch) + slot_end; // (live: 16-byte aligned, inside the container)
+        const uint64_t src = reinterpret_cast<uint64_t>(p.syms) + first;
+        const uint32_t blocks = (live && (src & 3u) == 0) ? count >> 7 : 0u;
+        const uint32_t tail = live ? count - (blocks << 7) : 0u;
+        const uint32_t tail_rounds = (uint32_t)(((uint64_t)tail + 7u) >> 3);
+        const uint32_t max_blocks = wave_max(blocks), max_tail_rounds = wave_max(tail_rounds);
+
+        uint32_t x = Tr::kL, c = 0, fb = 0; // state, words emitted so far (the group's), blocks flushed
+        uint32_t m_lo = live ? gm_lo : 0u, m_hi = live ? gm_hi : 0u; // my group's bits of the ballot; none once it is dead
+        // block fb of the ring -> its place below the slot's end; a piece that would start below the slot's first byte is dropped,
+        // and so is one that lies wholly below the stream (k_encode_word_groups' two guards); nothing leaves a dead group
+        auto flush_block = [&](uint32_t have_bytes) { // have_bytes: the group's stream so far
+            const uint64_t below = (uint64_t)kEncGrpBlock * (fb + 1u) - 16u * i; // this lane's piece starts `below` bytes under the slot's end
+            if (live && below <= slot && below - 16u < have_bytes) {
+                const u32x4 v = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(ring_c + ((fb & 1u) ? 0u : kEncGrpBlock) + 16u * i));
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(out_end - below) = v;
+            }
+            fb += 1u;
+        };
+        auto one_round = [&](uint32_t sym, bool active) { // (k_encode_word_groups' one_round, the ballot cut by m_lo / m_hi)
+            const u32x4 rec = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(sym << 4));
+            const bool emit = active && x > rec.y; // rans_word_sse41.h:85
+            const uint64_t m = __builtin_amdgcn_ballot_w64(emit);
+            const uint32_t t_lo = (uint32_t)m & m_lo, t_hi = (uint32_t)(m >> 32) & m_hi;
+            const uint32_t rank = __builtin_amdgcn_mbcnt_hi(t_hi, __builtin_amdgcn_mbcnt_lo(t_lo, 0u));
+            c += (uint32_t)__builtin_popcount(t_lo) + (uint32_t)__builtin_popcount(t_hi);
+            if (emit) {
+                *reinterpret_cast<RANS_LDS uint16_t *>((uintptr_t)(ring_c | ((2u * (rank - c)) & 255u))) = (uint16_t)x;
+                x >>= 16;
+            }
+            if (active) { // encode_common.hpp RANS_ENC_WORD_TAIL_*: x += bias + (x / freq) * cmpl
+                uint32_t q = __umulhi(x, rec.x);
+                if constexpr (!SMALL)
+                    q += (x - q) >> 1;
+                q >>= rec.z >> 24;
+                x = x + rec.w + (q & 0xffffffu) * (rec.z & 0xffffffu);
+                worst |= rec.z;
+            }
+        };
+        // ---- tail: the rounds behind the stream's last whole line, the group's last round first
+        {
+            const uint8_t RANS_GLOBAL *tsrc = reinterpret_cast<const uint8_t RANS_GLOBAL *>(src + ((uint64_t)blocks << 7) + i);
+            for (uint32_t k = 0; k < max_tail_rounds; ++k) {
+                const bool in = k < tail_rounds; // (the same for the eight lanes of a group)
+                const uint32_t r = tail_rounds - 1u - k;
+                const bool active = in && r * 8u + i < tail; // (r < 2^29: count < 2^31 follows from the slot's size)
+                one_round(active ? (uint32_t)tsrc[(uint64_t)r * 8u] : 0u, active);
+                // (at least every eight rounds of any group; never true for a group that sits out: its c stands still)
+                if ((k & 7u) == 7u && c >= 64u * (fb + 1u))
+                    flush_block(2u * c);
+            }
+        }
+        // ---- lines: sixteen rounds each, the group's last line first
+        uint64_t lp = src + ((uint64_t)blocks << 7) + 16u * i; // 128 bytes above this lane's piece of the next line to load
+        auto load_line = [&](bool want) -> u32x4 {
+            u32x4 v = {0u, 0u, 0u, 0u}; // (a dead group codes zeros)
+            if (want) {
+                lp -= kEncGrpBlock;
+                const u32x4_sym t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_sym RANS_GLOBAL *>(lp));
+                v = u32x4{t.x, t.y, t.z, t.w};
+            }
+            return v;
+        };
+        u32x4 next = load_line(blocks != 0u);
+        for (uint32_t q = 0;; ++q) {
+            if (live && q == blocks) { // ---- finalise: this group's last round is behind it
+                if (c >= 64u * (fb + 1u)) // (the last eight rounds' block)
+                    flush_block(2u * c);
+                // the final states, state 0 lowest (RansWordEncFlush): lane i's dword starts 2 c + 32 - 4 i bytes below the slot's end
+                const uint32_t at = 0u - (2u * c + 32u - 4u * i);
+                *reinterpret_cast<RANS_LDS uint16_t *>((uintptr_t)(ring_c | (at & 255u))) = (uint16_t)x;
+                *reinterpret_cast<RANS_LDS uint16_t *>((uintptr_t)(ring_c | ((at + 2u) & 255u))) = (uint16_t)(x >> 16);
+                c += 16u;
+                const uint32_t len = 2u * c;
+                if (64u * fb < c)
+                    flush_block(len);
+                if (64u * fb < c)
+                    flush_block(len);
+                if (i == 0) {
+                    p.lengths[s] = len;
+                    p.offsets[s] = slot_end - len;
+                }
+                live = false; // dead: no block, no index store ever again
+                m_lo = m_hi = 0u;
+            }
+            if (q == max_blocks)
+                break;
+            const bool run = q < blocks;
+            const u32x4 v = next;
+            next = load_line(q + 1u < blocks);
+            const uint32_t worst_keep = worst;
+            uint32_t a0, a1, a2, a3;
+            // rows 2 i, 2 i + 1 of the line -> this state's column (k_encode_word_groups' exchange, under full exec: see there)
+            asm volatile("s_nop 1\n\t"
+                         "s_mov_b64 vcc, %[lower]\n\t"
+                         "v_cndmask_b32_dpp %[a0], %[vy], %[vx], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                         "v_cndmask_b32_dpp %[a1], %[vw], %[vz], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                         "s_mov_b64 vcc, %[upper]\n\t"
+                         "v_cndmask_b32_dpp %[a2], %[vx], %[vy], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+                         "v_cndmask_b32_dpp %[a3], %[vz], %[vw], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+                         : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3)
+                         : [vx] "v"(v.x), [vy] "v"(v.y), [vz] "v"(v.z), [vw] "v"(v.w), [lower] "s"(0x0f0f0f0f0f0f0f0full),
+                           [upper] "s"(0xf0f0f0f0f0f0f0f0ull)
+                         : "vcc");
+            a0 = quad_transpose(a0, sel1, sel2); // byte J of a_k: round 8 (k >> 1) + 2 J + (k & 1)
+            a1 = quad_transpose(a1, sel1, sel2);
+            a2 = quad_transpose(a2, sel1, sel2);
+            a3 = quad_transpose(a3, sel1, sel2);
+            if (c >= 64u * (fb + 1u)) // (never true for a dead group: it left with 64 fb >= c, and its c stands still)
+                flush_block(2u * c);
+            encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a2, a3, k4, m_lo, m_hi, k255, ring); // rounds 15 .. 8
+            if (c >= 64u * (fb + 1u))
+                flush_block(2u * c);
+            encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a0, a1, k4, m_lo, m_hi, k255, ring); // rounds 7 .. 0
+            worst = run ? worst : worst_keep;
+        }
+    }
+    if (TRACK && __builtin_amdgcn_ballot_w64((worst >> 31) != 0) != 0 && lane == 0)
+        atomicOr(p.flags, 1u);
+}
+
 } // namespace
 
 // (api.cpp asks this while it still fills the parameters in: only what it sets first counts -- the shape, the symbol buffer, the
@@ -331,6 +577,37 @@ hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_
         RANS_LAUNCH((k_encode_word_groups<false, true>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
     else
         RANS_LAUNCH((k_encode_word_groups<false, false>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
+    return hipGetLastError();
+}
+
+// the ragged form: the reference's 8-way word layout over u8 symbols at 12 bits, from eight streams on (everything else stays
+// with the wave-per-stream kernels); counts, symbol addresses and slots are the kernel's to check
+bool encode_batch_word_groups_applicable(const EncParams &p)
+{
+    return p.n_ways == 8 && p.sym_bytes == 1 && p.nsyms <= 256 && p.word_enc_recs && p.scale_bits == 12 && p.nchunks >= 8 &&
+           (reinterpret_cast<uintptr_t>(p.scratch) & 15u) == 0;
+}
+
+hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **group_batch_enc_kernel)
+{
+    if (!encode_batch_word_groups_applicable(p) || !p.sym_offsets || !p.sym_counts || !p.slot_offsets || !p.lengths || !p.offsets || !p.flags)
+        return hipErrorInvalidValue;
+    const size_t lds = kEncGrpTable + (size_t)(kEncGrpThreads / 64) * kEncGrpWaveLds;
+    const uint64_t octets = (p.nchunks + 7u) / 8u;
+    const uint64_t want_blocks = (octets + kEncGrpThreads / 64 - 1) / (kEncGrpThreads / 64);
+    const uint64_t cap = (uint64_t)num_cus * 2u;
+    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
+    if (group_batch_enc_kernel)
+        *group_batch_enc_kernel = "k_encode_batch_word_groups";
+    const bool small = p.word_small != 0, track = p.dense256 == 0;
+    if (small && track)
+        RANS_LAUNCH((k_encode_batch_word_groups<true, true>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
+    else if (small)
+        RANS_LAUNCH((k_encode_batch_word_groups<true, false>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
+    else if (track)
+        RANS_LAUNCH((k_encode_batch_word_groups<false, true>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
+    else
+        RANS_LAUNCH((k_encode_batch_word_groups<false, false>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
     return hipGetLastError();
 }
 

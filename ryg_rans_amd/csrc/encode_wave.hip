@@ -86,7 +86,7 @@ __device__ __forceinline__ void place_and_copy(const EncParams &p, uint64_t chun
 //         still lies inside the slot -- exactly where the stream is staged in LDS (the flush knows what it is about to
 //         write), by the round's worst case elsewhere -- and a chunk that does not fit is abandoned and listed for the
 //         second launch (EncParams::redo), which codes the listed chunks into worst-case slots behind the sized ones.
-// MODE 4: MODE 2 for a ragged batch (rans_amd_encode_batch): stream c's symbols are sym_counts[c] at sym_offsets[c] and its
+// MODE 4: MODE 2 for a ragged batch (rans_amd_encode_batch[_ordered]; claim k takes stream EncParams::order[k]): stream c's symbols are sym_counts[c] at sym_offsets[c] and its
 //         slot is [slot_offsets[c], slot_offsets[c + 1]) -- both the caller's data: a slot that is misplaced, lies outside
 //         out_cap or is smaller than the worst case of its stream is not written at all (flags bit 1, RANS_AMD_E_SPACE).
 template <int FMT, int K, int MODE>
@@ -266,7 +266,18 @@ __global__ void __launch_bounds__(FMT == FMT_ALIAS_LDS ? kEncAliasLdsThreads : (
         }
         if (chunk_v >= p.nchunks)
             break;
-        const uint64_t chunk = uniform64(chunk_v);
+        uint64_t claimed = uniform64(chunk_v);
+        if constexpr (RAGGED) { // claim k takes stream order[k]: its own symbols, its own slot, its own index entry
+            if (p.order) {
+                claimed = uniform(p.order[claimed]);
+                if (claimed >= p.nchunks) { // the entry names no stream: nothing coded, no index entry (RANS_AMD_E_ARG)
+                    if (lane == 0)
+                        atomicOr(p.flags, 2048u);
+                    continue;
+                }
+            }
+        }
+        const uint64_t chunk = claimed;
         uint64_t first = chunk * p.chunk_syms;
         uint32_t nsym = 0;
         uint64_t slot_size = p.slot_bytes, ragged_at = 0;

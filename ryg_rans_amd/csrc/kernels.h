@@ -30,6 +30,7 @@ constexpr uint32_t kVarNoDual = 8u;        // alias decoders: always one chunk p
 constexpr uint32_t kVarDualAlways = 16u;   // ... two chunks per wave (k_decode_dual) whenever the tables fit, not only when
                                            //     they leave no room for a second block per CU
 constexpr uint32_t kVarBatchGroups = 32u;  // ragged batches of the 8-way word layout: eight streams per wave (k_decode_batch_word_groups)
+constexpr uint32_t kVarBatchEncGroups = 64u; // ... in the ENCODER as well (k_encode_batch_word_groups)
 
 constexpr uint32_t kWorkPools = 8;       // chunk hand-out counters per launch (one per XCD)
 constexpr uint32_t kWorkPoolStride = 16; // in uint32: every counter on its own 64-byte line
@@ -167,12 +168,14 @@ struct EncParams {
     uint32_t redo;              // 1 = the second launch
     uint64_t ovf_base;          // redo: byte offset of the overflow region (= nchunks * the first launch's slot_bytes)
     uint32_t no_lanes;          // the request goes to the wave encoders whatever its interleave (sized slots the lane encoders cannot take)
-    // Ragged batches (rans_amd_encode_batch; k_encode's MODE 4, nobody else reads these): stream c codes the sym_counts[c]
-    // symbols at syms + sym_offsets[c] * sym_bytes into the slot [slot_offsets[c], slot_offsets[c + 1]) of `scratch` (the
-    // caller's container, out_cap bytes), ending at the slot's end
+    // Ragged batches (rans_amd_encode_batch[_ordered]; k_encode's MODE 4 and k_encode_batch_word_groups, nobody else reads
+    // these): stream c codes the sym_counts[c] symbols at syms + sym_offsets[c] * sym_bytes into the slot [slot_offsets[c],
+    // slot_offsets[c + 1]) of `scratch` (the caller's container, out_cap bytes), ending at the slot's end; claim k takes
+    // stream order[k] -- every stream lands in its OWN slot whatever its position, the order decides who codes it and when
     const uint64_t *sym_offsets;
     const uint32_t *sym_counts;
     const uint64_t *slot_offsets; // [nchunks + 1], multiples of 16
+    const uint32_t *order;        // or NULL: claim k takes stream k
 };
 constexpr uint32_t kEncMailboxStride = 640; // a block's mailbox in global memory (EncParams::mailbox_global): whole 128-byte lines
 // Scratch ring of the fused wave encoders: every coding wave owns kEncRingSlots worst-case slots and codes its chunks
@@ -234,9 +237,10 @@ bool encode_lanes_can_fuse(int format, const EncParams &p, int num_cus); // lane
 hipError_t launch_layout(const LayoutParams &p, hipStream_t stream);
 uint32_t layout_blocks(uint64_t nchunks); // blocks (and block_sums entries) launch_layout uses
 hipError_t launch_compact(const CompactParams &p, int num_cus, hipStream_t stream);
-// Ragged batches (rans_amd_decode_batch / rans_amd_encode_batch): one stream per wave, whatever the interleave -- but for the
-// decoder of the 8-way word layout under kVarBatchGroups, eight streams per wave; *batch_kernel receives the name of the
-// kernel that was launched.  `format` is the kernel-side format number.
+// Ragged batches (rans_amd_decode_batch / rans_amd_encode_batch[_ordered]): one stream per wave, whatever the interleave -- but
+// for the 8-way word layout eight streams per wave, in the decoder under kVarBatchGroups and in the encoder under
+// kVarBatchEncGroups; *batch_kernel receives the name of the kernel that was launched.  `format` is the kernel-side format
+// number.
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
 hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
 // rans_amd_batch_order: a permutation of the stream indices in which floor(log2(count + 1)) never increases.

@@ -87,6 +87,10 @@ hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t
 // three-kernel placement, the slot layout or sized slots (no fused placement)
 bool encode_word_groups_applicable(const EncParams &p);
 hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **name);
+// ... its ragged form (rans_amd_encode_batch[_ordered] under kVarBatchEncGroups): eight STREAMS per wave, each with its own
+// symbol count, symbol address and slot, from eight streams on; the name goes to *group_batch_enc_kernel
+bool encode_batch_word_groups_applicable(const EncParams &p);
+hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **group_batch_enc_kernel);
 
 // lane-per-stream kernels (N = 1, 2, 4, 8 with at least kLaneKernelMinChunks chunks): decode_lanes.hip, encode_lanes.hip
 constexpr uint64_t kLaneKernelMinChunks = 64;

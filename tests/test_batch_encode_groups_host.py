@@ -1,0 +1,114 @@
+"""Ragged batches CODED with eight 8-way word streams per wave (RANS_AMD_OPT_BATCH_ENCODE_GROUPS) and the batch encoders'
+hand-out order (rans_amd_encode_batch_ordered), the part that needs no GPU: the name test of the group batch ENCODERS, the
+option's constant, the entry point, and the proof that the rate inputs of tests/test_gpu_batch_encode_groups.py reach the
+bounds that file claims.
+
+test_no_group_batch_enc_kernel_without_a_row: the launchers of the encoders that pack several ragged streams into a wave
+report their kernel through an out-parameter spelled `*group_batch_enc_kernel = ...;` -- a fifth spelling beside
+`*name = ...;` (tests/test_gpu_kernel_matrix.py), `*batch_kernel = ...;` (tests/test_batch_host.py), `*models_batch_kernel
+= ...;` (tests/test_batch_models_host.py) and `*group_batch_kernel = ...;` (tests/test_batch_groups_host.py), invisible to
+those four tests.  Every literal of such a statement in ryg_rans_amd/csrc/*.hip must be the encode name of a row of
+ENC_GROUP_ROWS in tests/test_gpu_batch_encode_groups.py, and ENC_GROUP_ROWS must name no encoder the sources do not contain."""
+import glob
+import os
+import re
+
+import numpy as np
+
+import _stream_rate as S
+import ryg_rans_amd as R
+from _oracle import FMT_WORD
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
+_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
+
+
+def source_group_batch_enc_kernel_names(csrc=CSRC):
+    """Every string literal of a statement `*group_batch_enc_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
+    names, sites = set(), 0
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        for m in re.finditer(r"\*group_batch_enc_kernel\s*=\s*([^;]*);", open(path).read()):
+            sites += 1
+            names.update(_LITERAL.findall(m.group(1)))
+    return names, sites
+
+
+def test_no_group_batch_enc_kernel_without_a_row():
+    from test_gpu_batch_encode_groups import ENC_GROUP_ROWS
+    names, sites = source_group_batch_enc_kernel_names()
+    assert sites >= 1, sites
+    assert "k_encode_batch_word_groups" in names
+    rows = {r["encode"] for r in ENC_GROUP_ROWS}
+    assert names == rows, ("kernels no row of ENC_GROUP_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
+    # disjoint from what the four other spellings' scans find
+    from test_batch_groups_host import source_group_batch_kernel_names
+    from test_batch_host import source_batch_kernel_names
+    from test_batch_models_host import source_models_batch_kernel_names
+    from test_gpu_kernel_matrix import source_kernel_names
+    assert not names & source_kernel_names()[0]
+    assert not names & source_batch_kernel_names()[0]
+    assert not names & source_models_batch_kernel_names()[0]
+    assert not names & source_group_batch_kernel_names()[0]
+    # the check has teeth: without its row a kernel is reported missing
+    less = {r["encode"] for r in ENC_GROUP_ROWS if r["id"] != "word-8-enc-groups"}
+    assert "k_encode_batch_word_groups" in names - less
+
+
+def test_batch_encode_groups_option_constant():
+    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
+    m = re.search(r"RANS_AMD_OPT_BATCH_ENCODE_GROUPS\s*=\s*(\d+)", header)
+    assert m and int(m.group(1)) == 6
+    assert R.OPT_BATCH_ENCODE_GROUPS == 6
+    # the five older constants are where they were
+    older = ("LANE_KERNELS", "LANE_FUSED_PLACEMENT", "FUSED_PLACEMENT", "DUAL_DECODE", "ENC_SCRATCH_RING", "BATCH_GROUPS")
+    for value, name in enumerate(older):
+        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % name, header)
+        assert m and int(m.group(1)) == value and getattr(R, "OPT_" + name) == value, name
+    # (a NULL context is refused before the option is looked at; the values need a context: tests/test_gpu_batch_encode_groups.py)
+    assert R.lib().rans_amd_ctx_set_option(None, 6, 1) == R.E_ARG
+    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+
+
+def test_encode_batch_ordered_refuses_a_null_context():
+    assert "rans_amd_encode_batch_ordered" in open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
+    rc = R.lib().rans_amd_encode_batch_ordered(None, None, None, None, None, 0, 8, None, None, None, 0, None, None, None)
+    assert rc == R.E_ARG
+    assert b"NULL argument" in R.lib().rans_amd_last_error()
+
+
+def test_rate_inputs_reach_their_bounds():
+    """The rare-only streams of the GPU file's rate octet hold a window of eight rounds with 96 bytes -- a 128-byte block
+    per check of the group's ring, the most a valid stream can emit --, its quiet streams have at least 1000 consecutive
+    rounds without a byte, and its bursts hold both; the finish octet's streams begin with rare symbols."""
+    from test_gpu_batch_encode_groups import RATE_KINDS, finish_octet, no_zero_batch, rate_octet
+    freqs, counts, contents = rate_octet()
+    assert np.array_equal(freqs, S.quiet_model()) and counts.size == 8
+    seen = {"rare": 0, "quiet": 0, "bursts": 0}
+    for g, kind in enumerate(RATE_KINDS):
+        assert contents[g].size == counts[g]
+        rb = S.round_bytes(FMT_WORD, freqs, 12, contents[g], 8)
+        if kind.startswith("rare+"):
+            assert np.array_equal(contents[g][:8], S.rare_only(freqs, int(counts[g]), 60 + g)[:8])
+            assert S.windows(rb).max() == 96, (g, S.windows(rb).max())
+            seen["rare"] += 1
+        elif kind == "quiet":
+            assert np.all(contents[g] == S.COMMON)
+            assert S.longest_silence(rb) >= 1000, (g, S.longest_silence(rb))
+            seen["quiet"] += 1
+        else:
+            w = S.windows(rb)
+            assert w.max() == 96 and w.min() == 0, (g, w.min(), w.max())
+            seen["bursts"] += 1
+    assert min(seen.values()) >= 2, seen
+    assert len(set(counts.tolist())) >= 7 and len({int(c) >> 7 for c in counts}) >= 6  # (the groups finish in different iterations)
+    freqs, counts, contents = finish_octet()
+    rare, common = S.rare_and_common(freqs)
+    assert common == 0 and counts.tolist() == [128 * k for k in range(1, 9)]
+    for g in range(8):  # whole lines only; the symbols the coder sees last are rare: the state it leaves is large
+        assert np.all(np.isin(contents[g][:64], rare)) and S.windows(S.round_bytes(FMT_WORD, freqs, 12, contents[g], 8)).max() == 96
+    freqs, counts, contents = no_zero_batch()
+    assert freqs[0] == 0 and int(freqs.sum()) == 4096 and counts.size == 24
+    assert all(contents[k].size == counts[k] and not np.any(contents[k] == 0) for k in range(24))
+    assert len({int(c) >> 7 for c in counts[8:16]}) >= 4 and counts[8:16].max() >= 256

@@ -1,0 +1,445 @@
+"""Ragged batches of the reference's 8-way word layout CODED with eight streams per wave: k_encode_batch_word_groups, the
+kernel rans_amd_encode_batch[_ordered] launches on a context with RANS_AMD_OPT_BATCH_ENCODE_GROUPS = 1, and the hand-out
+order of the batch encoders (d_order).
+
+ENC_GROUP_ROWS names the kernel the library must report (tests/test_batch_encode_groups_host.py holds the rows to the names
+the launchers can report).  The helpers are tests/test_gpu_batch.py's: run_row checks the reported kernel, every stream byte
+for byte against the oracle's, each ending at its slot's end, and decodes the result.
+
+The coder works from a stream's last symbol to its first, so a wave's eight groups start together and finish at different
+times: a group is finalised (states, last blocks, index entry) right behind its last round and is dead from then on, while
+the wave's sixteen-round sequence -- full exec, LDS writes under the whole wave's ballot -- runs on for the others.  The
+shapes below are the smallest at which that can go wrong.
+
+Containers of two encodes are compared over the bytes of their streams: the 16-byte piece that holds a stream's first byte
+is stored whole, and what it holds below the stream is whatever the group's ring held (as with the wave kernels' flushes).
+Wall time on an MI355X: 12.7 s for the 21 cases of this file -- 6.0 s of it the `several` regime (81 925 calls of the oracle),
+2.7 s the captured graph's child process, 1.7 s the first case's setup and 0.6 s its call (they load the kernels), 0.7 s the
+`half` regime, 0.2 s the order test, 0.04 s and less for each of the others."""
+import os
+
+import numpy as np
+import pytest
+
+import _stream_rate as S
+from _oracle import FMT_WORD
+from test_gpu_batch import POISON, ROW, Batch, draw_lengths, mandatory_lengths, resident_waves, run_row
+
+OPT_BATCH_GROUPS = 5
+OPT_BATCH_ENCODE_GROUPS = 6
+ENC_GROUP_ROWS = [
+    {"id": "word-8-enc-groups", "fmt": FMT_WORD, "sb": 12, "K": 256, "ways": 8,
+     "decode": "k_decode_batch<word>", "encode": "k_encode_batch_word_groups"},
+]
+EROW = ENC_GROUP_ROWS[0]
+WAVE = "k_encode_batch<word>"
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the GPU box"
+    import ryg_rans_amd as R
+    ctx = R.Context(0)
+    ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 1)  # (only the new option)
+    off = R.Context(0)  # everything at its default: the wave-per-stream kernels
+    yield R, ctx, torch, off
+    off.close()
+    ctx.close()
+
+
+def draw_log_uniform(n_streams, max_len, seed):
+    """Log-uniform in [0, max_len]."""
+    rng = np.random.default_rng(seed)
+    return (np.exp(rng.random(n_streams) * np.log(max_len + 1.0)) - 1.0).astype(np.int64).clip(0, max_len).astype(np.uint32)
+
+
+# ---- inputs that the host test proves to sit at their bounds (tests/test_batch_encode_groups_host.py) -----------------
+def finish_octet():
+    """Counts 128 k, k = 1..8, bursts under 3841 + 255 x 1: every stream BEGINS with a run of 64 rare symbols -- the last the
+    coder sees --, so a finished group's state is large, and the common symbol (byte value 0, what a dead group is fed)
+    pushes it over its threshold: the dead group's lanes write into its ring while the others run on."""
+    freqs = S.rate_model()
+    counts = np.array([128 * k for k in range(1, 9)], dtype=np.uint32)
+    return freqs, counts, {g: S.bursts(freqs, int(counts[g]), 40 + g) for g in range(8)}
+
+
+RATE_KINDS = ("quiet", "rare+0", "bursts", "rare+1", "quiet", "bursts", "rare+2", "rare+0")
+RATE_COUNTS = (12288, 128 * 9 + 77, 1500, 128 * 20, 9001, 333, 641, 12288)
+
+
+def rate_octet():
+    """One wave under 4065 + 16 + 15 x 1: rare-only streams (96 bytes in every eight rounds: a block per check), quiet
+    streams (common-only: no block for a thousand rounds and more, then only the states) and bursts, at different lengths
+    -> (freqs, counts, {group: symbols})."""
+    freqs = S.quiet_model()
+    contents = {}
+    for g, (kind, n) in enumerate(zip(RATE_KINDS, RATE_COUNTS)):
+        if kind == "quiet":
+            contents[g] = S.common_only(freqs, n)
+        elif kind == "bursts":
+            contents[g] = S.bursts(freqs, n, 60 + g, lead=8 * g)
+        else:
+            contents[g] = S.rare_only(freqs, n, 60 + g, shift=int(kind[5:]))
+    return freqs, np.array(RATE_COUNTS, dtype=np.uint32), contents
+
+
+def no_zero_model():
+    """Byte value 0 has no record (frequency 0), every other value has: 3842 + 254 x 1.  dense256 is false: TRACK."""
+    f = np.ones(256, dtype=np.uint32)
+    f[0] = 0
+    f[1] = 4096 - 254
+    return f
+
+
+def no_zero_batch():
+    """24 streams (three octets) of uneven lengths, drawn from no_zero_model: groups park at different times, some from the start."""
+    freqs = no_zero_model()
+    counts = np.array([(37 * k * k + 11 * k) % 1500 for k in range(24)], dtype=np.uint32)
+    counts[5] = 0
+    return freqs, counts, {k: S.drawn(freqs, int(counts[k]), 80 + k) for k in range(24)}
+
+
+# ---- helpers --------------------------------------------------------------------------------------------------------
+def stream_mask(torch, n_bytes, offs, lens, n):
+    """True for the bytes of [offs[c], offs[c] + lens[c]), c < n."""
+    d = torch.zeros(n_bytes + 1, dtype=torch.int32, device="cuda")
+    o, ln = offs[:n].to(torch.int64), lens[:n].to(torch.int64)
+    d.index_add_(0, o, torch.ones(n, dtype=torch.int32, device="cuda"))
+    d.index_add_(0, o + ln, torch.full((n,), -1, dtype=torch.int32, device="cuda"))
+    return torch.cumsum(d[:n_bytes], 0) > 0
+
+
+def same_result(torch, a, b, n, what):
+    """Two (container, offsets, lengths) results: equal index entries, equal stream bytes."""
+    assert torch.equal(a[1][:n], b[1][:n]) and torch.equal(a[2][:n], b[2][:n]), (what, "index entries differ")
+    m = stream_mask(torch, a[0].numel(), a[1], a[2], n)
+    assert torch.equal(a[0][m], b[0][m]), (what, "stream bytes differ")
+
+
+def encode_poisoned(b, cx, gm, d_buf, d_sym, d_slot, cap, d_order=None, sentinel=None):
+    """encode_batch into a poison-filled container with 4096 guard bytes behind `cap`; sentinel: pre-filled index entries."""
+    torch = b.torch
+    d_out = torch.full((cap + 4096,), POISON, dtype=torch.uint8, device="cuda")
+    d_offs = torch.full((b.n,), 0 if sentinel is None else sentinel, dtype=torch.int64, device="cuda")
+    d_lens = torch.full((b.n,), 0 if sentinel is None else sentinel, dtype=torch.int32, device="cuda")
+    return cx.encode_batch(gm, d_buf, d_sym, b.d_counts, b.row["ways"], d_slot, d_out=d_out, d_offsets=d_offs, d_lengths=d_lens,
+                           out_cap=cap, d_order=d_order)
+
+
+OCTETS = {
+    "one-line-each": [128] * 8,
+    "boundaries": [0, 1, 7, 8, 9, 127, 128, 129],
+    "seven-dead-512-lines": [65536, 0, 0, 0, 0, 0, 0, 1],
+    "every-group-finishes-elsewhere": [128 * (g + 1) + 5 * g for g in range(8)],
+    "all-empty": [0] * 8,
+    "second-octet-of-one": [300] * 9,
+    "mandatory-and-200s": mandatory_lengths(8) + [200] * 7,
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(OCTETS))
+def test_single_octets(gpu, oracle, name):
+    """One or two octets: one line each and no tail; every line and tail boundary in one wave; seven groups dead for 512
+    lines while one keeps flushing; every group finishing in another iteration with another tail; eight empty streams
+    (32 bytes of flushed initial states each); a second octet of one stream; the mandatory lengths.  Each at sym_align 1
+    (every symbol a round at a time, byte loads) and 4."""
+    R, ctx, torch, _ = gpu
+    b = Batch(R, ctx, torch, oracle, EROW, np.array(OCTETS[name], dtype=np.uint32))
+    for align in (1, 4):
+        run_row(b, align)
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_finish_hazard(gpu, oracle):
+    """Every group finishes at a line boundary while others run on, and its free-running state emits (finish_octet): the
+    write lands where the stream's last word went.  Every stream equals the oracle's -- in particular its last bytes written,
+    the flushed states and the word below them (the stream's first 34 bytes)."""
+    R, ctx, torch, _ = gpu
+    freqs, counts, contents = finish_octet()
+    b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
+    cont, offs, lens = run_row(b, 4)[:3]
+    h, h_offs = cont.cpu().numpy(), offs.cpu().numpy()
+    for g in range(8):
+        a = int(h_offs[g])
+        assert b.lens[g] >= 34 and np.array_equal(h[a:a + 34], b.streams[g][:34]), ("states and last word of group", g)
+
+
+@pytest.mark.gpu
+def test_rate_extremes_in_one_wave(gpu, oracle):
+    """rate_octet: 96 bytes per eight rounds beside streams that flush no block for a thousand rounds, and bursts, at
+    different lengths, at sym_align 4 and 1."""
+    R, ctx, torch, _ = gpu
+    freqs, counts, contents = rate_octet()
+    b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
+    for align in (4, 1):
+        run_row(b, align)
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_no_false_e_model_from_parked_groups(gpu, oracle):
+    """A model without byte value 0, contents that never use it, uneven lengths: dead groups are fed zeros and read the
+    record of byte value 0, which must not reach the flags.  encode_status() is OK (run_row asks) and every stream is the
+    oracle's."""
+    R, ctx, torch, _ = gpu
+    freqs, counts, contents = no_zero_batch()
+    assert freqs[0] == 0 and all(not np.any(c == 0) for c in contents.values())
+    b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
+    for align in (4, 1):
+        run_row(b, align)
+
+
+@pytest.mark.gpu
+def test_true_e_model_is_reported_and_contained(gpu, oracle):
+    """The same batch with one symbol of one stream overwritten by 0 on the device: E_MODEL, as the default context reports
+    for the same batch; every stream of the other octets is the oracle's; nothing is written outside the container."""
+    R, ctx, torch, off = gpu
+    freqs, counts, contents = no_zero_batch()
+    b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
+    gm_off = off.model(FMT_WORD, freqs, 12)
+    d_buf, sym_offs, slot_offs = b.laid_out(4)
+    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
+    victim = 8 + int(np.argmax(counts[8:16]))  # (the longest stream of the second octet)
+    assert counts[victim] >= 256
+    bad = d_buf.clone()
+    bad[int(sym_offs[victim]) + int(counts[victim]) // 2] = 0
+    cap = int(slot_offs[-1])
+    for cx, gm, kernel in ((ctx, b.gm, EROW["encode"]), (off, gm_off, WAVE)):
+        cont, offs, lens = encode_poisoned(b, cx, gm, bad, d_sym, d_slot, cap)
+        assert cx.last_encode_kernel()[0] == kernel, cx.last_encode_kernel()
+        with pytest.raises(R.RansAmdError) as e:
+            cx.encode_status()
+        assert e.value.status == R.E_MODEL, kernel
+        h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
+        for c in range(b.n):
+            if c // 8 != victim // 8:
+                a = int(h_offs[c])
+                assert h_lens[c] == b.lens[c] and a + int(h_lens[c]) == int(slot_offs[c + 1]), (kernel, c)
+                assert np.array_equal(h[a:a + int(h_lens[c])], b.streams[c]), (kernel, "stream", c)
+        assert np.all(h[cap:] == POISON), (kernel, "written behind the container")
+    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, 8, d_slot)  # the next call succeeds
+    ctx.encode_status()
+
+
+@pytest.mark.gpu
+def test_order(gpu, oracle):
+    """17 streams.  No order, the reversed identity and batch_order's result give the same streams, offsets and lengths; an
+    order with one entry replaced by n_streams reports E_ARG, every stream still named is exact, and the stream that lost
+    its position keeps its slot's poison and its pre-filled index entries.  The same on the default context and on a
+    64-way batch, which report the wave kernel."""
+    R, ctx, torch, off = gpu
+    n = 17
+    counts = draw_lengths(n, 8, 23)
+    for cx, row in ((ctx, EROW), (off, ROW["word-8"]), (ctx, ROW["word-64"])):
+        b = Batch(R, cx, torch, oracle, row, counts)
+        d_buf, sym_offs, slot_offs = b.laid_out(4)
+        d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
+        cap = int(slot_offs[-1])
+        d_order = cx.batch_order(b.d_counts)
+        assert sorted(d_order.cpu().tolist()) == list(range(n))
+        results = []
+        for name, order in (("no order", None), ("reversed identity", b.dev(np.arange(n)[::-1], np.int32)), ("batch_order", d_order)):
+            res = encode_poisoned(b, cx, b.gm, d_buf, d_sym, d_slot, cap, d_order=order)
+            assert cx.last_encode_kernel()[0] == row["encode"] and cx.last_encode_placement() == 2, (name, cx.last_encode_kernel())
+            cx.encode_status()
+            b.check_streams(res[0].cpu().numpy(), res[1].cpu().numpy().astype(np.uint64), res[2].cpu().numpy().view(np.uint32),
+                            "%s, %s" % (row["id"], name))
+            assert np.all(res[0].cpu().numpy()[cap:] == POISON)
+            results.append(res)
+        same_result(torch, results[0], results[1], n, "reversed identity")
+        same_result(torch, results[0], results[2], n, "batch_order")
+        lost = int(np.argmax(counts))
+        order = np.arange(n)
+        order[lost] = n
+        cont, offs, lens = encode_poisoned(b, cx, b.gm, d_buf, d_sym, d_slot, cap, d_order=b.dev(order, np.int32), sentinel=-77)
+        assert cx.last_encode_kernel()[0] == row["encode"], cx.last_encode_kernel()
+        with pytest.raises(R.RansAmdError) as e:
+            cx.encode_status()
+        assert e.value.status == R.E_ARG, row["id"]
+        h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
+        for c in range(n):
+            lo, hi = int(slot_offs[c]), int(slot_offs[c + 1])
+            if c == lost:
+                assert h_offs[c] == -77 and h_lens[c] == -77, "the index entry of the stream without a position was written"
+                assert np.all(h[lo:hi] == POISON), "the slot of the stream without a position was written"
+            else:
+                ln = int(h_lens[c])
+                assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, (row["id"], c)
+                assert np.array_equal(h[hi - ln:hi], b.streams[c]), (row["id"], "stream", c)
+        assert np.all(h[cap:] == POISON)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regime", ["half", "several"])
+def test_half_and_several(gpu, oracle, regime):
+    """half: fewer octets than the launch has resident waves, lengths log-uniform up to 64 Ki with the mandatory ones.
+    several: at least 1.25 x as many octets as resident waves, so that waves come back for further claims and must reset
+    x, c, fb and their rings; lengths log-uniform up to 1024 (the oracle's side stays in seconds).  The last octet of each
+    is partial; sym_align = 4; then the same batch under batch_order's order: the same result."""
+    R, ctx, torch, _ = gpu
+    resident = resident_waves(torch)
+    if regime == "half":
+        octets = resident // 8
+        counts = draw_lengths(octets * 8 - 3, 8, 7)
+        assert 0 < octets < resident and set(mandatory_lengths(8)) <= set(counts.tolist())
+    else:
+        octets = resident + resident // 4 + 1
+        counts = draw_log_uniform(octets * 8 - 3, 1024, 9)
+        assert 4 * octets >= 5 * resident
+    b = Batch(R, ctx, torch, oracle, EROW, counts)
+    cont, offs, lens, d_buf, d_sym, d_slot, sym_offs, slot_offs = run_row(b, 4, with_oracle_container=False)
+    ordered = ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, 8, d_slot, d_order=ctx.batch_order(b.d_counts))
+    assert ctx.last_encode_kernel()[0] == EROW["encode"]
+    ctx.encode_status()
+    same_result(torch, (cont, offs, lens), ordered, b.n, "under batch_order")
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_bad_slots(gpu, oracle):
+    """test_batch_encode_rejects_bad_slots' construction on the 8-way shape with the option on: every slot 32 bytes larger
+    than its bound; a slot off 16 bytes on both sides (two streams), one a granule too small, one beyond out_cap -- each in
+    an octet with valid streams.  E_SPACE, the rejected slots keep their poison and get lengths 0, every other stream is
+    exact, the first 16 bytes of every accepted slot are still poison, nothing is written behind the container."""
+    R, ctx, torch, _ = gpu
+    counts = draw_lengths(400, 8, 71)
+    b = Batch(R, ctx, torch, oracle, EROW, counts)
+    d_buf, sym_offs, _ = b.laid_out(4)
+    bound = np.array([R.chunk_bound(FMT_WORD, int(c), 8) for c in counts], dtype=np.int64)
+    sizes = bound + 32
+    idx = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    cap = int(idx[-1])
+    big = np.nonzero(counts >= 1000)[0]
+    off16, past = int(big[0]), 399
+    small = int(big[(big > off16 + 2) & (big < past - 1)][0])
+    bad_idx = idx.copy()
+    bad_idx[off16 + 1] += 8
+    bad_idx[small] = bad_idx[small + 1] - (bound[small] - 16)
+    rejected = {off16, off16 + 1, small, past}
+    assert len(rejected) == 4
+    for c in rejected:  # (its octet holds valid streams as well)
+        assert any(k not in rejected for k in range(8 * (c // 8), min(8 * (c // 8) + 8, 400)))
+    d_out = torch.full((cap + 4096,), POISON, dtype=torch.uint8, device="cuda")
+    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, b.dev(sym_offs, np.int64), b.d_counts, 8, b.dev(bad_idx, np.int64), d_out=d_out,
+                                        out_cap=cap - 16)
+    assert ctx.last_encode_kernel()[0] == EROW["encode"], ctx.last_encode_kernel()
+    with pytest.raises(R.RansAmdError) as e:
+        ctx.encode_status()
+    assert e.value.status == R.E_SPACE
+    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
+    for c in range(b.n):
+        lo, hi = int(bad_idx[c]), int(bad_idx[c + 1])
+        if c in rejected:
+            assert h_lens[c] == 0 and int(h_offs[c]) == hi, c
+            if hi > lo:
+                assert np.all(h[lo:hi] == POISON), ("a rejected slot was written", c)
+        else:
+            ln = int(h_lens[c])
+            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, c
+            assert np.array_equal(h[hi - ln:hi], b.streams[c]), ("stream", c)
+            assert np.all(h[lo:lo + 16] == POISON), ("the head of a slot was written", c)
+    assert np.all(h[cap:] == POISON), "written behind the container"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rid,n_streams", [("word-64", 20), ("word-u16-64", 20), ("word-8", 7), ("byte-2", 40)])
+def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_streams):
+    """64-way, u16 symbols, fewer than eight 8-way streams and the byte format take the wave-per-stream kernels on the
+    context with the option on, and code right."""
+    R, ctx, torch, _ = gpu
+    row = ROW[rid]
+    assert row["encode"] != EROW["encode"]
+    b = Batch(R, ctx, torch, oracle, row, draw_lengths(n_streams, row["ways"], 29))
+    run_row(b, 4)  # (asserts the row's kernel names)
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_option_takes_zero_or_one(gpu, oracle):
+    """Any other value is E_ARG and changes nothing; 0 restores the wave-per-stream kernel, 1 the group kernel; the
+    decoder's option alone leaves the encoder where it was."""
+    R, ctx, torch, off = gpu
+    b = Batch(R, ctx, torch, oracle, EROW, np.array([300] * 9, dtype=np.uint32))
+    for bad in (2, -1):
+        with pytest.raises(R.RansAmdError) as e:
+            ctx.set_option(OPT_BATCH_ENCODE_GROUPS, bad)
+        assert e.value.status == R.E_ARG
+    run_row(b, 4)
+    ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 0)
+    try:
+        run_row(Batch(R, ctx, torch, oracle, ROW["word-8"], b.counts), 4)
+    finally:
+        ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 1)
+    run_row(b, 4)
+    off.set_option(OPT_BATCH_GROUPS, 1)
+    try:
+        d_buf, sym_offs, slot_offs = b.laid_out(4)
+        off.encode_batch(off.model(FMT_WORD, b.freqs, 12), d_buf, b.dev(sym_offs, np.int64), b.d_counts, 8, b.dev(slot_offs, np.int64))
+        assert off.last_encode_kernel()[0] == WAVE, off.last_encode_kernel()
+        off.encode_status()
+    finally:
+        off.set_option(OPT_BATCH_GROUPS, 0)
+
+
+_GRAPH_SCRIPT = r"""
+import os, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import numpy as np, torch
+import bench, ryg_rans_amd as R
+from test_gpu_batch import draw_lengths, POISON
+from test_gpu_batch_encode_groups import stream_mask
+ctx = R.Context(0)
+ctx.set_option(R.OPT_BATCH_ENCODE_GROUPS, 1)
+counts = draw_lengths(3000, 8, 61)
+n = counts.size
+sym_offs, slot_offs = R.batch_layout(counts, R.FMT_WORD, 8, 4)
+d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
+freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, 256), 4096)
+gm = ctx.model(R.FMT_WORD, freqs, 12)
+d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
+d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda(); d_slot = torch.from_numpy(slot_offs.astype(np.int64)).cuda()
+cap = int(slot_offs[-1])
+want, w_offs, w_lens = ctx.encode_batch(gm, d_syms, d_sym, d_counts, 8, d_slot)   # (outside the capture first)
+ctx.encode_status()
+assert ctx.last_encode_kernel()[0] == "k_encode_batch_word_groups", ctx.last_encode_kernel()
+back = torch.full_like(d_syms, POISON)
+ctx.decode_batch(gm, want, cap, w_offs, w_lens, d_sym, d_counts, 8, back)
+m = stream_mask(torch, cap, w_offs, w_lens, n)
+out = torch.full((cap,), POISON, dtype=torch.uint8, device="cuda")
+offs = torch.zeros(n, dtype=torch.int64, device="cuda"); lens = torch.zeros(n, dtype=torch.int32, device="cuda")
+s = torch.cuda.Stream()
+g = torch.cuda.CUDAGraph()
+with torch.cuda.stream(s):
+    with torch.cuda.graph(g, stream=s):
+        ctx.encode_batch(gm, d_syms, d_sym, d_counts, 8, d_slot, d_out=out, d_offsets=offs, d_lengths=lens, out_cap=cap)
+for _ in range(3):
+    out.fill_(POISON); offs.zero_(); lens.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    ctx.encode_status()
+    assert torch.equal(offs, w_offs[:n]) and torch.equal(lens, w_lens[:n]), "replay: index entries differ"
+    assert torch.equal(out[m], want[:cap][m]), "replay: stream bytes differ"
+assert ctx.last_encode_kernel()[0] == "k_encode_batch_word_groups"
+print("graph ok")
+"""
+
+
+@pytest.mark.gpu
+def test_group_batch_encode_in_a_captured_graph(tmp_path):
+    """One captured encode_batch of 3000 8-way streams with the option on: one eager call first, then three replays into a
+    poison-refilled container, each equal to the eager result (stream bytes, offsets, lengths), in a child process under a
+    time limit of its own.  Graph replay needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set
+    below that the test does not apply."""
+    import subprocess
+    import sys
+    q = os.environ.get("GPU_MAX_HW_QUEUES")
+    if q is not None and int(q) < 4:
+        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
+    script = tmp_path / "graph_batch_encode_groups.py"
+    script.write_text(_GRAPH_SCRIPT)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
