@@ -647,6 +647,11 @@ int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value)
             return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_ENCODE_GROUPS takes 0 (one stream per wave) or 1 (eight 8-way word streams per wave)");
         ctx->variant = value ? (ctx->variant | kVarBatchEncGroups) : (ctx->variant & ~kVarBatchEncGroups);
         return RANS_AMD_OK;
+    case RANS_AMD_OPT_BATCH_PAIRS:
+        if (value != 0 && value != 1)
+            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_PAIRS takes 0 (one stream per wave) or 1 (thirty-two 2-way byte streams per wave)");
+        ctx->variant = value ? (ctx->variant | kVarBatchPairs) : (ctx->variant & ~kVarBatchPairs);
+        return RANS_AMD_OK;
     default:
         return fail(RANS_AMD_E_ARG, "set_option: unknown option");
     }
@@ -1451,8 +1456,9 @@ int rans_amd_decode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
         RC_TRY(take_counter_slot(ctx, capture, s, dp)); // (n_streams fits the 32-bit counters: checked above)
         int dec_format = decoder_kernel_format(model);
         // byte format: the fused slot records where the model has them and they leave room for two blocks per CU (rans_amd_decode;
-        // every batch kernel is a wave-per-stream kernel)
-        if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12)
+        // the wave-per-stream kernels' tables -- the 32-streams-per-wave kernel of RANS_AMD_OPT_BATCH_PAIRS keeps cum2sym + records)
+        const bool pairs = (ctx->variant & kVarBatchPairs) && dec_format == RANS_AMD_FMT_BYTE && decode_batch_byte_pairs_applicable(dp);
+        if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12 && !pairs)
             dec_format = use_byte_fused_tables(dp, model);
         RC_TRY(launch_decoder(ctx, capture, s, launch_decode_batch, dec_format, dp));
     }

@@ -265,22 +265,27 @@ __device__ __forceinline__ rsrc_t marker_rsrc(const DecParams &p, uint32_t wave_
 // times in LDS (the tables there are dead by now), one thread folds them into the launch's record with two
 // atomics.  One pair per BLOCK: 8192 waves hammering two words cost ~80 us per launch (an L2 atomic unit
 // retires ~90 same-address atomics per microsecond).
-__device__ __forceinline__ void record_span(const DecParams &p, unsigned long long t_start, uint8_t *smem)
+// (tid: threadIdx.x, or the same number from the wave and the lane where a kernel has no register to keep it in)
+__device__ __forceinline__ void record_span(const DecParams &p, unsigned long long t_start, uint8_t *smem, uint32_t tid)
 {
     if (!p.span)
         return;
     unsigned long long *ends = reinterpret_cast<unsigned long long *>(smem);
     __syncthreads(); // every wave of the block is done with the tables
-    if ((threadIdx.x & 63u) == 0)
-        ends[threadIdx.x >> 6] = wall_clock64();
+    if ((tid & 63u) == 0)
+        ends[tid >> 6] = wall_clock64();
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (tid == 0) {
         unsigned long long last = 0;
         for (uint32_t w = 0; w < (blockDim.x >> 6); ++w)
             last = ends[w] > last ? ends[w] : last;
         atomicMax(p.span, ~t_start);
         atomicMax(p.span + 1, last);
     }
+}
+__device__ __forceinline__ void record_span(const DecParams &p, unsigned long long t_start, uint8_t *smem)
+{
+    record_span(p, t_start, smem, threadIdx.x);
 }
 
 // byte `kSymByte` of `raw` goes to byte J of acc, the other bytes of acc stay

@@ -23,7 +23,8 @@
 // Chunks of a multiple of 4 symbols -- the output is stored in dwords -- (the launcher hands everything else to the lane
 // kernel); a ragged last chunk sends the input's last octet one round at a time; what a chunk size off 128 leaves goes four rounds, then one round
 // at a time.  The mirror image, the 8-way encoder: encode_groups.hip.  The ragged form for rans_amd_decode_batch -- eight
-// STREAMS per wave, each with its own symbol count -- is k_decode_batch_word_groups, behind the uniform kernel.
+// STREAMS per wave, each with its own symbol count -- is k_decode_batch_word_groups, behind the uniform kernel; the 2-way byte
+// layout's, thirty-two streams per wave, is k_decode_batch_byte_pairs behind k_decode_byte_pairs.
 //
 // No MFMA: integer, table-driven, serial per state.
 
@@ -1010,6 +1011,291 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_byte_pairs(const DecP
         atomicAdd(p.err_count, (unsigned long long)nbad);
 }
 
+// ---------------------------------------------------------------------------
+// k_decode_batch_byte_pairs -- the ragged form of k_decode_byte_pairs (rans_amd_decode_batch under
+// RANS_AMD_OPT_BATCH_PAIRS): a wave's thirty-two pairs hold thirty-two STREAMS, each with its own symbol count and its own
+// output address.  The unit of work is one wave-load of the hand-out order: lane 2 g + i holds state i of the stream at
+// position 32 w + g -- stream order[32 w + g], or 32 w + g without an order; a position at or past nchunks has no stream.
+// The rounds, the 68-byte ring rows and their refills, the pair interleave and the quad gather are k_decode_byte_pairs';
+// what is new is that the pairs' loop counts differ, as the groups' do in k_decode_batch_word_groups:
+//   * the wave runs the 64-round line body max_g(blocks_g) times with FULL exec, blocks_g = count_g >> 7 whole 128-byte
+//     lines.  The sequence sets exec = -1 itself and its DPP moves read the pair's other lane, so a pair that has run out of
+//     lines cannot be masked off: it is PARKED.  There is no per-pair ballot to zero here (a lane's byte count comes from
+//     its own two compares), so a parked pair's cursor does move; instead
+//       - its checkpoint() is gated by q < blocks_g: it writes no ring byte and issues no global load, and its ring, pend,
+//         ld, left and thr stay exactly what they were when it parked -- it still owes its tail;
+//       - its state x and its cursor cur are put back from copies behind every line (two selects);
+//       - its line is not stored.
+//     A parked pair keeps running the rounds on whatever its state becomes, and that is safe: a round reads only LDS and
+//     writes nothing but the pair's own registers.  It reads cum2sym at x & mask, inside table 0 whatever x is; a record at
+//     rec + 8 s with s a byte of cum2sym, i.e. a symbol of the model, inside table 1 for every table the model builder
+//     makes; and the ring at ring + (position & 63) and one byte further, inside the pair's own 68-byte row whatever the
+//     cursor is.  It reads no global memory: refills are checkpoint()'s, and that is gated.  The same holds for a pair
+//     without a stream or with a rejected one, which is parked from the start and whose ring is never filled from memory
+//     (b0, b1 and pend are zero, left = 0).
+//   * behind the common loop every pair decodes its count_g - 128 blocks_g remaining symbols one round at a time, lanes
+//     without a symbol sitting out, a byte store per lane (the uniform kernel's path for a ragged last chunk).
+// Every lane addresses its output in 64 bits (out_syms is 64-bit, and the 32 streams of a wave may lie anywhere in it).  A
+// stream whose output is not 4-byte aligned takes the round-by-round path for all of its symbols (blocks_g = 0).
+// Index entries are the caller's data and checked per pair as k_decode_batch_word_groups checks them per group: the order
+// entry names a stream, the stream holds its two states and lies inside the container, the symbol range lies inside
+// [0, out_syms); no parity rule on the offset (the byte format's unit is 1).  A stream that fails is counted once, by the
+// pair's even lane; nothing of it is fetched, nothing stored.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(const DecParams p)
+{
+    using Tr = FmtTraits<FMT_BYTE>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const unsigned long long t_start = p.span ? wall_clock64() : 0ull;
+    const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // cum2sym u8[M]
+    const uint32_t t1_bytes = (p.table1_bytes + 15u) & ~15u; // {freq, start}[nsyms]
+    {
+        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.table0);
+        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
+        for (uint32_t i = threadIdx.x; i < t0_bytes / 16u; i += blockDim.x)
+            l0[i] = g0[i];
+        const uint4 *g1 = reinterpret_cast<const uint4 *>(p.table1);
+        uint4 *l1 = reinterpret_cast<uint4 *>(smem + t0_bytes);
+        for (uint32_t i = threadIdx.x; i < t1_bytes / 16u; i += blockDim.x)
+            l1[i] = g1[i];
+    }
+    __syncthreads();
+    if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never decode on a wrong assumption
+        if (threadIdx.x == 0)
+            atomicAdd(p.err_count, 1ull << 32);
+        return;
+    }
+    if (p.work_counter_reset && blockIdx.x == 0 && threadIdx.x < kWorkPools)
+        p.work_counter_reset[threadIdx.x * kWorkPoolStride] = 0u;
+    if (p.span_reset && blockIdx.x == 0 && threadIdx.x < 2)
+        p.span_reset[threadIdx.x] = 0ull;
+
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t ring_c = t0_bytes + t1_bytes + wave * kPairWaveLds + (lane >> 1) * kPairRow; // (as in k_decode_byte_pairs, the constants as well)
+    uint32_t ring = ring_c, maskv = (1u << p.scale_bits) - 1u, sbv = p.scale_bits, rec = t0_bytes;
+    uint32_t l23 = 1u << 23, l15 = 1u << 15;
+    uint32_t sel_p = (lane & 1u) ? 0x03070206u : 0x05010400u;
+    uint32_t ring_i = ring_c + 16u * (lane & 1u); // where this lane's 16 bytes of a block go
+    asm volatile("v_mov_b32 %0, %0" : "+v"(ring_i));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(ring));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(maskv));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(sbv));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(rec));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(l23));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(l15));
+
+    const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
+    const uint64_t glo = cbase & ~uint64_t(15), glimit = (cbase + p.container_bytes + 15u) & ~uint64_t(15);
+    const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 31u) >> 5); // wave-loads, one per claim (the last one may hold fewer than 32
+                                                                         // streams); stream indices are 32-bit
+
+    auto load16 = [&](uint64_t a) -> u32x4 { // 16 bytes of the container, zeros beyond its granules
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (a >= glo && a < glimit)
+            v = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(a));
+        return v;
+    };
+    // over the 32 pairs (v is the same in a pair's lanes): a butterfly over lane ^ 2, 4, 8, 16 inside each half of the wave
+    // (ds_swizzle in bit-mask mode: and 0x1f, or 0, xor d -- no address register), then the larger of the two halves
+    auto wave_max = [&](uint32_t v) -> uint32_t {
+        uint32_t t;
+        t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x081f);
+        v = t > v ? t : v;
+        t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x101f);
+        v = t > v ? t : v;
+        t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x201f);
+        v = t > v ? t : v;
+        t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401f);
+        v = t > v ? t : v;
+        const uint32_t lo = __builtin_amdgcn_readlane(v, 0), hi = __builtin_amdgcn_readlane(v, 32);
+        return lo > hi ? lo : hi;
+    };
+    // the lane number, worked out where it is needed: what follows from it -- index addresses, shuffle addresses, 16 t -- is
+    // then worked out per claim as well and not kept in registers across the line loop (volatile: not hoisted)
+    auto lane_now = [&]() -> uint32_t {
+        uint32_t l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return l;
+    };
+
+    uint32_t nbad = 0;
+    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
+    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
+    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
+    const uint32_t pool = blockIdx.x % npools;
+    for (;;) {
+        uint64_t load; // (handed out as in k_decode_byte_pairs: the pooled counter, or a static stride without one)
+        if (p.work_counter) {
+            uint32_t got = 0;
+            if (lane == 0)
+                got = atomicAdd(p.work_counter + pool * kWorkPoolStride, 1u);
+            load = (uint64_t)uniform(got) * npools + pool;
+        } else {
+            load = uniform64(claim_v);
+            claim_v += total_waves;
+        }
+        if ((load >> 32) != 0 || (uint32_t)load >= loads) // (scalar compares)
+            break;
+        // ---- this pair's stream: its index entries, all of them the caller's data
+        const uint32_t ln = lane_now();
+        const uint32_t g = ln >> 1, i = ln & 1u;
+        const uint64_t pos = load * 32u + g;
+        const bool exists = pos < p.nchunks;
+        uint64_t s = pos;
+        if (exists && p.order)
+            s = p.order[pos];
+        bool valid = exists && s < p.nchunks;
+        uint64_t off = 0, first = 0;
+        uint32_t len = 0, count = 0;
+        if (valid) {
+            off = p.offsets[s];
+            len = p.lengths[s];
+            first = p.sym_offsets[s];
+            count = p.sym_counts[s];
+        }
+        valid = valid && len >= 2u * 4u && off <= p.container_bytes && len <= p.container_bytes - off && first <= p.out_syms &&
+                count <= p.out_syms - first;
+        if (exists && !valid && i == 0)
+            nbad++;
+        const uint64_t src = cbase + (valid ? off : 0u);
+        uint32_t x = Tr::kL;
+        if (valid) // RansDecInit order: state 0 first (main.cpp:261-262)
+            x = reinterpret_cast<const uint32_t RANS_GLOBAL *>(src)[i];
+        // the ring, its positions and its refills: k_decode_byte_pairs' (a pair without a valid stream fetches nothing)
+        const uint64_t abase = src & ~uint64_t(kPairBlock - 1u);
+        const uint32_t start = (uint32_t)(src - abase) + 2u * 4u; // < 40
+        uint32_t cur = start;
+        uint64_t ld = abase + 16u * i;
+        u32x4 b0 = {0u, 0u, 0u, 0u}, b1 = b0, pend = b0;
+        if (valid) {
+            b0 = load16(ld);
+            b1 = load16(ld + kPairBlock);
+            pend = load16(ld + 2u * kPairBlock);
+        }
+        ld += 3u * kPairBlock;
+        uint32_t left = 0;
+        if (valid && ld < glimit) {
+            const uint64_t pieces = (glimit - ld + (kPairBlock - 1u)) / kPairBlock;
+            left = pieces < 0x7fffffffu ? (uint32_t)pieces : 0x7fffffffu;
+        }
+        auto put = [&](uint32_t at, const u32x4 &v) { // (rows are 4-byte aligned: four dword writes)
+            RANS_LDS uint32_t *d = reinterpret_cast<RANS_LDS uint32_t *>((uintptr_t)(ring_i + at));
+            d[0] = v.x;
+            d[1] = v.y;
+            d[2] = v.z;
+            d[3] = v.w;
+            if (at == 0 && ring_i == ring) // (the even lane)
+                *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(ring + kPairRing)) = (uint8_t)v.x;
+        };
+        put(0, b0);
+        put(kPairBlock, b1);
+        uint32_t thr = kPairBlock;
+        auto checkpoint = [&](bool live) { // live: the pair runs (the same for both of its lanes); a parked pair's ring stays as it is
+            if (live && cur >= thr) {
+                put(~thr & kPairBlock, pend);
+                thr += kPairBlock;
+                if (left) {
+                    pend = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(ld));
+                    left--;
+                }
+                ld += kPairBlock;
+            }
+        };
+        checkpoint(valid); // the states may end in block 1
+        const uint32_t end = len + (start - 2u * 4u); // the cursor at the end of the stream
+
+        // ---- the pair's own counts: whole lines through the common loop, the rest a round at a time
+        const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + first; // (valid: [dst, dst + count) lies inside the output)
+        const uint32_t blocks = (valid && (dst & 3u) == 0) ? count >> 7 : 0u;
+        const uint32_t tail = valid ? count - (blocks << 7) : 0u;
+        const uint32_t max_blocks = wave_max(blocks), max_tail = wave_max(tail);
+        // the quad's two streams A = g & ~1 and B = A + 1, as lane t = lane & 3 of the quad addresses them: 16 t bytes in
+        // (ds_bpermute with the byte address of the lane to read: __shfl keeps a lane number of its own in a register)
+        auto from = [&](uint32_t v, int addr) -> uint32_t { return (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v); };
+        const int lane_a = (int)(4u * (ln & ~3u)), lane_b = (int)(4u * (ln | 2u));
+        const uint32_t blocks_a = from(blocks, lane_a), blocks_b = from(blocks, lane_b);
+        uint64_t line_a = ((uint64_t)from((uint32_t)(dst >> 32), lane_a) << 32 | from((uint32_t)dst, lane_a)) + 16u * (ln & 3u);
+        uint64_t line_b = ((uint64_t)from((uint32_t)(dst >> 32), lane_b) << 32 | from((uint32_t)dst, lane_b)) + 16u * (ln & 3u);
+        const bool pair_b = (ln & 2u) != 0; // this lane's own stream is the quad's B
+        bool run = false;
+        auto sixteen = [&]() -> u32x4 { // 16 rounds -> this lane's 16 of the pair's 32 bytes (k_decode_byte_pairs')
+            uint32_t a0, a1, a2, a3;
+            checkpoint(run);
+            decode_pairs_8rounds(x, cur, a0, a1, maskv, sbv, rec, l23, l15, ring);
+            checkpoint(run);
+            decode_pairs_8rounds(x, cur, a2, a3, maskv, sbv, rec, l23, l15, ring);
+            return pair_lines(a0, a1, a2, a3, sel_p);
+        };
+        for (uint32_t q = 0; q < max_blocks; ++q) {
+            run = pair_b ? q < blocks_b : q < blocks_a; // q < this pair's blocks
+            const uint32_t x_keep = x, cur_keep = cur;
+            const u32x4 v0 = sixteen();
+            const u32x4 v1 = sixteen();
+            const u32x4 v2 = sixteen();
+            const u32x4 v3 = sixteen();
+            // a quad writes 64 contiguous bytes per instruction, a stream's line with two instructions back to back; the
+            // gathers run under full exec (their DPP moves read all four lanes), the stores under q < blocks of the stream
+            // they belong to.  Plain stores: a stream starts anywhere on the 4-byte grid, so its lines straddle the memory's
+            // -- the case in which k_decode_byte_pairs leaves it to L2 to put the pieces together.
+            const u32x4 ha0 = quad_half<0>(v0, v1), ha1 = quad_half<0>(v2, v3);
+            if (q < blocks_a) {
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_a) = ha0;
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_a + 64u) = ha1;
+            }
+            const u32x4 hb0 = quad_half<1>(v0, v1), hb1 = quad_half<1>(v2, v3);
+            if (q < blocks_b) {
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_b) = hb0;
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_b + 64u) = hb1;
+            }
+            line_a += 128u; // (past a stream's last line the address is not used any more)
+            line_b += 128u;
+            x = run ? x : x_keep;
+            cur = run ? cur : cur_keep;
+        }
+        // ---- count - 128 blocks symbols (all of them where the output is not 4-byte aligned): one round at a time, compiler-scheduled
+        // (this pair's address from the quad's: the lines have moved on by max_blocks, the pair's tail follows its own blocks)
+        const uint32_t lt = lane_now();
+        const uint32_t gt = lt >> 1, it = lt & 1u;
+        const bool tail_b = (lt & 2u) != 0;
+        const int lane_o = (int)(4u * (lt ^ 1u)); // the pair's other lane
+        const uint64_t tail_dst = (tail_b ? line_b : line_a) - 16u * (lt & 3u) - ((uint64_t)(max_blocks - (tail_b ? blocks_b : blocks_a)) << 7);
+        const uint32_t tail_rounds = (uint32_t)(((uint64_t)max_tail + 1u) >> 1);
+        for (uint32_t rr = 0; rr < tail_rounds; ++rr) {
+            if ((rr & 7u) == 0)
+                checkpoint(valid);
+            const uint32_t s0 = rr << 1; // < max_tail
+            const bool active = s0 < tail && it < tail - s0;
+            uint32_t sy = 0, n = 0;
+            if (active) {
+                const uint32_t cf = x & maskv; // rans_byte.h:125-128 (get), :291-298 (advance)
+                sy = *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)cf);
+                const u32x2 fr = *reinterpret_cast<RANS_LDS const u32x2 *>((uintptr_t)(rec + 8u * sy));
+                x = (fr.x & 0xffffffu) * ((x >> sbv) & 0xffffffu) + cf - fr.y;
+                n = (uint32_t)(x < l23) + (uint32_t)(x < l15); // rans_byte.h:307-318: state 0's bytes first
+            }
+            const uint32_t n_other = from(n, lane_o);
+            const uint32_t at = cur + (it ? n_other : 0u);
+            cur += n + n_other;
+            if (n >= 1u)
+                x = (x << 8) | *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)(ring + (at & 63u)));
+            if (n >= 2u)
+                x = (x << 8) | *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)(ring + ((at + 1u) & 63u)));
+            if (active)
+                *reinterpret_cast<uint8_t RANS_GLOBAL *>(tail_dst + s0 + it) = (uint8_t)sy;
+        }
+        // integrity: both states back at L, the cursor exactly at the end of the stream
+        const bool bad = valid && (x != Tr::kL || cur != end);
+        const uint64_t bm = __builtin_amdgcn_ballot_w64(bad);
+        if (it == 0 && ((bm >> (2u * gt)) & 3u) != 0)
+            nbad++;
+    }
+    if (nbad)
+        atomicAdd(p.err_count, (unsigned long long)nbad);
+    record_span(p, t_start, smem, wave * 64u + lane_now());
+}
+
 } // namespace
 
 // (a ragged last chunk included: its octet goes one round at a time and is handed out first)
@@ -1087,6 +1373,33 @@ hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t
     const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
     if (name)
         *name = "k_decode_byte_pairs";
+    RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
+    return hipGetLastError();
+}
+
+// The ragged form: byte format over u8 symbols with the cum2sym tables (the caller has checked the format: the fused slot
+// records are another kernel format), from 32 streams on; any symbol count, any output address.
+bool decode_batch_byte_pairs_applicable(const DecParams &p)
+{
+    const size_t tables = (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u);
+    return p.n_ways == 2 && p.sym_bytes == 1 && p.scale_bits >= 8 && p.scale_bits <= 16 && p.nchunks >= 32 && p.sym_offsets && p.sym_counts &&
+           !p.trace && tables + (size_t)(kGrpThreads / 64) * kPairWaveLds <= 160u * 1024u;
+}
+
+hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **pair_batch_kernel)
+{
+    const size_t tables = (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u);
+    const size_t lds = tables + (size_t)(kGrpThreads / 64) * kPairWaveLds;
+    auto kern = k_decode_batch_byte_pairs;
+    static std::atomic<uint64_t> lds_ok{0};
+    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
+        return e;
+    const uint32_t per_cu = 2u * lds <= 160u * 1024u ? 2u : 1u;
+    const uint64_t want_blocks = ((p.nchunks + 31u) / 32u + kGrpThreads / 64 - 1) / (kGrpThreads / 64); // one wave-load per wave
+    const uint64_t cap = (uint64_t)num_cus * per_cu;
+    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
+    if (pair_batch_kernel)
+        *pair_batch_kernel = "k_decode_batch_byte_pairs";
     RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
     return hipGetLastError();
 }

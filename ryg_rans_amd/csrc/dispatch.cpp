@@ -32,13 +32,16 @@ hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_
 
 // ragged batches: the wave-per-stream kernels, whatever the interleave -- unless the context asked for eight streams per wave
 // (RANS_AMD_OPT_BATCH_GROUPS for the decoder, RANS_AMD_OPT_BATCH_ENCODE_GROUPS for the encoder) and the batch is the
-// reference's 8-way word layout over u8 symbols, from eight streams on: the ragged kernels of decode_groups.hip and
-// encode_groups.hip.  Every other shape takes the wave kernels under those options as well (the ragged forms of
-// k_decode_byte_pairs and of the lane kernels are later work).
+// reference's 8-way word layout over u8 symbols, from eight streams on, or for thirty-two streams per wave
+// (RANS_AMD_OPT_BATCH_PAIRS, the decoder's alone) and the batch is the reference's 2-way byte layout over u8 symbols, from
+// 32 streams on: the ragged kernels of decode_groups.hip and encode_groups.hip.  Every other shape takes the wave kernels
+// under those options as well (the ragged forms of the lane kernels and of the 2-way byte ENCODER are later work).
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
 {
     if ((p.variant & kVarBatchGroups) && format == (int)RANS_AMD_FMT_WORD && decode_batch_word_groups_applicable(p))
         return launch_decode_batch_word_groups(p, num_cus, stream, batch_kernel);
+    if ((p.variant & kVarBatchPairs) && format == (int)RANS_AMD_FMT_BYTE && decode_batch_byte_pairs_applicable(p))
+        return launch_decode_batch_byte_pairs(p, num_cus, stream, batch_kernel);
     return launch_decode_batch_wave(format, p, num_cus, stream, batch_kernel);
 }
 

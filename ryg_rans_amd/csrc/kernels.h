@@ -31,6 +31,7 @@ constexpr uint32_t kVarDualAlways = 16u;   // ... two chunks per wave (k_decode_
                                            //     they leave no room for a second block per CU
 constexpr uint32_t kVarBatchGroups = 32u;  // ragged batches of the 8-way word layout: eight streams per wave (k_decode_batch_word_groups)
 constexpr uint32_t kVarBatchEncGroups = 64u; // ... in the ENCODER as well (k_encode_batch_word_groups)
+constexpr uint32_t kVarBatchPairs = 128u;    // ragged batches of the 2-way byte layout: 32 streams per wave (k_decode_batch_byte_pairs)
 
 constexpr uint32_t kWorkPools = 8;       // chunk hand-out counters per launch (one per XCD)
 constexpr uint32_t kWorkPoolStride = 16; // in uint32: every counter on its own 64-byte line
@@ -239,7 +240,8 @@ uint32_t layout_blocks(uint64_t nchunks); // blocks (and block_sums entries) lau
 hipError_t launch_compact(const CompactParams &p, int num_cus, hipStream_t stream);
 // Ragged batches (rans_amd_decode_batch / rans_amd_encode_batch[_ordered]): one stream per wave, whatever the interleave -- but
 // for the 8-way word layout eight streams per wave, in the decoder under kVarBatchGroups and in the encoder under
-// kVarBatchEncGroups; *batch_kernel receives the name of the kernel that was launched.  `format` is the kernel-side format
+// kVarBatchEncGroups, and for the 2-way byte layout 32 streams per wave in the decoder under kVarBatchPairs; *batch_kernel
+// receives the name of the kernel that was launched.  `format` is the kernel-side format
 // number.
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
 hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);

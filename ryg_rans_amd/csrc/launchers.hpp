@@ -82,6 +82,11 @@ hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipS
 // 32 chunks per wave, the byte format's 2-way layout over u8 symbols (cum2sym tables), same file
 bool decode_byte_pairs_applicable(const DecParams &p);
 hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **name);
+// ... its ragged form (rans_amd_decode_batch under kVarBatchPairs): 32 STREAMS per wave, each with its own symbol count and
+// output address, from 32 streams on, the tables and the wave rings inside the CU's 160 KiB of LDS; the name goes to
+// *pair_batch_kernel
+bool decode_batch_byte_pairs_applicable(const DecParams &p);
+hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **pair_batch_kernel);
 
 // the 8-way word layout's encoder, eight chunks per wave (encode_groups.hip): chunks of a multiple of 4 u8 symbols, the
 // three-kernel placement, the slot layout or sized slots (no fused placement)

@@ -1,0 +1,132 @@
+"""Ragged batches with thirty-two 2-way byte streams per wave (RANS_AMD_OPT_BATCH_PAIRS), the part that needs no GPU: the name
+test of the pair batch kernel, the option's constant, and the proof that the rate inputs of tests/test_gpu_batch_pairs.py
+reach the bounds that file claims.
+
+test_no_pair_batch_kernel_without_a_row: the launcher of the kernel that packs 32 ragged byte streams into a wave reports
+its kernel through an out-parameter spelled `*pair_batch_kernel = ...;` -- a sixth spelling beside `*name = ...;`
+(tests/test_gpu_kernel_matrix.py), `*batch_kernel = ...;` (tests/test_batch_host.py), `*models_batch_kernel = ...;`
+(tests/test_batch_models_host.py), `*group_batch_kernel = ...;` (tests/test_batch_groups_host.py) and
+`*group_batch_enc_kernel = ...;` (tests/test_batch_encode_groups_host.py), invisible to those five tests, which anchor on
+the `*`.  Every literal of such a statement in ryg_rans_amd/csrc/*.hip must be the decode name of a row of PAIR_ROWS in
+tests/test_gpu_batch_pairs.py, and PAIR_ROWS must name no decoder the sources do not contain."""
+import glob
+import os
+import re
+
+import numpy as np
+
+import _stream_rate as S
+import ryg_rans_amd as R
+from _oracle import FMT_BYTE
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
+_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
+
+
+def source_pair_batch_kernel_names(csrc=CSRC):
+    """Every string literal of a statement `*pair_batch_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
+    names, sites = set(), 0
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        for m in re.finditer(r"\*pair_batch_kernel\s*=\s*([^;]*);", open(path).read()):
+            sites += 1
+            names.update(_LITERAL.findall(m.group(1)))
+    return names, sites
+
+
+def test_no_pair_batch_kernel_without_a_row():
+    from test_gpu_batch_pairs import PAIR_ROWS
+    names, sites = source_pair_batch_kernel_names()
+    assert sites >= 1, sites
+    assert "k_decode_batch_byte_pairs" in names
+    rows = {r["decode"] for r in PAIR_ROWS}
+    assert names == rows, ("kernels no row of PAIR_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
+    assert all(r["ways"] == 2 and r["fmt"] == FMT_BYTE and r["encode"] == "k_encode_batch<byte>" for r in PAIR_ROWS)
+    assert sorted((r["sb"], r["K"]) for r in PAIR_ROWS) == [(8, 256), (10, 64), (12, 256), (14, 256), (16, 256)]
+    # disjoint from what the five other spellings' scans find
+    from test_batch_encode_groups_host import source_group_batch_enc_kernel_names
+    from test_batch_groups_host import source_group_batch_kernel_names
+    from test_batch_host import source_batch_kernel_names
+    from test_batch_models_host import source_models_batch_kernel_names
+    from test_gpu_kernel_matrix import source_kernel_names
+    for scan in (source_kernel_names, source_batch_kernel_names, source_models_batch_kernel_names, source_group_batch_kernel_names,
+                 source_group_batch_enc_kernel_names):
+        assert not names & scan()[0], scan.__name__
+    # the check has teeth: without its rows the kernel is reported missing
+    less = {r["decode"] for r in PAIR_ROWS if not r["id"].startswith("byte-2-pairs")}
+    assert "k_decode_batch_byte_pairs" in names - less
+
+
+def test_batch_pairs_option_constant():
+    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
+    m = re.search(r"RANS_AMD_OPT_BATCH_PAIRS\s*=\s*(\d+)", header)
+    assert m and int(m.group(1)) == 7
+    assert R.OPT_BATCH_PAIRS == 7
+    # options 0..6 are where they were, and the version has not moved (additions only)
+    for name, value in (("LANE_KERNELS", 0), ("LANE_FUSED_PLACEMENT", 1), ("FUSED_PLACEMENT", 2), ("DUAL_DECODE", 3),
+                        ("ENC_SCRATCH_RING", 4), ("BATCH_GROUPS", 5), ("BATCH_ENCODE_GROUPS", 6)):
+        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % name, header)
+        assert m and int(m.group(1)) == value, name
+        assert getattr(R, "OPT_" + name) == value, name
+    assert re.search(r"#define\s+RANS_AMD_VERSION\s+600\b", header)
+    # (a NULL context is refused before the option is looked at; the values need a context: tests/test_gpu_batch_pairs.py)
+    assert R.lib().rans_amd_ctx_set_option(None, 7, 1) == R.E_ARG
+    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+
+
+def test_rate_inputs_reach_the_rings_bound():
+    """The 16-bit model of 255 frequency-1 symbols and one common symbol (tests/test_gpu_rate_extremes.py b_case's).
+      * A state in [2^23, 2^31) that meets a frequency-1 symbol becomes x >> 16 < 2^15 and takes two bytes, in every round: every
+        frequency-1-only stream of the GPU file with at least eight rounds has a window of eight rounds that takes 32 bytes,
+        what one refill brings -- every window does.
+      * A common symbol costs log2(65536 / 65281) = 0.0056 bits: a state takes a byte every 1400 rounds or so.  The common-only
+        streams of the 64-stream batch are 384 rounds at the most and take nothing at all -- a cursor that never moves beside
+        quad-mates at the bound --, and the 65536-symbol one of the single wave-load has 1000 and more consecutive silent
+        rounds.  (No stream of fewer than 1000 rounds can show a thousand silent ones: the thousand rounds are the long
+        stream's.)
+    The inputs are the GPU file's own generators."""
+    import test_gpu_batch_pairs as G
+    assert G.OPT_BATCH_PAIRS == R.OPT_BATCH_PAIRS and G.OPT_BATCH_GROUPS == R.OPT_BATCH_GROUPS  # (the option these inputs are decoded under)
+    assert 16 in G.RATE_BITS and G.RATE_ROW[16]["sb"] == 16
+    freqs, counts, contents, phases = G.rate_batch(16)
+    b_freqs = np.ones(256, dtype=np.uint32)
+    b_freqs[S.COMMON] = (1 << 16) - 255
+    assert np.array_equal(freqs, b_freqs) and int(freqs.sum()) == 1 << 16
+    assert counts.size == G.RATE_STREAMS == 64 and sorted(p % 64 for p in phases) == list(range(64))
+    assert set(counts.tolist()) == {128 * b + t for b in (0, 1, 5) for t in (0, 1, 77, 127)}
+    kinds = [G.rate_kind(k) for k in range(64)]
+    assert all((kinds[k] == "common") == (k % 3 == 2) for k in range(64))
+    # every count meets both kinds; in every quad both streams' kinds and counts are on record
+    assert {(kinds[k], int(counts[k])) for k in range(64)} == {(kd, c) for kd in ("rare", "common") for c in set(counts.tolist())}
+    rare_long = 0
+    for k in range(64):
+        rb = S.round_bytes(FMT_BYTE, freqs, 16, contents[k], 2)
+        n = int(counts[k])
+        if kinds[k] == "rare":
+            assert np.all(np.isin(contents[k], np.nonzero(freqs == 1)[0]))
+            if n // 2 >= 8:
+                w = S.windows(rb[:n // 2])
+                assert w.size >= 1 and w.max() == 32 and w.min() == 32, (k, n, w.min(), w.max())
+                rare_long += 1
+        else:
+            assert np.all(contents[k] == S.COMMON)
+            assert rb.sum() == 0 and S.longest_silence(rb) == (n + 1) // 2, (k, n, int(rb.sum()))
+    assert rare_long >= 20, rare_long
+    for name in G.RATE_WAVES:
+        freqs, counts, contents, phases = G.rate_wave(16, name)
+        w_kinds = G.RATE_WAVES[name][1]
+        assert counts.size == 32 and len(set(p % 64 for p in phases)) == 32
+        for k in range(32):
+            rb = S.round_bytes(FMT_BYTE, freqs, 16, contents[k], 2)
+            n = int(counts[k])
+            if w_kinds[k] == "rare":
+                if n // 2 >= 8:
+                    w = S.windows(rb[:n // 2])
+                    assert w.max() == 32 and w.min() == 32, (name, k, n)
+            elif n >= 2000:
+                assert S.longest_silence(rb) >= 1000, (name, k, S.longest_silence(rb))
+            else:
+                assert rb.sum() == 0, (name, k)
+    # the stalled cursor really is in the file: a common-only stream of 2000 symbols and more
+    assert any(c >= 2000 and kd == "common" for cs, kds in G.RATE_WAVES.values() for c, kd in zip(cs, kds))
