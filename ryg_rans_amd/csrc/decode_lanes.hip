@@ -101,8 +101,11 @@ __device__ __forceinline__ void lane_renorm(typename FmtTraits<FMT>::state_t &x,
 // lanes publish which line they need next, and 4 lanes fetch one chunk's line with coalesced
 // 16-byte loads (4 load instructions cover 64 chunks x 64 B).  16 symbols consume at most one
 // line (rans64: <= 4 B per symbol), so "at least 64 bytes ahead" before every group is all the
-// invariant there is.  Ring rows are 136 bytes apart: equal positions of the 64 lanes spread over
-// 32 banks.  Positions are 32-bit offsets from the line of the wave's first chunk.
+// invariant there is.  (What a VALID stream reaches is half of that: symbols of frequency 1 at
+// 16 bits take 32 bytes per group in every format -- tests/test_lane_rate_cpu.py --, so the
+// invariant has 32 bytes to spare; a refill threshold of 31 decodes wrongly.)  Ring rows are 136
+// bytes apart: equal positions of the 64 lanes spread over 32 banks.  Positions are 32-bit offsets
+// from the line of the wave's first chunk.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kLaneWaveLds = 64 * kLaneRingStride + 64 * 4; // rings + one request word per lane
 
@@ -394,7 +397,9 @@ __global__ void __launch_bounds__(1024) k_decode_lanes_staged(const DecParams p)
 //    it is written to the ring: the pieces stay in registers over the group.  A valid stream consumes <= 40 B per
 //    group (5 renormalisations per state: 8 x 16 bits out, 32 bits in each) and the window reads 8 B ahead, so
 //    >= 48 B ahead at a group boundary is the invariant; a lane below that (streams of 2^-16 symbols) is served
-//    synchronously on a side path;
+//    synchronously on a side path.  (The 40 is a loose bound: a state that loses 8 x 16 bits and stays inside its
+//    32-bit-wide interval takes at most FOUR dwords, 32 B per group for both -- tests/test_lane_rate_cpu.py -- so a valid
+//    stream needs 40 B ahead and the invariant has a dword per state to spare; a threshold of 36 decodes wrongly.)
 //  * the whole trip loop is ONE asm statement: states, window, parked pieces, packed symbols and temporaries in
 //    fixed registers (64-bit operands need their halves named; nothing in flight crosses a statement the compiler
 //    schedules).  The 64 symbols of a trip are stored at the start of the next trip, after its first vmcnt wait, so

@@ -627,9 +627,11 @@ __global__ void __launch_bounds__(1024) k_encode_lanes_staged(const EncParams p)
 //    the flush derives them from the ring position (at most 64 bytes per group);
 //  * symbols: four 64-byte lines per quad and block (instruction t = the line of the quad's lane t), transposed in
 //    registers, the next block in flight during the current one; flushes by quads as in the staged kernel.
-// Requirements (launcher): rans64 with scale_bits 7..16 and no frequency of 2^16, u8 symbols, chunk_syms % 64 == 0,
-// 16-byte aligned input, full batches of full chunks (the rest goes through the staged kernel in a second launch, which
-// continues the same status array).
+// Requirements (launcher): rans64 with scale_bits 7..16, u8 symbols, chunk_syms % 64 == 0, 16-byte aligned input, full
+// batches of full chunks (the rest goes through the staged kernel in a second launch, which continues the same status
+// array).  A frequency of 2^16 -- a one-symbol model at 16 bits -- is inside the working range: its record is cmpl = 0,
+// rcp = 2^63, rcp_shift = 15, the renormalisation test x.hi + (0 << 15) >= 2^31 never fires (rans64.h:83's bound is 2^63)
+// and x + bias + q * 0 leaves the state where it is (tests/test_gpu_lane_extremes.py, the one-symbol case).
 // ---------------------------------------------------------------------------
 constexpr uint32_t kR64EncRing = 8192;   // per coding wave
 constexpr uint32_t kR64EncTable = 8192;  // 256 records of 16 bytes at LDS address 0 (rings behind, 8 KiB aligned)

@@ -38,17 +38,26 @@ def expect_decode(ctx, kernels, what):
 
 
 def check_every_chunk(R, ctx, torch, fmt, sb, K, ways, chunk, n, kernels=None, seed=1, damaged=True, sized=True,
-                      sized_ratio=1.35, all_overflow_at_half=True, d_syms=None):
+                      sized_ratio=1.35, all_overflow_at_half=True, d_syms=None, freqs=None):
     """See the module docstring.  sized_ratio: the sized container against the compact one (None: small chunks, whose slots
     of whole 64-byte lines outweigh the compact layout's 16-byte grid -- only rans_amd_encode_sized_bound() holds there).
     all_overflow_at_half: chunks large enough that every full one is longer than half its tight slot.  Returns the artifact
-    dict of the compact container (d_syms, freqs, cont, offs, lens, total ...)."""
+    dict of the compact container (d_syms, freqs, cont, offs, lens, total ...).
+    freqs: a normalised model in place of the one counted from the input (tests/test_gpu_lane_extremes.py: input that does not
+    follow its model -- frequency-1 symbols only, say, whose histogram would normalise to a flat model).  Chunks of such
+    input overflow a tight slot by design, so the sized steps then get overflow room for every chunk."""
     import bench
     if d_syms is None:
         d_syms = bench.gen_zipf(torch, n, K, 1.0, seed, "cuda")
-    counts = ctx.count_freqs_device(d_syms, K)
-    assert int(counts.sum()) == n
-    freqs, _ = R.normalize_freqs(counts, 1 << sb)
+    if freqs is None:
+        counts = ctx.count_freqs_device(d_syms, K)
+        assert int(counts.sum()) == n
+        freqs, _ = R.normalize_freqs(counts, 1 << sb)
+        room = None
+    else:
+        freqs = np.ascontiguousarray(freqs, dtype=np.uint32)
+        assert freqs.size == K and int(freqs.sum()) == 1 << sb
+        room = (n + chunk - 1) // chunk
     gm = ctx.model(fmt, freqs, sb)
     cont, offs, lens, total = ctx.encode(gm, d_syms, ways, chunk)
     expect_encode(ctx, kernels, "encode", "compact encode")
@@ -97,12 +106,12 @@ def check_every_chunk(R, ctx, torch, fmt, sb, K, ways, chunk, n, kernels=None, s
     if sized:
         nchunks = (n + chunk - 1) // chunk
         worst = R.slot_bytes(fmt, n, ways, chunk)
-        t_cont, t_offs, t_lens, t_total, t_slot = ctx.encode_sized(gm, d_syms, ways, chunk)
+        t_cont, t_offs, t_lens, t_total, t_slot = ctx.encode_sized(gm, d_syms, ways, chunk, overflow_chunks=room)
         assert torch.equal(t_lens, lens) and t_slot < worst
         expect_encode(ctx, kernels, "sized", "sized slots")
         if sized_ratio is not None:
             assert t_total <= sized_ratio * total, (t_total, total)  # (config 2's 512-symbol chunks in whole 64-byte lines: 1.23 x)
-        assert t_total <= R.encode_sized_bound(fmt, n, ways, chunk, t_slot, nchunks // 64 + 4), t_total
+        assert t_total <= R.encode_sized_bound(fmt, n, ways, chunk, t_slot, nchunks // 64 + 4 if room is None else room), t_total
         assert bench.oracle_check_chunks(dict(art, cont=t_cont, offs=t_offs, lens=t_lens, total=t_total, slot=t_slot, worst=worst)) == nchunks
         out = ctx.decode(gm, t_cont, t_total, t_offs, t_lens, n, ways, chunk)
         assert torch.equal(out, d_syms)

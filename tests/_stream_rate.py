@@ -4,6 +4,8 @@ definitions in include/ryg_rans_amd/compat/*.h (rans_byte.h:62-128 and :291-318,
 
 round_bytes() is what the rate-extreme tests (tests/test_stream_rate_cpu.py, tests/test_gpu_rate_extremes.py) rest on: the
 first proves on the CPU that the inputs below reach the bounds the GPU tests claim, the second decodes those inputs.
+tests/test_lane_rate_cpu.py and tests/test_gpu_lane_extremes.py are the same pair for the lane-per-chunk kernels: group_bytes()
+turns round_bytes() into bytes per 16-symbol group of one lane's chunk, chunk_grid() builds the chunks of a whole launch.
 
 Two facts about the formats that shape the inputs:
 
@@ -115,6 +117,23 @@ def windows(per_round, w=8):
     return c[w:] - c[:-w]
 
 
+def group_bytes(per_round, n_ways, group=16):
+    """Bytes per `group`-symbol group of one lane's chunk: the sums over every window of group / n_ways rounds (the lane
+    kernels refill, flush and check their invariants once per 16 symbols, wherever the group boundary falls)."""
+    assert group % n_ways == 0
+    return windows(per_round, group // n_ways)
+
+
+def rare_group_bytes(fmt, scale_bits, n_ways, group=16):
+    """(least, most) bytes a window of group / n_ways rounds of frequency-1 symbols takes -- from the formats alone.  A symbol
+    of frequency 1 makes the decoder's step x = x >> scale_bits (its slot is its start): exactly scale_bits bits leave the
+    state.  A state's bit length is in [b, b + u) before and after the window (u: the unit's bits), so the k units that
+    come in satisfy T - u < k u < T + u for the T = (group / n_ways) scale_bits bits that left: k = T / u where u divides T,
+    floor or ceil otherwise -- whatever the state was when the window began."""
+    lost, u = (group // n_ways) * scale_bits, _UNIT_BITS[fmt]
+    return n_ways * (lost // u) * UNIT[fmt], n_ways * ((lost + u - 1) // u) * UNIT[fmt]
+
+
 def longest_silence(per_round):
     """The longest run of consecutive rounds that take no byte."""
     best = run = 0
@@ -151,6 +170,35 @@ def quiet_model():
     f = np.zeros(256, dtype=np.uint32)
     f[COMMON], f[SHIFT] = 4096 - 16 - 15, 16
     f[2:17] = 1
+    return f
+
+
+def lane_model(sb):
+    """255 x 1 and one common symbol at 2^sb."""
+    f = np.ones(256, dtype=np.uint32)
+    f[COMMON] = (1 << sb) - 255
+    return f
+
+
+def packed_model_14():
+    """252 x 1 and four symbols of 4033 at 2^14: frequency-1 symbols under a model whose largest frequency fits the 12-bit
+    field of the rans64 packed slot records.  (No silent extreme: the commonest symbol still costs two bits.)"""
+    f = np.ones(256, dtype=np.uint32)
+    f[:4] = 4033
+    assert int(f.sum()) == 1 << 14
+    return f
+
+
+def top_frequency_model(sb, top):
+    """Largest frequency exactly `top` (4095 / 4096) at 2^sb, 13 or 14 bits: `top`, three (one) further common symbols of at
+    most 4094, frequency 1 for the rest."""
+    f = np.ones(256, dtype=np.uint32)
+    k = 2 if sb == 13 else 4
+    rest = (1 << sb) - (256 - k) - top
+    f[0] = top
+    share = [rest // (k - 1) + (1 if i < rest % (k - 1) else 0) for i in range(k - 1)]
+    f[1:k] = share
+    assert int(f.sum()) == 1 << sb and int(f.max()) == top and int(np.count_nonzero(f == top)) == 1
     return f
 
 
@@ -218,6 +266,91 @@ def bursts(freqs, n, seed, lead=0, run=64):
 def drawn(freqs, n, seed):
     f = np.asarray(freqs, dtype=np.float64)
     return np.random.default_rng(seed).choice(f.size, n, p=f / f.sum()).astype(_dtype(freqs))
+
+
+# ---- contents of a grid of chunks, one chunk per lane of a wave ---------------------------------------------------------
+LANE_KINDS = ("rare", "common", "bursts64", "bursts16", "drawn")
+RARE, COMMON_K, BURSTS64, BURSTS16, DRAWN = range(5)
+QUADS = (0, 7, 15)  # a first, a middle and the last quad of a wave
+
+
+def lane_patterns():
+    """What the 64 lanes of a wave hold -> [(name, kind of lane 0..63)], 35 waves:
+      rotating-r          lane l holds LANE_KINDS[(l + r) mod 5]: over the five every lane position meets every kind
+      quad-mates-differ-r [rare, common, bursts, drawn] x 16 rotated by r (runs of 64 in the even quads, of 16 in the odd ones)
+      one-rare-qQ-lL      one rare lane -- lane L of quad Q -- among 63 common ones
+      one-common-qQ-lL    the inverse: a lane that asks for nothing beside 63 that take the most
+      all-rare, all-common"""
+    out = []
+    lanes = np.arange(64)
+    for r in range(5):
+        out.append(("rotating-%d" % r, (lanes + r) % 5))
+    quad = np.array([RARE, COMMON_K, BURSTS64, DRAWN])
+    for r in range(4):
+        k = quad[(lanes + r) % 4]
+        k[(k == BURSTS64) & ((lanes // 4) % 2 == 1)] = BURSTS16
+        out.append(("quad-mates-differ-%d" % r, k))
+    for name, one, rest in (("one-rare", RARE, COMMON_K), ("one-common", COMMON_K, RARE)):
+        for q in QUADS:
+            for l in range(4):
+                k = np.full(64, rest)
+                k[4 * q + l] = one
+                out.append(("%s-q%d-l%d" % (name, q, l), k))
+    out.append(("all-rare", np.full(64, RARE)))
+    out.append(("all-common", np.full(64, COMMON_K)))
+    return [(n, k.astype(np.uint8)) for n, k in out]
+
+
+def pattern_kinds(nchunks, names=None):
+    """Kind of every chunk: batch b (64 chunks, one wave) holds pattern b mod len(patterns) of lane_patterns() (`names`: of
+    those alone)."""
+    pats = [k for n, k in lane_patterns() if names is None or n in names]
+    table = np.stack(pats)
+    c = np.arange(nchunks)
+    return table[(c // 64) % len(pats), c % 64]
+
+
+def turn_kinds(nchunks, kinds=(RARE, COMMON_K, BURSTS64, DRAWN)):
+    """The kinds in turn by chunk."""
+    return np.asarray(kinds, dtype=np.uint8)[np.arange(nchunks) % len(kinds)]
+
+
+def burst_lead(c):
+    """Symbols cut off the first (rare) run of chunk c's bursts: a multiple of 8 -- of every interleave --, 0 .. 120, spread by
+    a multiplicative hash so that it does not follow the lane or the batch."""
+    return 8 * (((np.asarray(c, dtype=np.uint64) * np.uint64(2654435761)) >> np.uint64(9)) % np.uint64(16)).astype(np.int64)
+
+
+def chunk_grid(freqs, kinds, chunk, seed, first_chunk=0):
+    """-> symbols [len(kinds), chunk]: chunk c of kind kinds[c] (an index into LANE_KINDS), vectorised over the grid.  rare:
+    symbols of the smallest frequency on record; common: the commonest symbol; bursts64 / bursts16: runs of 64 / 16 rare and
+    as many common symbols in turn, burst_lead(first_chunk + c) symbols of the first run cut off; drawn: from the model."""
+    f = np.asarray(freqs, dtype=np.int64)
+    kinds = np.asarray(kinds)
+    rare, common = rare_and_common(freqs)
+    rng = np.random.default_rng(seed)
+    n = kinds.size
+    out = rare.astype(_dtype(freqs))[rng.integers(0, 256, (n, chunk), dtype=np.uint8) % rare.size]
+    out[kinds == COMMON_K] = common
+    pos = np.arange(chunk)
+    for kind, run in ((BURSTS64, 64), (BURSTS16, 16)):
+        rows = np.nonzero(kinds == kind)[0]
+        if rows.size:
+            sub = out[rows]
+            sub[((pos[None, :] + burst_lead(rows + first_chunk)[:, None]) // run) % 2 == 1] = common
+            out[rows] = sub
+    rows = np.nonzero(kinds == DRAWN)[0]
+    if rows.size:
+        cum = np.cumsum(f)
+        out[rows] = np.searchsorted(cum, rng.integers(0, int(cum[-1]), (rows.size, chunk)), side="right").astype(out.dtype)
+    return out
+
+
+def lane_phases(nchunks, unit):
+    """Start offsets modulo 128 for pack_at_phases: lane l of batch b at unit * ((l + 7 b) mod (128 / unit)).  Units of 1 and 2
+    bytes: the 64 lanes of a wave at 64 different offsets; over 19 (10, 5) batches every multiple of the unit is met."""
+    c = np.arange(nchunks)
+    return unit * ((c % 64 + 7 * (c // 64)) % (128 // unit))
 
 
 _ORACLE = []
