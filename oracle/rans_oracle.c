@@ -197,6 +197,25 @@ static int build_alias(orc_model *m)
     return ok ? ORC_OK : ORC_E_ARG;
 }
 
+/* cum2sym is a table of 4 << scale_bits bytes: 8 GiB at 31 bits.  Above this many bits the decoder finds the symbol by a
+ * binary search over cum[] instead -- the same answer (the symbol s with cum[s] <= slot < cum[s + 1]). */
+#define ORC_CUM2SYM_MAX_BITS 24
+
+static uint32_t sym_of_slot(const orc_model *m, uint32_t cf)
+{
+    if (m->cum2sym)
+        return m->cum2sym[cf];
+    uint32_t lo = 0, hi = m->nsyms; /* cum[lo] <= cf < cum[hi] */
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (m->cum[mid] <= cf)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
 orc_model *orc_model_create(const uint32_t *norm_freqs, uint32_t nsyms, uint32_t scale_bits, int with_alias)
 {
     if (!norm_freqs || nsyms == 0 || scale_bits == 0 || scale_bits > 31)
@@ -209,8 +228,9 @@ orc_model *orc_model_create(const uint32_t *norm_freqs, uint32_t nsyms, uint32_t
     m->scale_bits = scale_bits;
     m->freqs = (uint32_t *)malloc(sizeof(uint32_t) * nsyms);
     m->cum = (uint32_t *)malloc(sizeof(uint32_t) * (nsyms + 1));
-    m->cum2sym = (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)1 << scale_bits));
-    if (!m->freqs || !m->cum || !m->cum2sym) {
+    const int tabled = scale_bits <= ORC_CUM2SYM_MAX_BITS;
+    m->cum2sym = tabled ? (uint32_t *)malloc(sizeof(uint32_t) * ((size_t)1 << scale_bits)) : NULL;
+    if (!m->freqs || !m->cum || (tabled && !m->cum2sym)) {
         orc_model_destroy(m);
         return NULL;
     }
@@ -226,7 +246,7 @@ orc_model *orc_model_create(const uint32_t *norm_freqs, uint32_t nsyms, uint32_t
         return NULL;
     }
     /* main.cpp:143-148 (cum2sym) */
-    for (uint32_t s = 0; s < nsyms; s++)
+    for (uint32_t s = 0; tabled && s < nsyms; s++)
         for (uint32_t c = m->cum[s]; c < m->cum[s + 1]; c++)
             m->cum2sym[c] = s;
     if (with_alias && build_alias(m) != ORC_OK) {
@@ -441,7 +461,7 @@ int orc_decode(int fmt, const orc_model *m, const uint8_t *stream, size_t len, s
                 /* rans64.h:118-121 get, :286-292 step */
                 uint64_t x = st[l];
                 uint32_t cf = (uint32_t)x & mask;
-                s = m->cum2sym[cf];
+                s = sym_of_slot(m, cf);
                 st[l] = (uint64_t)m->freqs[s] * (x >> sb) + cf - m->cum[s];
             } else if (fmt == ORC_FMT_ALIAS) {
                 /* main_alias.cpp:252-267; 32-bit wrap-around is intended */
@@ -456,7 +476,7 @@ int orc_decode(int fmt, const orc_model *m, const uint8_t *stream, size_t len, s
                  * (slot table == cum2sym + {freq, slot - start}) */
                 uint32_t x = (uint32_t)st[l];
                 uint32_t cf = x & mask;
-                s = m->cum2sym[cf];
+                s = sym_of_slot(m, cf);
                 st[l] = (uint32_t)(m->freqs[s] * (x >> sb) + cf - m->cum[s]);
             }
             sym_put(out, base + l, sym_bytes, s);

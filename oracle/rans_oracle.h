@@ -45,7 +45,7 @@ typedef struct orc_model {
     uint32_t scale_bits;   /* sum(freqs) == 1 << scale_bits */
     uint32_t *freqs;       /* [nsyms]   */
     uint32_t *cum;         /* [nsyms+1] */
-    uint32_t *cum2sym;     /* [1<<scale_bits] symbol owning each cumulative slot */
+    uint32_t *cum2sym;     /* [1<<scale_bits] symbol owning each cumulative slot; NULL above 24 bits (the decoder searches cum) */
     /* alias tables (NULL unless built) */
     uint32_t *divider;     /* [nsyms]   */
     uint32_t *slot_adjust; /* [2*nsyms] */

@@ -6,6 +6,9 @@ round_bytes() is what the rate-extreme tests (tests/test_stream_rate_cpu.py, tes
 first proves on the CPU that the inputs below reach the bounds the GPU tests claim, the second decodes those inputs.
 tests/test_lane_rate_cpu.py and tests/test_gpu_lane_extremes.py are the same pair for the lane-per-chunk kernels: group_bytes()
 turns round_bytes() into bytes per 16-symbol group of one lane's chunk, chunk_grid() builds the chunks of a whole launch.
+tests/test_wave_rate_cpu.py and tests/test_gpu_wave_extremes.py are the pair for the wave-per-chunk kernels: interval_bound() is
+the most a valid stream takes between two checkpoints of the decoders' stream window, window_walk() a plain model of that
+window, steered() the input that puts the cursor of a rare-only stream where one wants it.
 
 Two facts about the formats that shape the inputs:
 
@@ -29,8 +32,9 @@ _UNIT_BITS = {FMT_BYTE: 8, FMT_ALIAS: 8, FMT_WORD: 16, FMT_R64: 32}
 _MAX_UNITS = {FMT_BYTE: 2, FMT_ALIAS: 2, FMT_WORD: 1, FMT_R64: 1}  # `while` in the byte formats, `if` in the other two
 
 
-def simulate(fmt, freqs, scale_bits, syms, n_ways, remap=None):
-    """-> (bytes per round, the flushed states).  Symbol i is state i mod n_ways's; a round is one symbol of every state.
+def simulate(fmt, freqs, scale_bits, syms, n_ways, remap=None, per_state=False):
+    """-> (bytes per round, the flushed states); with per_state also the units every state takes in every round, [rounds,
+    n_ways].  Symbol i is state i mod n_ways's; a round is one symbol of every state.
 
     The coder's pass (last symbol first) yields the renormalisation units of every round and the final states; the
     decoder's pass then starts from those states and runs x = f (x >> sb) + (x & mask) - start and the format's
@@ -97,6 +101,8 @@ def simulate(fmt, freqs, scale_bits, syms, n_ways, remap=None):
         x[:k] = xs
         per_round[r] = int(got.sum()) * UNIT[fmt]
     assert np.all(x == low), "the states do not end at the format's lower bound"
+    if per_state:
+        return per_round, states, taken
     return per_round, states
 
 
@@ -132,6 +138,59 @@ def rare_group_bytes(fmt, scale_bits, n_ways, group=16):
     floor or ceil otherwise -- whatever the state was when the window began."""
     lost, u = (group // n_ways) * scale_bits, _UNIT_BITS[fmt]
     return n_ways * (lost // u) * UNIT[fmt], n_ways * ((lost + u - 1) // u) * UNIT[fmt]
+
+
+def interval_bound(fmt, scale_bits, states, rounds):
+    """The most bytes a valid stream can take in an interval of `rounds` rounds of `states` states -- from the format alone,
+    as rare_group_bytes: a round removes at most scale_bits bits from a state (a frequency-1 symbol: x = x >> scale_bits),
+    a state's bit length lies in a range one unit wide before and after the interval, so at most ceil(rounds scale_bits /
+    unit bits) units come in; and no more than the format's renormalisation can bring in in `rounds` rounds (two units per
+    round in the byte formats, one in the other two)."""
+    units = (rounds * scale_bits + _UNIT_BITS[fmt] - 1) // _UNIT_BITS[fmt]
+    return states * min(units, rounds * _MAX_UNITS[fmt]) * UNIT[fmt]
+
+
+def substep_bytes(taken, fmt, n_ways):
+    """The bytes of every sub-step, in the decoders' order: a sub-step is the renormalisation of 64 states (one per lane of a
+    wave) -- round r of an N-way stream is ceil(N / 64) of them, states 0..63 first.  `taken`: simulate(per_state=True)."""
+    taken = np.asarray(taken, dtype=np.int64)
+    k = (int(n_ways) + 63) // 64
+    padded = np.zeros((taken.shape[0], 64 * k), dtype=np.int64)
+    padded[:, :taken.shape[1]] = taken
+    return (padded.reshape(taken.shape[0], k, 64).sum(axis=2) * UNIT[fmt]).reshape(-1)
+
+
+RING_BLOCK, RING_BYTES, RING_MIRROR = 1024, 2048, 768  # (the comment at the top of decode_common.hpp; wave_shape.hpp)
+
+
+def window_walk(substeps, first, cadence, every_from=None):
+    """A plain model of the decoders' stream window, written from the comment at the top of decode_common.hpp: a 2 KiB ring
+    filled in aligned 1 KiB blocks, the cursor starting at `first` mod 16 (the window opens at the 16-byte granule of the
+    first unit), the mark at 1024.  A checkpoint falls in front of sub-step 0, cadence, 2 cadence ... (from sub-step
+    `every_from` on: in front of every sub-step -- the element-store tail).  At a checkpoint with cursor >= mark: while the
+    mark is 1024 the first half is refilled and the mark goes to 2048; otherwise the cursor drops by 2048, the second half is
+    refilled and the mark returns to 1024.  Between checkpoints the cursor only moves up.
+    -> ([(cursor - mark, refilled, bytes of the interval that follows)] per checkpoint, the largest ring offset reached)."""
+    b = np.asarray(substeps, dtype=np.int64)
+    n = b.size
+    at = [i for i in range(n) if (every_from is not None and i >= every_from) or i % cadence == 0]
+    cur, mark, top = int(first) & 15, RING_BLOCK, 0
+    out = []
+    for j, i in enumerate(at):
+        rel = cur - mark
+        refilled = cur >= mark
+        if refilled:
+            if mark == RING_BLOCK:
+                mark = RING_BYTES
+            else:
+                cur -= RING_BYTES
+                mark = RING_BLOCK
+        nxt = at[j + 1] if j + 1 < len(at) else n
+        took = int(b[i:nxt].sum())
+        out.append((rel, refilled, took))
+        cur += took
+        top = max(top, cur)
+    return out, top
 
 
 def longest_silence(per_round):
@@ -177,6 +236,13 @@ def lane_model(sb):
     """255 x 1 and one common symbol at 2^sb."""
     f = np.ones(256, dtype=np.uint32)
     f[COMMON] = (1 << sb) - 255
+    return f
+
+
+def model_rare(sb, K):
+    """K - 1 symbols of frequency 1 and one common symbol at 2^sb, for alphabets above 256 as well (u16 symbols)."""
+    f = np.ones(K, dtype=np.uint32)
+    f[COMMON] = (1 << sb) - (K - 1)
     return f
 
 
@@ -261,6 +327,17 @@ def bursts(freqs, n, seed, lead=0, run=64):
     out = rare_only(freqs, n, seed)
     out[((np.arange(n) + lead) // run) % 2 == 1] = rare_and_common(freqs)[1]
     return out
+
+
+def steered(freqs, lanes_rare, lead_rounds, rare_rounds, seed, n_ways):
+    """(lead_rounds + rare_rounds) n_ways symbols: in the first lead_rounds rounds states 0 .. lanes_rare - 1 hold rare
+    symbols and the others the common one, rare-only rounds follow.  The bytes of a round depend on the rounds from it on
+    alone, so the rare-only part renormalises in lock-step whatever leads it, and the lead moves the decoder's cursor by
+    whatever multiple of the unit its rare states take: the cursor of a rare-only stream can be put anywhere."""
+    n = (lead_rounds + rare_rounds) * n_ways
+    out = rare_only(freqs, n, seed).reshape(lead_rounds + rare_rounds, n_ways)
+    out[:lead_rounds, lanes_rare:] = rare_and_common(freqs)[1]
+    return out.reshape(-1)
 
 
 def drawn(freqs, n, seed):
