@@ -29,22 +29,14 @@
 // No MFMA: integer, table-driven, serial per state.
 
 #include "decode_common.hpp"
+#include "groups_common.hpp"
 
 namespace rans_amd {
 
 namespace {
 
-constexpr uint32_t kGrpBlock = 128;             // bytes a group fetches at a time: 8 lanes x 16 B
-constexpr uint32_t kGrpRing = 2 * kGrpBlock;    // per group
-constexpr uint32_t kGrpWaveLds = 8 * kGrpRing;  // per wave
-constexpr uint32_t kGrpThreads = 1024;
 constexpr uint32_t kGrpClaimSyms = 8192;        // symbols one claim of the work counter covers, at least
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes on the 4-byte grid (the ragged kernel's lines)
-
-__device__ __forceinline__ uint32_t lds_u16(uint32_t addr)
-{
-    return *reinterpret_cast<RANS_LDS const uint16_t *>((uintptr_t)addr);
-}
 
 // Eight rounds of the eight chunks as one hand-scheduled sequence: rans_word_sse41.h:123-141 (the D step and the
 // renormalisation of RansWordDecSym / RansWordDecRenorm), 14 VALU + 2 LDS per round:
@@ -111,12 +103,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
     using Tr = FmtTraits<FMT_WORD>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // WordSlot[4096]: 32 KiB, a multiple of the ring size
-    {
-        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.table0);
-        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
-        for (uint32_t i = threadIdx.x; i < t0_bytes / 16u; i += blockDim.x)
-            l0[i] = g0[i];
-    }
+    stage_table(smem, p.table0, t0_bytes);
     __syncthreads();
     DecTables<FMT_WORD> T;
     T.init(smem, smem + t0_bytes, p.scale_bits, p.log2nsyms);
@@ -125,32 +112,15 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
             atomicAdd(p.err_count, 1ull << 32);
         return;
     }
-    if (p.work_counter_reset && blockIdx.x == 0 && threadIdx.x < kWorkPools)
-        p.work_counter_reset[threadIdx.x * kWorkPoolStride] = 0u;
-    if (p.span_reset && blockIdx.x == 0 && threadIdx.x < 2)
-        p.span_reset[threadIdx.x] = 0ull;
+    reset_for_next_launch(p);
 
     const uint32_t lane = lane_id();
     const uint32_t wave = uniform(threadIdx.x >> 6);
     const uint32_t waves_per_block = blockDim.x >> 6;
     const uint32_t g = lane >> 3, i = lane & 7u;
-    // raw LDS byte address of this group's ring (LDS starts at zero; 256-byte aligned: positions wrap with an and-or)
-    const uint32_t ring = t0_bytes + wave * kGrpWaveLds + g * kGrpRing;
-    // Ring positions carry a per-group bias of 16 g bytes: the groups' cursors move at the same average pace, and eight
-    // rings 256 bytes apart would otherwise sit on the same banks.
-    const uint32_t bias = 16u * g;
-    // this group's bits of the ballot's halves (one of the two is zero)
-    uint32_t gm_lo = g < 4 ? 0xffu << (8u * g) : 0u, gm_hi = g >= 4 ? 0xffu << (8u * (g - 4u)) : 0u;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_lo)); // opaque: keep them in VGPRs
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_hi));
-    uint32_t k255 = 255u, k65536 = 0x10000u;
-    // v_perm selectors of the symbol accumulators (decode_common.hpp acc_symbol for byte 3 of the slot record's first word)
-    uint32_t sel_a = 0x03020703u, sel_b = 0x03070100u, sel_c = 0x07020100u;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_a));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_b));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_c));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k255));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k65536));
+    const WordGroupLane L(t0_bytes, wave, g);
+    const uint32_t ring = L.ring, bias = L.bias, gm_lo = L.gm_lo, gm_hi = L.gm_hi, k255 = L.k255, k65536 = L.k65536;
+    const uint32_t sel_a = L.sel_a, sel_b = L.sel_b, sel_c = L.sel_c;
 
     const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
     const uint64_t glo = cbase & ~uint64_t(15), glimit = (cbase + p.container_bytes + 15u) & ~uint64_t(15);
@@ -163,34 +133,9 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
     const uint32_t per_claim = uniform(p.chunk_syms >= kGrpClaimSyms / 8u ? 1u : (kGrpClaimSyms / 8u + p.chunk_syms - 1u) / p.chunk_syms);
     const uint64_t claims = (octets + per_claim - 1u) / per_claim;
 
-    auto load16 = [&](uint64_t a) -> u32x4 { // 16 bytes of the container, zeros beyond its granules
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (a >= glo && a < glimit)
-            v = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(a));
-        return v;
-    };
-
     uint32_t nbad = 0;
-    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
-    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
-    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
-    const uint32_t pool = blockIdx.x % npools;
-    // Work is handed out dynamically, as in decode_wave.hip k_decode (pool = blockIdx % 8 owns the claims c with c % 8 == pool).
-    // Nothing is claimed or fetched ahead of its octet: the kernel is bound by VALU and LDS issue (eight waves per SIMD), a
-    // wave's trips to memory in front of an octet are covered by the other seven, and measured (profiles/r06_word8_groups.md)
-    // a claim held while another octet is decoded keeps work from the waves that run dry: + 6 % at 16 octets per wave, + 15 %
-    // at one; index entries fetched during the last rounds only add to what the refills' s_waitcnt vmcnt(0) waits for.
-    auto claim_take = [&]() -> uint64_t {
-        if (p.work_counter) {
-            uint32_t got = 0;
-            if (lane == 0)
-                got = atomicAdd(p.work_counter + pool * kWorkPoolStride, 1u);
-            return (uint64_t)uniform(got) * npools + pool;
-        }
-        const uint64_t c = claim_v;
-        claim_v += total_waves;
-        return uniform64(c);
-    };
+    WorkClaims work;
+    work.init(p.work_counter, wave, waves_per_block);
     // A ragged last chunk (p.n % p.chunk_syms != 0) is decoded here as well: its octet, the input's last, goes one round at a
     // time with the lanes that have no symbol sitting out -- three times an octet's usual time, so the octets are handed out
     // back to front then and that one starts first.
@@ -199,7 +144,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
     uint64_t vk, o_end;
     bool have;
     {
-        const uint64_t c = claim_take();
+        const uint64_t c = work.take(lane);
         have = c < claims;
         vk = c * per_claim;
         o_end = (c + 1u) * per_claim < octets ? (c + 1u) * per_claim : octets;
@@ -221,62 +166,16 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
             uint32_t x = Tr::kL;
             if (valid) // RansDecInit order: state 0 first (rans_word_sse41.h:104-113)
                 x = reinterpret_cast<const uint32_t RANS_GLOBAL *>(src)[i];
-            // positions count from the 128-byte line of the chunk's first byte
-            const uint64_t abase = src & ~uint64_t(kGrpBlock - 1u);
-            const uint32_t start = (uint32_t)(src - abase) + 8u * 4u; // < 160
-            uint32_t curw = (start + bias) >> 1; // the cursor in words (biased)
-            uint64_t ld = abase + 16u * i;
-            const u32x4 b0 = load16(ld), b1 = load16(ld + kGrpBlock);
-            u32x4 pend = load16(ld + 2u * kGrpBlock); // block 2; the ring holds blocks nb - 2 and nb - 1, pend is block nb
-            ld += 3u * kGrpBlock;
-            // 16-byte pieces at ld, ld + 128, ... that still lie inside the container's granules: the refills count them down instead
-            // of comparing addresses (a piece beyond the end is not fetched; the ring then keeps what it had -- only a damaged
-            // stream reads that far, and the integrity check is what catches those)
-            uint32_t left = 0;
-            if (ld < glimit) {
-                const uint64_t pieces = (glimit - ld + (kGrpBlock - 1u)) / kGrpBlock;
-                left = pieces < 0x7fffffffu ? (uint32_t)pieces : 0x7fffffffu;
-            }
-            *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)(ring | ((16u * i + bias) & 255u))) = b0;
-            *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)(ring | ((kGrpBlock + 16u * i + bias) & 255u))) = b1;
-            uint32_t wr = ring | ((16u * i + bias) & 255u); // where block nb goes
-            uint32_t thr = (kGrpBlock + bias) >> 1;         // cursor (words) from which block nb has to be in the ring
-            auto checkpoint = [&]() {
-                if (curw >= thr) { // (the same for the eight lanes of a group)
-                    *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)wr) = pend;
-                    wr ^= kGrpBlock;
-                    thr += kGrpBlock / 2u;
-                    if (left) {
-                        pend = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(ld));
-                        left--;
-                    }
-                    ld += kGrpBlock;
-                }
-            };
-            checkpoint(); // the states may end in block 1
+            WordRing R;
+            const uint32_t start = R.open(src, i, ring, bias, true, glo, glimit);
+            uint32_t &curw = R.curw;
+            auto checkpoint = [&]() { R.checkpoint(); };
 
             // symbol stores through a descriptor of the octet's output: the running offset is an SGPR
             const rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
                 reinterpret_cast<void *>(reinterpret_cast<uint64_t>(p.out) + octet * 8u * p.chunk_syms), 0, 8u * p.chunk_syms, kRsrcFlags);
             const uint32_t out_off16 = valid ? g * p.chunk_syms + 16u * i : 0x80000000u; // (an invalid chunk's stores: dropped by the range check)
             uint32_t osoff = 0;
-#define RANS_GROUP_ROUND(ACC, J)                                                                        \
-    {                                                                                                   \
-        ACC = acc_symbol<Tr::kSymByte, J>(dec_step<FMT_WORD>(T, x), ACC);                               \
-        const bool need = x < k65536;                                                                   \
-        const uint64_t m = __builtin_amdgcn_ballot_w64(need);                                           \
-        const uint32_t t_lo = (uint32_t)m & gm_lo, t_hi = (uint32_t)(m >> 32) & gm_hi;                  \
-        /* the cursor + this group's renormalising lanes below me (v_mbcnt adds its second operand) */  \
-        const uint32_t at = __builtin_amdgcn_mbcnt_hi(t_hi, __builtin_amdgcn_mbcnt_lo(t_lo, curw));     \
-        curw += __builtin_popcount(t_lo) + __builtin_popcount(t_hi);                                    \
-        if (need)                                                                                       \
-            x = (x << 16) | lds_u16(((at << 1) & k255) | ring);                                         \
-    }
-            // Sixteen rounds = one 128-byte line per group.  Round r's symbols go to byte (r >> 1) & 3 of accumulator
-            // (r & 1) + 2 (r >> 3): after the quad transposes lane (m = i & 3, h = i >> 2) holds the dwords (row 2 m, half h),
-            // (row 2 m + 1, half h), (row 8 + 2 m, h), (row 9 + 2 m, h) of the line's sixteen 8-byte rows; the halves h = 0
-            // keep the first two and take their other halves from lane i + 4, the halves h = 1 the last two from lane i - 4:
-            // lane i then holds bytes [16 i, 16 i + 16) of the line, one 16-byte store per lane.
             const bool by_rounds = ragged && octet + 1u == octets; // (wave-uniform)
             for (uint32_t q = 0; q < (by_rounds ? 0u : groups16); ++q) {
                 uint32_t a0, a1, a2, a3;
@@ -290,20 +189,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
                 a1 = quad_transpose(a1, sel1, sel2);
                 a2 = quad_transpose(a2, sel1, sel2);
                 a3 = quad_transpose(a3, sel1, sel2);
-                // (v_cndmask_b32_dpp by hand: left to the compiler, the select becomes a branch around the DPP move, and a DPP
-                // move under an exec mask reads zeros from the lanes the mask has switched off -- the very lanes it is after)
-                u32x4 v;
-                asm volatile("s_nop 1\n\t"
-                             "s_mov_b64 vcc, %[lower]\n\t"
-                             "v_cndmask_b32_dpp %[vx], %[a2], %[a0], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" // lower ? a0 : a2 of lane - 4
-                             "v_cndmask_b32_dpp %[vz], %[a3], %[a1], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                             "s_mov_b64 vcc, %[upper]\n\t"
-                             "v_cndmask_b32_dpp %[vy], %[a0], %[a2], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" // upper ? a2 : a0 of lane + 4
-                             "v_cndmask_b32_dpp %[vw], %[a1], %[a3], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                             : [vx] "=&v"(v.x), [vy] "=&v"(v.y), [vz] "=&v"(v.z), [vw] "=&v"(v.w)
-                             : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [lower] "s"(0x0f0f0f0f0f0f0f0full),
-                               [upper] "s"(0xf0f0f0f0f0f0f0f0ull)
-                             : "vcc");
+                const u32x4 v = halves_to_line(a0, a1, a2, a3);
                 // (chunk sizes off 64: a chunk's lines straddle the memory's at odd places, and the pieces of a memory line arrive
                 //  sixteen rounds apart -- plain stores let L2 put them together: 1000-symbol chunks 1.10 -> 0.77 ms, 4000: 0.90 ->
                 //  0.65; on the 64-byte grid `nt sc1` wins: 960-symbol chunks 0.52 against 0.59)
@@ -315,10 +201,10 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
             }
             for (uint32_t q = 0; q < (by_rounds ? 0u : rem4); ++q) { // what is left of a chunk that is not a multiple of 128 symbols: 4 rounds a time
                 uint32_t acc = 0;
-                RANS_GROUP_ROUND(acc, 0)
-                RANS_GROUP_ROUND(acc, 1)
-                RANS_GROUP_ROUND(acc, 2)
-                RANS_GROUP_ROUND(acc, 3)
+                acc = acc_symbol<Tr::kSymByte, 0>(decode_word_round(T, x, curw, true, gm_lo, gm_hi, k255, k65536, ring), acc);
+                acc = acc_symbol<Tr::kSymByte, 1>(decode_word_round(T, x, curw, true, gm_lo, gm_hi, k255, k65536, ring), acc);
+                acc = acc_symbol<Tr::kSymByte, 2>(decode_word_round(T, x, curw, true, gm_lo, gm_hi, k255, k65536, ring), acc);
+                acc = acc_symbol<Tr::kSymByte, 3>(decode_word_round(T, x, curw, true, gm_lo, gm_hi, k255, k65536, ring), acc);
                 if (q & 1u)
                     checkpoint();
                 const uint32_t v = quad_transpose(acc, sel1, sel2);
@@ -326,7 +212,6 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
                 __builtin_amdgcn_raw_buffer_store_b32(v, orsrc, out_off16 - 16u * li + (li & 3u) * 8u + (li >> 2) * 4u, osoff, 0);
                 osoff += 32u;
             }
-#undef RANS_GROUP_ROUND
             // what a chunk size off 32 leaves (at most 31 symbols: three rounds and a partial one, main_simd.cpp:313-332 with
             // in_size % 8 != 0) -- or, in the ragged chunk's octet, every round: lanes without a symbol sit the round out, a byte
             // store per lane
@@ -340,16 +225,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
                 if (by_rounds && (r0 & 63u) == 0)
                     checkpoint();
                 const bool active = r0 + i < nsym;
-                uint32_t raw = 0;
-                if (active)
-                    raw = dec_step<FMT_WORD>(T, x);
-                const bool need = active && x < k65536;
-                const uint64_t m = __builtin_amdgcn_ballot_w64(need);
-                const uint32_t t_lo = (uint32_t)m & gm_lo, t_hi = (uint32_t)(m >> 32) & gm_hi;
-                const uint32_t at = __builtin_amdgcn_mbcnt_hi(t_hi, __builtin_amdgcn_mbcnt_lo(t_lo, curw));
-                curw += __builtin_popcount(t_lo) + __builtin_popcount(t_hi);
-                if (need)
-                    x = (x << 16) | lds_u16(((at << 1) & k255) | ring);
+                const uint32_t raw = decode_word_round(T, x, curw, active, gm_lo, gm_hi, k255, k65536, ring);
                 if (active)
                     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)(raw >> 24), orsrc, out_off16 - 16u * i + r0 + i, 0, 0);
             }
@@ -362,7 +238,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_word_groups(const Dec
             uint64_t n_vk = vk + 1u, n_end = o_end;
             bool n_have = true;
             if (n_vk >= o_end) {
-                const uint64_t c = claim_take();
+                const uint64_t c = work.take(lane);
                 n_have = c < claims;
                 n_vk = c * per_claim;
                 n_end = (c + 1u) * per_claim < octets ? (c + 1u) * per_claim : octets;
@@ -417,12 +293,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_word_groups(con
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const unsigned long long t_start = p.span ? wall_clock64() : 0ull;
     const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // WordSlot[4096]: 32 KiB, a multiple of the ring size
-    {
-        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.table0);
-        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
-        for (uint32_t i = threadIdx.x; i < t0_bytes / 16u; i += blockDim.x)
-            l0[i] = g0[i];
-    }
+    stage_table(smem, p.table0, t0_bytes);
     __syncthreads();
     DecTables<FMT_WORD> T;
     T.init(smem, smem + t0_bytes, p.scale_bits, p.log2nsyms);
@@ -431,27 +302,15 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_word_groups(con
             atomicAdd(p.err_count, 1ull << 32);
         return;
     }
-    if (p.work_counter_reset && blockIdx.x == 0 && threadIdx.x < kWorkPools)
-        p.work_counter_reset[threadIdx.x * kWorkPoolStride] = 0u;
-    if (p.span_reset && blockIdx.x == 0 && threadIdx.x < 2)
-        p.span_reset[threadIdx.x] = 0ull;
+    reset_for_next_launch(p);
 
     const uint32_t lane = lane_id();
     const uint32_t wave = uniform(threadIdx.x >> 6);
     const uint32_t waves_per_block = blockDim.x >> 6;
     const uint32_t g = lane >> 3, i = lane & 7u;
-    const uint32_t ring = t0_bytes + wave * kGrpWaveLds + g * kGrpRing; // (as in k_decode_word_groups, the bias as well)
-    const uint32_t bias = 16u * g;
-    uint32_t gm_lo = g < 4 ? 0xffu << (8u * g) : 0u, gm_hi = g >= 4 ? 0xffu << (8u * (g - 4u)) : 0u;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_lo));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_hi));
-    uint32_t k255 = 255u, k65536 = 0x10000u;
-    uint32_t sel_a = 0x03020703u, sel_b = 0x03070100u, sel_c = 0x07020100u;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_a));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_b));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sel_c));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k255));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k65536));
+    const WordGroupLane L(t0_bytes, wave, g);
+    const uint32_t ring = L.ring, bias = L.bias, gm_lo = L.gm_lo, gm_hi = L.gm_hi, k255 = L.k255, k65536 = L.k65536;
+    const uint32_t sel_a = L.sel_a, sel_b = L.sel_b, sel_c = L.sel_c;
 
     const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
     const uint64_t glo = cbase & ~uint64_t(15), glimit = (cbase + p.container_bytes + 15u) & ~uint64_t(15);
@@ -459,104 +318,35 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_word_groups(con
     const uint32_t sel2 = (lane & 2u) ? 0x03020706u : 0x05040100u;
     const uint64_t octets = (p.nchunks + 7u) >> 3; // one per claim (the last one may hold fewer than eight streams)
 
-    auto load16 = [&](uint64_t a) -> u32x4 { // 16 bytes of the container, zeros beyond its granules
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (a >= glo && a < glimit)
-            v = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(a));
-        return v;
-    };
-    auto wave_max = [&](uint32_t v) -> uint32_t { // over the eight groups (v is the same in a group's lanes)
-        uint32_t m = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const uint32_t t = __builtin_amdgcn_readlane(v, 8 * k);
-            m = t > m ? t : m;
-        }
-        return m;
-    };
-
     uint32_t nbad = 0;
-    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
-    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
-    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
-    const uint32_t pool = blockIdx.x % npools;
+    WorkClaims work;
+    work.init(p.work_counter, wave, waves_per_block);
     for (;;) {
-        uint64_t octet; // (handed out as in k_decode_word_groups: the pooled counter, or a static stride without one)
-        if (p.work_counter) {
-            uint32_t got = 0;
-            if (lane == 0)
-                got = atomicAdd(p.work_counter + pool * kWorkPoolStride, 1u);
-            octet = (uint64_t)uniform(got) * npools + pool;
-        } else {
-            octet = uniform64(claim_v);
-            claim_v += total_waves;
-        }
+        const uint64_t octet = work.take(lane);
         if (octet >= octets)
             break;
         // ---- this group's stream: its index entries, all of them the caller's data
-        const uint64_t pos = octet * 8u + g;
-        const bool exists = pos < p.nchunks;
-        uint64_t s = pos;
-        if (exists && p.order)
-            s = p.order[pos];
-        bool valid = exists && s < p.nchunks;
-        uint64_t off = 0, first = 0;
-        uint32_t len = 0, count = 0;
-        if (valid) {
-            off = p.offsets[s];
-            len = p.lengths[s];
-            first = p.sym_offsets[s];
-            count = p.sym_counts[s];
-        }
-        valid = valid && (off & 1u) == 0 && len >= 8u * 4u && off <= p.container_bytes && len <= p.container_bytes - off &&
-                first <= p.out_syms && count <= p.out_syms - first;
+        bool exists, valid;
+        uint64_t off, first;
+        uint32_t len, count;
+        fetch_stream_entry<8u * 4u, true>(p, octet * 8u + g, exists, valid, off, first, len, count);
         if (exists && !valid && i == 0)
             nbad++;
         const uint64_t src = cbase + (valid ? off : 0u);
         uint32_t x = Tr::kL;
         if (valid) // RansDecInit order: state 0 first (rans_word_sse41.h:104-113)
             x = reinterpret_cast<const uint32_t RANS_GLOBAL *>(src)[i];
-        // the ring, its positions and its refills: k_decode_word_groups' (a group without a valid stream fetches nothing)
-        const uint64_t abase = src & ~uint64_t(kGrpBlock - 1u);
-        const uint32_t start = (uint32_t)(src - abase) + 8u * 4u; // < 160
-        uint32_t curw = (start + bias) >> 1;
-        uint64_t ld = abase + 16u * i;
-        u32x4 b0 = {0u, 0u, 0u, 0u}, b1 = b0, pend = b0;
-        if (valid) {
-            b0 = load16(ld);
-            b1 = load16(ld + kGrpBlock);
-            pend = load16(ld + 2u * kGrpBlock);
-        }
-        ld += 3u * kGrpBlock;
-        uint32_t left = 0;
-        if (valid && ld < glimit) {
-            const uint64_t pieces = (glimit - ld + (kGrpBlock - 1u)) / kGrpBlock;
-            left = pieces < 0x7fffffffu ? (uint32_t)pieces : 0x7fffffffu;
-        }
-        *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)(ring | ((16u * i + bias) & 255u))) = b0;
-        *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)(ring | ((kGrpBlock + 16u * i + bias) & 255u))) = b1;
-        uint32_t wr = ring | ((16u * i + bias) & 255u);
-        uint32_t thr = (kGrpBlock + bias) >> 1;
-        auto checkpoint = [&]() {
-            if (curw >= thr) { // (the same for the eight lanes of a group; never true for a parked group: its cursor stands still)
-                *reinterpret_cast<RANS_LDS u32x4 *>((uintptr_t)wr) = pend;
-                wr ^= kGrpBlock;
-                thr += kGrpBlock / 2u;
-                if (left) {
-                    pend = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(ld));
-                    left--;
-                }
-                ld += kGrpBlock;
-            }
-        };
-        checkpoint(); // the states may end in block 1
+        WordRing R; // (a group without a valid stream fetches nothing)
+        const uint32_t start = R.open(src, i, ring, bias, valid, glo, glimit);
+        uint32_t &curw = R.curw;
+        auto checkpoint = [&]() { R.checkpoint(); };
         const uint32_t end2 = len + bias + (start - 8u * 4u); // twice the (biased) cursor at the end of the stream
 
         // ---- the group's own counts: whole lines through the common loop, the rest a round at a time
         const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + first; // (valid: [dst, dst + count) lies inside the output)
         const uint32_t blocks = (valid && (dst & 3u) == 0) ? count >> 7 : 0u;
         const uint32_t tail = valid ? count - (blocks << 7) : 0u;
-        const uint32_t max_blocks = wave_max(blocks), max_tail = wave_max(tail);
+        const uint32_t max_blocks = wave_max8(blocks), max_tail = wave_max8(tail);
         uint64_t line = dst + 16u * i; // this lane's 16 bytes of the group's next line
         uint32_t m_lo = gm_lo, m_hi = gm_hi;
         for (uint32_t q = 0; q < max_blocks; ++q) {
@@ -573,18 +363,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_word_groups(con
             a1 = quad_transpose(a1, sel1, sel2);
             a2 = quad_transpose(a2, sel1, sel2);
             a3 = quad_transpose(a3, sel1, sel2);
-            u32x4 v; // (the half-group exchange of k_decode_word_groups, under full exec: see there)
-            asm volatile("s_nop 1\n\t"
-                         "s_mov_b64 vcc, %[lower]\n\t"
-                         "v_cndmask_b32_dpp %[vx], %[a2], %[a0], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "v_cndmask_b32_dpp %[vz], %[a3], %[a1], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "s_mov_b64 vcc, %[upper]\n\t"
-                         "v_cndmask_b32_dpp %[vy], %[a0], %[a2], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "v_cndmask_b32_dpp %[vw], %[a1], %[a3], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                         : [vx] "=&v"(v.x), [vy] "=&v"(v.y), [vz] "=&v"(v.z), [vw] "=&v"(v.w)
-                         : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [lower] "s"(0x0f0f0f0f0f0f0f0full),
-                           [upper] "s"(0xf0f0f0f0f0f0f0f0ull)
-                         : "vcc");
+            const u32x4 v = halves_to_line(a0, a1, a2, a3); // (under full exec: see there)
             // (plain stores: a stream starts anywhere on the 4-byte grid, so its lines straddle the memory's -- the case in which
             //  k_decode_word_groups leaves it to L2 to put the pieces together)
             if (run) {
@@ -601,16 +380,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_word_groups(con
                 checkpoint();
             const uint32_t r0 = rr << 3; // < max_tail
             const bool active = r0 < tail && i < tail - r0;
-            uint32_t raw = 0;
-            if (active)
-                raw = dec_step<FMT_WORD>(T, x);
-            const bool need = active && x < k65536;
-            const uint64_t m = __builtin_amdgcn_ballot_w64(need);
-            const uint32_t t_lo = (uint32_t)m & gm_lo, t_hi = (uint32_t)(m >> 32) & gm_hi;
-            const uint32_t at = __builtin_amdgcn_mbcnt_hi(t_hi, __builtin_amdgcn_mbcnt_lo(t_lo, curw));
-            curw += __builtin_popcount(t_lo) + __builtin_popcount(t_hi);
-            if (need)
-                x = (x << 16) | lds_u16(((at << 1) & k255) | ring);
+            const uint32_t raw = decode_word_round(T, x, curw, active, gm_lo, gm_hi, k255, k65536, ring);
             if (active)
                 *reinterpret_cast<uint8_t RANS_GLOBAL *>(tail_dst + r0 + i) = (uint8_t)(raw >> 24);
         }
@@ -641,10 +411,6 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_word_groups(con
 //     contiguous bytes per chunk.
 // Full chunks of a multiple of 4 symbols (what a size off 64 leaves goes one round at a time).
 // ---------------------------------------------------------------------------
-constexpr uint32_t kPairBlock = 32;              // bytes a pair fetches at a time: 2 lanes x 16 B
-constexpr uint32_t kPairRing = 2 * kPairBlock;   // per pair
-constexpr uint32_t kPairRow = kPairRing + 4;     // ring + the mirror byte; 17 dwords: equal positions of the 32 pairs on 32 banks
-constexpr uint32_t kPairWaveLds = 32 * kPairRow; // per wave
 constexpr int kPairAux = kAuxStore; // nt sc1, as the other decoders' symbol stores (plain stores: 0.94 ms against 0.73)
 
 // Eight rounds (one symbol per lane and round) as one hand-scheduled sequence; rans_byte.h:125-128 (get), :291-298 (advance),
@@ -791,48 +557,41 @@ __device__ __forceinline__ u32x4 quad_half(const u32x4 &lo, const u32x4 &hi)
     return o;
 }
 
+// sixteen rounds of a pair -> this lane's 16 of the pair's 32 bytes; the ring's row as PairRing takes it
+// (the refill check in front of the rounds here: behind them k_decode_byte_pairs is 1.5 % slower, k_decode_word_groups 3 % faster)
+template <class ROW> __device__ __forceinline__ u32x4 pair_sixteen(PairRing &R, uint32_t &x, const PairLane &L, const ROW &row, bool live)
+{
+    uint32_t a0, a1, a2, a3;
+    R.checkpoint(row, live);
+    decode_pairs_8rounds(x, R.cur, a0, a1, L.maskv, L.sbv, L.rec, L.l23, L.l15, L.ring);
+    R.checkpoint(row, live);
+    decode_pairs_8rounds(x, R.cur, a2, a3, L.maskv, L.sbv, L.rec, L.l23, L.l15, L.ring);
+    return pair_lines(a0, a1, a2, a3, L.sel_p);
+}
+
 __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_byte_pairs(const DecParams p)
 {
     using Tr = FmtTraits<FMT_BYTE>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // cum2sym u8[M]
     const uint32_t t1_bytes = (p.table1_bytes + 15u) & ~15u; // {freq, start}[nsyms]
-    {
-        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.table0);
-        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
-        for (uint32_t i = threadIdx.x; i < t0_bytes / 16u; i += blockDim.x)
-            l0[i] = g0[i];
-        const uint4 *g1 = reinterpret_cast<const uint4 *>(p.table1);
-        uint4 *l1 = reinterpret_cast<uint4 *>(smem + t0_bytes);
-        for (uint32_t i = threadIdx.x; i < t1_bytes / 16u; i += blockDim.x)
-            l1[i] = g1[i];
-    }
+    stage_table(smem, p.table0, t0_bytes);
+    stage_table(smem + t0_bytes, p.table1, t1_bytes);
     __syncthreads();
     if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never decode on a wrong assumption
         if (threadIdx.x == 0)
             atomicAdd(p.err_count, 1ull << 32);
         return;
     }
-    if (p.work_counter_reset && blockIdx.x == 0 && threadIdx.x < kWorkPools)
-        p.work_counter_reset[threadIdx.x * kWorkPoolStride] = 0u;
-    if (p.span_reset && blockIdx.x == 0 && threadIdx.x < 2)
-        p.span_reset[threadIdx.x] = 0ull;
+    reset_for_next_launch(p);
 
     const uint32_t lane = lane_id();
     const uint32_t wave = uniform(threadIdx.x >> 6);
     const uint32_t waves_per_block = blockDim.x >> 6;
     const uint32_t g = lane >> 1, i = lane & 1u;
     const uint32_t ring_c = t0_bytes + t1_bytes + wave * kPairWaveLds + g * kPairRow; // raw LDS byte address of the pair's ring
-    // per-lane constants in VGPRs (a VALU operand from an SGPR or a literal issues slower: profiles/r01_ubench.log)
-    uint32_t ring = ring_c, maskv = (1u << p.scale_bits) - 1u, sbv = p.scale_bits, rec = t0_bytes;
-    uint32_t l23 = 1u << 23, l15 = 1u << 15;
-    uint32_t sel_p = i ? 0x03070206u : 0x05010400u; // v_perm(theirs, mine): the pair's bytes in stream order
-    asm volatile("v_mov_b32 %0, %0" : "+v"(ring));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(maskv));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sbv));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(rec));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(l23));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(l15));
+    const PairLane L(ring_c, p.scale_bits, t0_bytes, i);
+    const uint32_t ring = L.ring, maskv = L.maskv, sbv = L.sbv, rec = L.rec, l23 = L.l23, l15 = L.l15, sel_p = L.sel_p;
 
     const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
     const uint64_t glo = cbase & ~uint64_t(15), glimit = (cbase + p.container_bytes + 15u) & ~uint64_t(15);
@@ -843,32 +602,12 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_byte_pairs(const DecP
     const uint32_t per_claim = uniform(p.chunk_syms >= kGrpClaimSyms / 32u ? 1u : (kGrpClaimSyms / 32u + p.chunk_syms - 1u) / p.chunk_syms);
     const uint64_t claims = (batches + per_claim - 1u) / per_claim;
 
-    auto load16 = [&](uint64_t a) -> u32x4 { // 16 bytes of the container, zeros beyond its granules
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (a >= glo && a < glimit)
-            v = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(a));
-        return v;
-    };
-
     uint32_t nbad = 0;
-    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
-    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
-    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
-    const uint32_t pool = blockIdx.x % npools;
-    auto claim_take = [&]() -> uint64_t { // (as in k_decode_word_groups)
-        if (p.work_counter) {
-            uint32_t got = 0;
-            if (lane == 0)
-                got = atomicAdd(p.work_counter + pool * kWorkPoolStride, 1u);
-            return (uint64_t)uniform(got) * npools + pool;
-        }
-        const uint64_t c = claim_v;
-        claim_v += total_waves;
-        return uniform64(c);
-    };
+    WorkClaims work;
+    work.init(p.work_counter, wave, waves_per_block);
     const bool ragged = p.n % p.chunk_syms != 0; // (as in k_decode_word_groups)
     for (;;) {
-        const uint64_t claim = claim_take();
+        const uint64_t claim = work.take(lane);
         if (claim >= claims)
             break;
         const uint64_t b_end = (claim + 1u) * per_claim < batches ? (claim + 1u) * per_claim : batches;
@@ -885,43 +624,11 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_byte_pairs(const DecP
             uint32_t x = Tr::kL;
             if (valid) // RansDecInit order: state 0 first (main.cpp:261-262)
                 x = reinterpret_cast<const uint32_t RANS_GLOBAL *>(src)[i];
-            // positions count from the 32-byte block of the chunk's first byte
-            const uint64_t abase = src & ~uint64_t(kPairBlock - 1u);
-            const uint32_t start = (uint32_t)(src - abase) + 2u * 4u; // < 40
-            uint32_t cur = start;
-            uint64_t ld = abase + 16u * i;
-            const u32x4 b0 = load16(ld), b1 = load16(ld + kPairBlock);
-            u32x4 pend = load16(ld + 2u * kPairBlock); // block 2; the ring holds blocks nb - 2 and nb - 1, pend is block nb
-            ld += 3u * kPairBlock;
-            uint32_t left = 0; // pieces at ld, ld + 32, ... inside the container's granules (as in k_decode_word_groups)
-            if (ld < glimit) {
-                const uint64_t pieces = (glimit - ld + (kPairBlock - 1u)) / kPairBlock;
-                left = pieces < 0x7fffffffu ? (uint32_t)pieces : 0x7fffffffu;
-            }
-            auto put = [&](uint32_t at, const u32x4 &v) { // (rows are 4-byte aligned: four dword writes)
-                RANS_LDS uint32_t *d = reinterpret_cast<RANS_LDS uint32_t *>((uintptr_t)(ring_c + at + 16u * i));
-                d[0] = v.x;
-                d[1] = v.y;
-                d[2] = v.z;
-                d[3] = v.w;
-                if (at == 0 && i == 0)
-                    *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(ring_c + kPairRing)) = (uint8_t)v.x;
-            };
-            put(0, b0);
-            put(kPairBlock, b1);
-            uint32_t thr = kPairBlock; // cursor from which block nb has to be in the ring; block nb goes to ring offset ~thr & 32
-            auto checkpoint = [&]() {
-                if (cur >= thr) { // (the same for both lanes of a pair)
-                    put(~thr & kPairBlock, pend);
-                    thr += kPairBlock;
-                    if (left) {
-                        pend = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(ld));
-                        left--;
-                    }
-                    ld += kPairBlock;
-                }
-            };
-            checkpoint(); // the states may end in block 1
+            PairRing R;
+            const PairRowOfLane row{ring_c, i};
+            const uint32_t start = R.open(src, i, row, true, glo, glimit);
+            uint32_t &cur = R.cur;
+            auto checkpoint = [&]() { R.checkpoint(row, true); };
 
             const rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(
                 reinterpret_cast<void *>(reinterpret_cast<uint64_t>(p.out) + batch * 32u * p.chunk_syms), 0, 32u * p.chunk_syms, kRsrcFlags);
@@ -931,14 +638,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_byte_pairs(const DecP
             const uint32_t off_a = valid_a ? (g & ~1u) * p.chunk_syms + 16u * (lane & 3u) : 0x80000000u;
             const uint32_t off_b = valid_b ? (g | 1u) * p.chunk_syms + 16u * (lane & 3u) : 0x80000000u;
             uint32_t osoff = 0;
-            auto sixteen = [&]() -> u32x4 { // 16 rounds -> this lane's 16 of the pair's 32 bytes
-                uint32_t a0, a1, a2, a3;
-                checkpoint(); // (in front of the rounds here: behind them this kernel is 1.5 % slower, k_decode_word_groups 3 % faster)
-                decode_pairs_8rounds(x, cur, a0, a1, maskv, sbv, rec, l23, l15, ring);
-                checkpoint();
-                decode_pairs_8rounds(x, cur, a2, a3, maskv, sbv, rec, l23, l15, ring);
-                return pair_lines(a0, a1, a2, a3, sel_p);
-            };
+            auto sixteen = [&]() -> u32x4 { return pair_sixteen(R, x, L, row, true); };
             // 64 rounds = one 128-byte line of the chunk: four 16-byte stores per lane leave back to back (a pair writes 32
             // contiguous bytes per instruction; pieces of a line that leave 16 or 32 rounds apart reach memory as partial
             // lines -- measured 1.18 ms against 0.70 without stores)
@@ -982,21 +682,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_byte_pairs(const DecP
                 if (((s0 - s_first) & 15u) == 0)
                     checkpoint();
                 const bool active = s0 + i < nsym;
-                uint32_t sy = 0, n = 0;
-                if (active) {
-                    const uint32_t cf = x & maskv; // rans_byte.h:125-128 (get), :291-298 (advance)
-                    sy = *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)cf);
-                    const u32x2 fr = *reinterpret_cast<RANS_LDS const u32x2 *>((uintptr_t)(rec + 8u * sy));
-                    x = (fr.x & 0xffffffu) * ((x >> sbv) & 0xffffffu) + cf - fr.y;
-                    n = (uint32_t)(x < l23) + (uint32_t)(x < l15); // rans_byte.h:307-318: state 0's bytes first
-                }
-                const uint32_t n_other = (uint32_t)__shfl_xor((int)n, 1, 64);
-                const uint32_t pos = cur + (i ? n_other : 0u);
-                cur += n + n_other;
-                if (n >= 1u)
-                    x = (x << 8) | *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)(ring_c + (pos & 63u)));
-                if (n >= 2u)
-                    x = (x << 8) | *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)(ring_c + ((pos + 1u) & 63u)));
+                const uint32_t sy = decode_pair_round<false>(x, cur, active, i, maskv, sbv, rec, l23, l15, ring_c, 0);
                 if (active)
                     __builtin_amdgcn_raw_buffer_store_b8((uint8_t)sy, orsrc, out_off16 - 16u * i + s0 + i, 0, 0);
             }
@@ -1049,54 +735,30 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
     const unsigned long long t_start = p.span ? wall_clock64() : 0ull;
     const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // cum2sym u8[M]
     const uint32_t t1_bytes = (p.table1_bytes + 15u) & ~15u; // {freq, start}[nsyms]
-    {
-        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.table0);
-        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
-        for (uint32_t i = threadIdx.x; i < t0_bytes / 16u; i += blockDim.x)
-            l0[i] = g0[i];
-        const uint4 *g1 = reinterpret_cast<const uint4 *>(p.table1);
-        uint4 *l1 = reinterpret_cast<uint4 *>(smem + t0_bytes);
-        for (uint32_t i = threadIdx.x; i < t1_bytes / 16u; i += blockDim.x)
-            l1[i] = g1[i];
-    }
+    stage_table(smem, p.table0, t0_bytes);
+    stage_table(smem + t0_bytes, p.table1, t1_bytes);
     __syncthreads();
     if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never decode on a wrong assumption
         if (threadIdx.x == 0)
             atomicAdd(p.err_count, 1ull << 32);
         return;
     }
-    if (p.work_counter_reset && blockIdx.x == 0 && threadIdx.x < kWorkPools)
-        p.work_counter_reset[threadIdx.x * kWorkPoolStride] = 0u;
-    if (p.span_reset && blockIdx.x == 0 && threadIdx.x < 2)
-        p.span_reset[threadIdx.x] = 0ull;
+    reset_for_next_launch(p);
 
     const uint32_t lane = lane_id();
     const uint32_t wave = uniform(threadIdx.x >> 6);
     const uint32_t waves_per_block = blockDim.x >> 6;
     const uint32_t ring_c = t0_bytes + t1_bytes + wave * kPairWaveLds + (lane >> 1) * kPairRow; // (as in k_decode_byte_pairs, the constants as well)
-    uint32_t ring = ring_c, maskv = (1u << p.scale_bits) - 1u, sbv = p.scale_bits, rec = t0_bytes;
-    uint32_t l23 = 1u << 23, l15 = 1u << 15;
-    uint32_t sel_p = (lane & 1u) ? 0x03070206u : 0x05010400u;
     uint32_t ring_i = ring_c + 16u * (lane & 1u); // where this lane's 16 bytes of a block go
-    asm volatile("v_mov_b32 %0, %0" : "+v"(ring_i));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(ring));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(maskv));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(sbv));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(rec));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(l23));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(l15));
+    pin_vgpr(ring_i);
+    const PairLane L(ring_c, p.scale_bits, t0_bytes, lane & 1u);
+    const uint32_t ring = L.ring, maskv = L.maskv, sbv = L.sbv, rec = L.rec, l23 = L.l23, l15 = L.l15, sel_p = L.sel_p;
 
     const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
     const uint64_t glo = cbase & ~uint64_t(15), glimit = (cbase + p.container_bytes + 15u) & ~uint64_t(15);
     const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 31u) >> 5); // wave-loads, one per claim (the last one may hold fewer than 32
                                                                          // streams); stream indices are 32-bit
 
-    auto load16 = [&](uint64_t a) -> u32x4 { // 16 bytes of the container, zeros beyond its granules
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (a >= glo && a < glimit)
-            v = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(a));
-        return v;
-    };
     // over the 32 pairs (v is the same in a pair's lanes): a butterfly over lane ^ 2, 4, 8, 16 inside each half of the wave
     // (ds_swizzle in bit-mask mode: and 0x1f, or 0, xor d -- no address register), then the larger of the two halves
     auto wave_max = [&](uint32_t v) -> uint32_t {
@@ -1121,26 +783,16 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
     };
 
     uint32_t nbad = 0;
-    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
-    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
-    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
-    const uint32_t pool = blockIdx.x % npools;
+    WorkClaims work;
+    work.init(p.work_counter, wave, waves_per_block);
     for (;;) {
-        uint64_t load; // (handed out as in k_decode_byte_pairs: the pooled counter, or a static stride without one)
-        if (p.work_counter) {
-            uint32_t got = 0;
-            if (lane == 0)
-                got = atomicAdd(p.work_counter + pool * kWorkPoolStride, 1u);
-            load = (uint64_t)uniform(got) * npools + pool;
-        } else {
-            load = uniform64(claim_v);
-            claim_v += total_waves;
-        }
+        const uint64_t load = work.take(lane);
         if ((load >> 32) != 0 || (uint32_t)load >= loads) // (scalar compares)
             break;
         // ---- this pair's stream: its index entries, all of them the caller's data
         const uint32_t ln = lane_now();
         const uint32_t g = ln >> 1, i = ln & 1u;
+        // (fetch_stream_entry<2 * 4, false>, written out: see the ring below)
         const uint64_t pos = load * 32u + g;
         const bool exists = pos < p.nchunks;
         uint64_t s = pos;
@@ -1163,16 +815,18 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
         uint32_t x = Tr::kL;
         if (valid) // RansDecInit order: state 0 first (main.cpp:261-262)
             x = reinterpret_cast<const uint32_t RANS_GLOBAL *>(src)[i];
-        // the ring, its positions and its refills: k_decode_byte_pairs' (a pair without a valid stream fetches nothing)
+        // The ring: PairRing's, but opened and checked here, on locals (a pair without a valid stream fetches nothing).  Through
+        // PairRing::open() / checkpoint() this kernel's claim set-up compiles differently and the launch is 0.4 % slower
+        // (profiles/groups_common_isa.md); put() and refill() are the shared ones.
         const uint64_t abase = src & ~uint64_t(kPairBlock - 1u);
         const uint32_t start = (uint32_t)(src - abase) + 2u * 4u; // < 40
         uint32_t cur = start;
         uint64_t ld = abase + 16u * i;
         u32x4 b0 = {0u, 0u, 0u, 0u}, b1 = b0, pend = b0;
         if (valid) {
-            b0 = load16(ld);
-            b1 = load16(ld + kPairBlock);
-            pend = load16(ld + 2u * kPairBlock);
+            b0 = load16(ld, glo, glimit);
+            b1 = load16(ld + kPairBlock, glo, glimit);
+            pend = load16(ld + 2u * kPairBlock, glo, glimit);
         }
         ld += 3u * kPairBlock;
         uint32_t left = 0;
@@ -1180,15 +834,9 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
             const uint64_t pieces = (glimit - ld + (kPairBlock - 1u)) / kPairBlock;
             left = pieces < 0x7fffffffu ? (uint32_t)pieces : 0x7fffffffu;
         }
-        auto put = [&](uint32_t at, const u32x4 &v) { // (rows are 4-byte aligned: four dword writes)
-            RANS_LDS uint32_t *d = reinterpret_cast<RANS_LDS uint32_t *>((uintptr_t)(ring_i + at));
-            d[0] = v.x;
-            d[1] = v.y;
-            d[2] = v.z;
-            d[3] = v.w;
-            if (at == 0 && ring_i == ring) // (the even lane)
-                *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(ring + kPairRing)) = (uint8_t)v.x;
-        };
+        const PairRowPinned row{ring, ring_i};
+        PairRing R;
+        auto put = [&](uint32_t at, const u32x4 &v) { R.put(row, at, v); };
         put(0, b0);
         put(kPairBlock, b1);
         uint32_t thr = kPairBlock;
@@ -1196,11 +844,13 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
             if (live && cur >= thr) {
                 put(~thr & kPairBlock, pend);
                 thr += kPairBlock;
-                if (left) {
-                    pend = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(ld));
-                    left--;
-                }
-                ld += kPairBlock;
+                R.ld = ld;
+                R.pend = pend;
+                R.left = left;
+                R.refill();
+                ld = R.ld;
+                pend = R.pend;
+                left = R.left;
             }
         };
         checkpoint(valid); // the states may end in block 1
@@ -1220,7 +870,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
         uint64_t line_b = ((uint64_t)from((uint32_t)(dst >> 32), lane_b) << 32 | from((uint32_t)dst, lane_b)) + 16u * (ln & 3u);
         const bool pair_b = (ln & 2u) != 0; // this lane's own stream is the quad's B
         bool run = false;
-        auto sixteen = [&]() -> u32x4 { // 16 rounds -> this lane's 16 of the pair's 32 bytes (k_decode_byte_pairs')
+        auto sixteen = [&]() -> u32x4 { // pair_sixteen() with this kernel's own checkpoint()
             uint32_t a0, a1, a2, a3;
             checkpoint(run);
             decode_pairs_8rounds(x, cur, a0, a1, maskv, sbv, rec, l23, l15, ring);
@@ -1267,21 +917,7 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
                 checkpoint(valid);
             const uint32_t s0 = rr << 1; // < max_tail
             const bool active = s0 < tail && it < tail - s0;
-            uint32_t sy = 0, n = 0;
-            if (active) {
-                const uint32_t cf = x & maskv; // rans_byte.h:125-128 (get), :291-298 (advance)
-                sy = *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)cf);
-                const u32x2 fr = *reinterpret_cast<RANS_LDS const u32x2 *>((uintptr_t)(rec + 8u * sy));
-                x = (fr.x & 0xffffffu) * ((x >> sbv) & 0xffffffu) + cf - fr.y;
-                n = (uint32_t)(x < l23) + (uint32_t)(x < l15); // rans_byte.h:307-318: state 0's bytes first
-            }
-            const uint32_t n_other = from(n, lane_o);
-            const uint32_t at = cur + (it ? n_other : 0u);
-            cur += n + n_other;
-            if (n >= 1u)
-                x = (x << 8) | *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)(ring + (at & 63u)));
-            if (n >= 2u)
-                x = (x << 8) | *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)(ring + ((at + 1u) & 63u)));
+            const uint32_t sy = decode_pair_round<true>(x, cur, active, it, maskv, sbv, rec, l23, l15, ring, lane_o);
             if (active)
                 *reinterpret_cast<uint8_t RANS_GLOBAL *>(tail_dst + s0 + it) = (uint8_t)sy;
         }
@@ -1308,20 +944,10 @@ bool decode_word_groups_applicable(const DecParams &p)
 
 hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {
-    const size_t table_lds = (p.table0_bytes + 15u) & ~15u;
-    const size_t lds = table_lds + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
-    auto kern = k_decode_word_groups;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
-        return e;
-    const uint32_t per_cu = 2u * lds <= 160u * 1024u ? 2u : 1u;
-    const uint64_t want_blocks = ((p.nchunks + 7u) / 8u + kGrpThreads / 64 - 1) / (kGrpThreads / 64);
-    const uint64_t cap = (uint64_t)num_cus * per_cu;
-    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
+    const size_t lds = ((p.table0_bytes + 15u) & ~15u) + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
     if (name)
         *name = "k_decode_word_groups";
-    RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
-    return hipGetLastError();
+    return launch_group_kernel<k_decode_word_groups>((p.nchunks + 7u) / 8u, lds, kGrpLdsCap, num_cus, stream, p);
 }
 
 // The ragged form: word format over u8 symbols (the caller has checked the format: the u16 kernel format is another one),
@@ -1334,74 +960,44 @@ bool decode_batch_word_groups_applicable(const DecParams &p)
 
 hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **group_batch_kernel)
 {
-    const size_t table_lds = (p.table0_bytes + 15u) & ~15u;
-    const size_t lds = table_lds + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
-    auto kern = k_decode_batch_word_groups;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
-        return e;
-    const uint32_t per_cu = 2u * lds <= 160u * 1024u ? 2u : 1u;
-    const uint64_t want_blocks = ((p.nchunks + 7u) / 8u + kGrpThreads / 64 - 1) / (kGrpThreads / 64); // one octet per wave
-    const uint64_t cap = (uint64_t)num_cus * per_cu;
-    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
+    const size_t lds = ((p.table0_bytes + 15u) & ~15u) + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
     if (group_batch_kernel)
         *group_batch_kernel = "k_decode_batch_word_groups";
-    RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
-    return hipGetLastError();
+    return launch_group_kernel<k_decode_batch_word_groups>((p.nchunks + 7u) / 8u, lds, kGrpLdsCap, num_cus, stream, p); // one octet per wave
 }
 
 // The same for the byte format's 2-way layout (cum2sym tables, scale_bits 8..16, u8 symbols).
+static size_t pair_lds(const DecParams &p) // both tables and the waves' ring rows
+{
+    return (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u) + (size_t)(kGrpThreads / 64) * kPairWaveLds;
+}
 bool decode_byte_pairs_applicable(const DecParams &p)
 {
-    const size_t tables = (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u);
     return p.n_ways == 2 && p.sym_bytes == 1 && p.scale_bits >= 8 && p.scale_bits <= 16 && (p.chunk_syms & 3u) == 0 &&
            p.chunk_syms >= 64 && p.chunk_syms <= (1u << 20) && (reinterpret_cast<uintptr_t>(p.out) & 3u) == 0 && p.n / p.chunk_syms >= 32 && !p.trace &&
-           tables + (size_t)(kGrpThreads / 64) * kPairWaveLds <= 160u * 1024u;
+           pair_lds(p) <= kGrpLdsCap;
 }
 
 hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
 {
-    const size_t tables = (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u);
-    const size_t lds = tables + (size_t)(kGrpThreads / 64) * kPairWaveLds;
-    auto kern = k_decode_byte_pairs;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
-        return e;
-    const uint32_t per_cu = 2u * lds <= 160u * 1024u ? 2u : 1u;
-    const uint64_t want_blocks = ((p.nchunks + 31u) / 32u + kGrpThreads / 64 - 1) / (kGrpThreads / 64);
-    const uint64_t cap = (uint64_t)num_cus * per_cu;
-    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
     if (name)
         *name = "k_decode_byte_pairs";
-    RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
-    return hipGetLastError();
+    return launch_group_kernel<k_decode_byte_pairs>((p.nchunks + 31u) / 32u, pair_lds(p), kGrpLdsCap, num_cus, stream, p);
 }
 
 // The ragged form: byte format over u8 symbols with the cum2sym tables (the caller has checked the format: the fused slot
 // records are another kernel format), from 32 streams on; any symbol count, any output address.
 bool decode_batch_byte_pairs_applicable(const DecParams &p)
 {
-    const size_t tables = (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u);
     return p.n_ways == 2 && p.sym_bytes == 1 && p.scale_bits >= 8 && p.scale_bits <= 16 && p.nchunks >= 32 && p.sym_offsets && p.sym_counts &&
-           !p.trace && tables + (size_t)(kGrpThreads / 64) * kPairWaveLds <= 160u * 1024u;
+           !p.trace && pair_lds(p) <= kGrpLdsCap;
 }
 
 hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **pair_batch_kernel)
 {
-    const size_t tables = (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u);
-    const size_t lds = tables + (size_t)(kGrpThreads / 64) * kPairWaveLds;
-    auto kern = k_decode_batch_byte_pairs;
-    static std::atomic<uint64_t> lds_ok{0};
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(kern), 160 * 1024, lds_ok); e != hipSuccess)
-        return e;
-    const uint32_t per_cu = 2u * lds <= 160u * 1024u ? 2u : 1u;
-    const uint64_t want_blocks = ((p.nchunks + 31u) / 32u + kGrpThreads / 64 - 1) / (kGrpThreads / 64); // one wave-load per wave
-    const uint64_t cap = (uint64_t)num_cus * per_cu;
-    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
     if (pair_batch_kernel)
         *pair_batch_kernel = "k_decode_batch_byte_pairs";
-    RANS_LAUNCH(kern, dim3(grid), dim3(kGrpThreads), lds, stream, p);
-    return hipGetLastError();
+    return launch_group_kernel<k_decode_batch_byte_pairs>((p.nchunks + 31u) / 32u, pair_lds(p), kGrpLdsCap, num_cus, stream, p); // one wave-load per wave
 }
 
 } // namespace rans_amd

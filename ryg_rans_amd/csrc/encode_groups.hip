@@ -28,15 +28,12 @@
 // No MFMA: integer, table-driven, serial per state.
 
 #include "decode_common.hpp"
+#include "groups_common.hpp"
 
 namespace rans_amd {
 
 namespace {
 
-constexpr uint32_t kEncGrpBlock = 128;               // bytes of a group's output block: 8 lanes x 16 B
-constexpr uint32_t kEncGrpRing = 2 * kEncGrpBlock;   // per group
-constexpr uint32_t kEncGrpWaveLds = 8 * kEncGrpRing; // per wave
-constexpr uint32_t kEncGrpThreads = 1024;
 constexpr uint32_t kEncGrpTable = 256 * 16;          // WordEncRec[256] at LDS address 0
 
 // Eight rounds, odd-numbered round first (accumulator B: rounds 15, 13, 11, 9 or 7, 5, 3, 1 -- bytes 3..0; accumulator A the
@@ -110,17 +107,35 @@ __device__ __forceinline__ void encode_octet_8rounds(uint32_t &x, uint32_t &c, u
 #undef RANS_GE_TAIL_SMALL
 #undef RANS_GE_HEAD
 
+// One 128-byte line of a group, last round first: the exchange and the transposes take the line apart into per-state bytes
+// (byte J of a_k: round 8 (k >> 1) + 2 J + (k & 1)), then two times eight rounds.  flush(have_bytes) is the kernel's
+// flush_block: the block that the LAST eight rounds of the line before may have finished leaves behind the wait for this
+// line's symbols -- in front of it the wait (s_waitcnt vmcnt(0), the compiler cannot count conditional stores) would be for a
+// store that has only just been issued.  (Never true for a dead group: it left with 64 fb >= c, and its c stands still.)
+template <bool SMALL, bool TRACK, class FLUSH>
+__device__ __forceinline__ void encode_line(const u32x4 &v, uint32_t &x, uint32_t &c, uint32_t &worst, const uint32_t &fb, uint32_t sel1, uint32_t sel2,
+                                            uint32_t k4, uint32_t m_lo, uint32_t m_hi, uint32_t k255, uint32_t ring, FLUSH &&flush)
+{
+    uint32_t a0, a1, a2, a3;
+    line_to_halves(v, a0, a1, a2, a3);
+    a0 = quad_transpose(a0, sel1, sel2);
+    a1 = quad_transpose(a1, sel1, sel2);
+    a2 = quad_transpose(a2, sel1, sel2);
+    a3 = quad_transpose(a3, sel1, sel2);
+    if (c >= 64u * (fb + 1u))
+        flush(2u * c);
+    encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a2, a3, k4, m_lo, m_hi, k255, ring); // rounds 15 .. 8
+    if (c >= 64u * (fb + 1u))
+        flush(2u * c);
+    encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a0, a1, k4, m_lo, m_hi, k255, ring); // rounds 7 .. 0
+}
+
 template <bool SMALL, bool TRACK>
-__global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_word_groups(const EncParams p)
+__global__ void __launch_bounds__(kGrpThreads, 8) k_encode_word_groups(const EncParams p)
 {
     using Tr = FmtTraits<FMT_WORD>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    {
-        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.word_enc_recs);
-        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
-        for (uint32_t i = threadIdx.x; i < kEncGrpTable / 16u; i += blockDim.x)
-            l0[i] = g0[i];
-    }
+    stage_table(smem, p.word_enc_recs, kEncGrpTable);
     __syncthreads();
     if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never code on a wrong assumption
         if (threadIdx.x == 0)
@@ -131,15 +146,13 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_word_groups(const 
     const uint32_t wave = uniform(threadIdx.x >> 6);
     const uint32_t waves_per_block = blockDim.x >> 6;
     const uint32_t g = lane >> 3, i = lane & 7u;
-    const uint32_t ring_c = kEncGrpTable + wave * kEncGrpWaveLds + g * kEncGrpRing; // raw LDS address of the group's ring (256-byte aligned)
+    const uint32_t ring_c = kEncGrpTable + wave * kGrpWaveLds + g * kGrpRing; // raw LDS address of the group's ring (256-byte aligned)
     uint32_t ring = ring_c;
-    uint32_t gm_lo = g < 4 ? 0xffu << (8u * g) : 0u, gm_hi = g >= 4 ? 0xffu << (8u * (g - 4u)) : 0u;
-    uint32_t k255 = 255u, k4 = 4u;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(ring)); // opaque: keep them in VGPRs
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_lo));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_hi));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k255));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k4));
+    uint32_t gm_lo, gm_hi, k255 = 255u, k4 = 4u;
+    pin_vgpr(ring);
+    group_ballot_bits(g, gm_lo, gm_hi);
+    pin_vgpr(k255);
+    pin_vgpr(k4);
     const uint32_t sel1 = (lane & 1u) ? 0x03070105u : 0x06020400u;
     const uint32_t sel2 = (lane & 2u) ? 0x03020706u : 0x05040100u;
     const uint32_t lines = uniform(p.chunk_syms >> 7); // 16 rounds of 8 symbols each
@@ -148,24 +161,15 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_word_groups(const 
     const bool ragged = p.n % p.chunk_syms != 0; // the input's last chunk is short: its octet takes the round-by-round path
 
     uint32_t worst = 0;
-    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
-    uint64_t octet_v = (uint64_t)blockIdx.x * waves_per_block + wave;
-    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
-    const uint32_t pool = blockIdx.x % npools;
+    WorkClaims work;
+    work.init(p.claims, wave, waves_per_block); // (the dynamic hand-out as in the decoders)
     // a claim covers at least 8192 symbols (one atomic unit retires ~90 claims per microsecond)
     const uint32_t per_claim = uniform(p.chunk_syms >= 1024u ? 1u : (1024u + p.chunk_syms - 1u) / p.chunk_syms);
     const uint64_t claims = (octets + per_claim - 1u) / per_claim;
     for (;;) {
-        if (p.claims) { // dynamic hand-out (pool = blockIdx % 8 owns the claims c with c % 8 == pool), as in the decoders
-            uint32_t got = 0;
-            if (lane == 0)
-                got = atomicAdd(p.claims + pool * kWorkPoolStride, 1u);
-            octet_v = (uint64_t)uniform(got) * npools + pool;
-        }
-        if (octet_v >= claims)
+        const uint64_t claim = work.take(lane);
+        if (claim >= claims)
             break;
-        const uint64_t claim = uniform64(octet_v);
-        octet_v += total_waves;
         const uint64_t o_end = (claim + 1u) * per_claim < octets ? (claim + 1u) * per_claim : octets;
         for (uint64_t vk = claim * per_claim; vk < o_end; ++vk) {
             // (a ragged last chunk: its octet takes three times an octet's usual time -- the work is dealt back to front then, and
@@ -183,65 +187,18 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_word_groups(const 
             // block fb of the ring -> its place below the slot's end; a piece that would start below the slot's first byte is dropped
             // (sized slots: the chunk then does not fit, its length says so at the end)
             auto flush_block = [&](uint32_t have_bytes) { // have_bytes: the group's stream so far
-                const uint32_t below = kEncGrpBlock * (fb + 1u) - 16u * i; // this lane's piece starts `below` bytes under the slot's end
+                const uint32_t below = kGrpBlock * (fb + 1u) - 16u * i; // this lane's piece starts `below` bytes under the slot's end
                 if (valid && below <= slot && below - 16u < have_bytes) {
-                    const u32x4 v = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(ring_c + ((fb & 1u) ? 0u : kEncGrpBlock) + 16u * i));
+                    const u32x4 v = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(ring_c + ((fb & 1u) ? 0u : kGrpBlock) + 16u * i));
                     __builtin_amdgcn_raw_buffer_store_b128(v, orsrc, slot_end - below, 0, 0);
                 }
                 fb += 1u;
             };
             auto sixteen = [&](const u32x4 &v) { // one 128-byte line of the chunk, last round first
-                uint32_t a0, a1, a2, a3;
-                // rows 2 i, 2 i + 1 of the line -> this state's column: the halves of the group swap what the decoder's output
-                // exchange gave them (decode_groups.hip), then the quad transposes
-                asm volatile("s_nop 1\n\t"
-                             "s_mov_b64 vcc, %[lower]\n\t"
-                             "v_cndmask_b32_dpp %[a0], %[vy], %[vx], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" // lower ? mine : y of lane - 4
-                             "v_cndmask_b32_dpp %[a1], %[vw], %[vz], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                             "s_mov_b64 vcc, %[upper]\n\t"
-                             "v_cndmask_b32_dpp %[a2], %[vx], %[vy], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t" // upper ? mine : x of lane + 4
-                             "v_cndmask_b32_dpp %[a3], %[vz], %[vw], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                             : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3)
-                             : [vx] "v"(v.x), [vy] "v"(v.y), [vz] "v"(v.z), [vw] "v"(v.w), [lower] "s"(0x0f0f0f0f0f0f0f0full),
-                               [upper] "s"(0xf0f0f0f0f0f0f0f0ull)
-                             : "vcc");
-                a0 = quad_transpose(a0, sel1, sel2); // byte J of a_k: round 8 (k >> 1) + 2 J + (k & 1)
-                a1 = quad_transpose(a1, sel1, sel2);
-                a2 = quad_transpose(a2, sel1, sel2);
-                a3 = quad_transpose(a3, sel1, sel2);
-                // (the block that the LAST eight rounds of the line before may have finished leaves here, behind the wait for this
-                //  line's symbols: in front of it the wait -- s_waitcnt vmcnt(0), the compiler cannot count conditional stores -- would
-                //  be for a store that has only just been issued)
-                if (c >= 64u * (fb + 1u))
-                    flush_block(2u * c);
-                encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a2, a3, k4, gm_lo, gm_hi, k255, ring); // rounds 15 .. 8
-                if (c >= 64u * (fb + 1u))
-                    flush_block(2u * c);
-                encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a0, a1, k4, gm_lo, gm_hi, k255, ring); // rounds 7 .. 0
+                encode_line<SMALL, TRACK>(v, x, c, worst, fb, sel1, sel2, k4, gm_lo, gm_hi, k255, ring, flush_block);
             };
-            // one round of the compiler-scheduled kind: lanes without a symbol sit it out (main_simd.cpp:287-300 with in_size % 8 !=
-            // 0: the partial round belongs to states 0 .. in_size % 8 - 1).  For what a chunk size off 128 leaves, and for the
-            // input's last octet when its last chunk is a ragged one.
-            auto one_round = [&](uint32_t sym, bool active) {
-                const u32x4 rec = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(sym << 4));
-                const bool emit = active && x > rec.y; // rans_word_sse41.h:85
-                const uint64_t m = __builtin_amdgcn_ballot_w64(emit);
-                const uint32_t t_lo = (uint32_t)m & gm_lo, t_hi = (uint32_t)(m >> 32) & gm_hi;
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(t_hi, __builtin_amdgcn_mbcnt_lo(t_lo, 0u));
-                c += (uint32_t)__builtin_popcount(t_lo) + (uint32_t)__builtin_popcount(t_hi);
-                if (emit) {
-                    *reinterpret_cast<RANS_LDS uint16_t *>((uintptr_t)(ring_c | ((2u * (rank - c)) & 255u))) = (uint16_t)x;
-                    x >>= 16;
-                }
-                if (active) { // encode_common.hpp RANS_ENC_WORD_TAIL_*: x += bias + (x / freq) * cmpl
-                    uint32_t q = __umulhi(x, rec.x);
-                    if constexpr (!SMALL)
-                        q += (x - q) >> 1;
-                    q >>= rec.z >> 24;
-                    x = x + rec.w + (q & 0xffffffu) * (rec.z & 0xffffffu);
-                    worst |= rec.z;
-                }
-            };
+            // (for what a chunk size off 128 leaves, and for the input's last octet when its last chunk is a ragged one)
+            auto one_round = [&](uint32_t sym, bool active) { encode_word_round<SMALL>(x, c, worst, sym, active, gm_lo, gm_hi, ring_c); };
             const uint8_t RANS_GLOBAL *src = (const uint8_t RANS_GLOBAL *)p.syms + chunk * p.chunk_syms;
             if (octet + 1u == octets && ragged) { // one octet of the whole input: a byte load per lane and round
                 uint32_t nsym = 0;
@@ -335,16 +292,11 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_word_groups(const 
 typedef uint32_t u32x4_sym __attribute__((ext_vector_type(4), aligned(4))); // a line piece on the 4-byte grid
 
 template <bool SMALL, bool TRACK>
-__global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_batch_word_groups(const EncParams p)
+__global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_word_groups(const EncParams p)
 {
     using Tr = FmtTraits<FMT_WORD>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    {
-        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.word_enc_recs);
-        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
-        for (uint32_t i = threadIdx.x; i < kEncGrpTable / 16u; i += blockDim.x)
-            l0[i] = g0[i];
-    }
+    stage_table(smem, p.word_enc_recs, kEncGrpTable);
     __syncthreads();
     if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never code on a wrong assumption
         if (threadIdx.x == 0)
@@ -355,45 +307,22 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_batch_word_groups(
     const uint32_t wave = uniform(threadIdx.x >> 6);
     const uint32_t waves_per_block = blockDim.x >> 6;
     const uint32_t g = lane >> 3, i = lane & 7u;
-    const uint32_t ring_c = kEncGrpTable + wave * kEncGrpWaveLds + g * kEncGrpRing; // (as in k_encode_word_groups)
+    const uint32_t ring_c = kEncGrpTable + wave * kGrpWaveLds + g * kGrpRing; // (as in k_encode_word_groups)
     uint32_t ring = ring_c;
-    uint32_t gm_lo = g < 4 ? 0xffu << (8u * g) : 0u, gm_hi = g >= 4 ? 0xffu << (8u * (g - 4u)) : 0u;
-    uint32_t k255 = 255u, k4 = 4u;
-    asm volatile("v_mov_b32 %0, %0" : "+v"(ring)); // opaque: keep them in VGPRs
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_lo));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(gm_hi));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k255));
-    asm volatile("v_mov_b32 %0, %0" : "+v"(k4));
+    uint32_t gm_lo, gm_hi, k255 = 255u, k4 = 4u;
+    pin_vgpr(ring);
+    group_ballot_bits(g, gm_lo, gm_hi);
+    pin_vgpr(k255);
+    pin_vgpr(k4);
     const uint32_t sel1 = (lane & 1u) ? 0x03070105u : 0x06020400u;
     const uint32_t sel2 = (lane & 2u) ? 0x03020706u : 0x05040100u;
     const uint64_t octets = (p.nchunks + 7u) >> 3; // one per claim (the last one may hold fewer than eight streams)
 
-    auto wave_max = [&](uint32_t v) -> uint32_t { // over the eight groups (v is the same in a group's lanes)
-        uint32_t m = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const uint32_t t = __builtin_amdgcn_readlane(v, 8 * k);
-            m = t > m ? t : m;
-        }
-        return m;
-    };
-
     uint32_t worst = 0;
-    const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
-    uint64_t claim_v = (uint64_t)blockIdx.x * waves_per_block + wave;
-    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
-    const uint32_t pool = blockIdx.x % npools;
+    WorkClaims work;
+    work.init(p.claims, wave, waves_per_block);
     for (;;) {
-        uint64_t octet; // (handed out as in k_encode_word_groups: the pooled counters, or a static stride without them)
-        if (p.claims) {
-            uint32_t got = 0;
-            if (lane == 0)
-                got = atomicAdd(p.claims + pool * kWorkPoolStride, 1u);
-            octet = (uint64_t)uniform(got) * npools + pool;
-        } else {
-            octet = uniform64(claim_v);
-            claim_v += total_waves;
-        }
+        const uint64_t octet = work.take(lane);
         if (octet >= octets)
             break;
         // ---- this group's stream: its index entries, all of them the caller's data
@@ -430,40 +359,21 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_batch_word_groups(
         const uint32_t blocks = (live && (src & 3u) == 0) ? count >> 7 : 0u;
         const uint32_t tail = live ? count - (blocks << 7) : 0u;
         const uint32_t tail_rounds = (uint32_t)(((uint64_t)tail + 7u) >> 3);
-        const uint32_t max_blocks = wave_max(blocks), max_tail_rounds = wave_max(tail_rounds);
+        const uint32_t max_blocks = wave_max8(blocks), max_tail_rounds = wave_max8(tail_rounds);
 
         uint32_t x = Tr::kL, c = 0, fb = 0; // state, words emitted so far (the group's), blocks flushed
         uint32_t m_lo = live ? gm_lo : 0u, m_hi = live ? gm_hi : 0u; // my group's bits of the ballot; none once it is dead
         // block fb of the ring -> its place below the slot's end; a piece that would start below the slot's first byte is dropped,
         // and so is one that lies wholly below the stream (k_encode_word_groups' two guards); nothing leaves a dead group
         auto flush_block = [&](uint32_t have_bytes) { // have_bytes: the group's stream so far
-            const uint64_t below = (uint64_t)kEncGrpBlock * (fb + 1u) - 16u * i; // this lane's piece starts `below` bytes under the slot's end
+            const uint64_t below = (uint64_t)kGrpBlock * (fb + 1u) - 16u * i; // this lane's piece starts `below` bytes under the slot's end
             if (live && below <= slot && below - 16u < have_bytes) {
-                const u32x4 v = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(ring_c + ((fb & 1u) ? 0u : kEncGrpBlock) + 16u * i));
+                const u32x4 v = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(ring_c + ((fb & 1u) ? 0u : kGrpBlock) + 16u * i));
                 *reinterpret_cast<u32x4 RANS_GLOBAL *>(out_end - below) = v;
             }
             fb += 1u;
         };
-        auto one_round = [&](uint32_t sym, bool active) { // (k_encode_word_groups' one_round, the ballot cut by m_lo / m_hi)
-            const u32x4 rec = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(sym << 4));
-            const bool emit = active && x > rec.y; // rans_word_sse41.h:85
-            const uint64_t m = __builtin_amdgcn_ballot_w64(emit);
-            const uint32_t t_lo = (uint32_t)m & m_lo, t_hi = (uint32_t)(m >> 32) & m_hi;
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi(t_hi, __builtin_amdgcn_mbcnt_lo(t_lo, 0u));
-            c += (uint32_t)__builtin_popcount(t_lo) + (uint32_t)__builtin_popcount(t_hi);
-            if (emit) {
-                *reinterpret_cast<RANS_LDS uint16_t *>((uintptr_t)(ring_c | ((2u * (rank - c)) & 255u))) = (uint16_t)x;
-                x >>= 16;
-            }
-            if (active) { // encode_common.hpp RANS_ENC_WORD_TAIL_*: x += bias + (x / freq) * cmpl
-                uint32_t q = __umulhi(x, rec.x);
-                if constexpr (!SMALL)
-                    q += (x - q) >> 1;
-                q >>= rec.z >> 24;
-                x = x + rec.w + (q & 0xffffffu) * (rec.z & 0xffffffu);
-                worst |= rec.z;
-            }
-        };
+        auto one_round = [&](uint32_t sym, bool active) { encode_word_round<SMALL>(x, c, worst, sym, active, m_lo, m_hi, ring_c); };
         // ---- tail: the rounds behind the stream's last whole line, the group's last round first
         {
             const uint8_t RANS_GLOBAL *tsrc = reinterpret_cast<const uint8_t RANS_GLOBAL *>(src + ((uint64_t)blocks << 7) + i);
@@ -482,7 +392,7 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_batch_word_groups(
         auto load_line = [&](bool want) -> u32x4 {
             u32x4 v = {0u, 0u, 0u, 0u}; // (a dead group codes zeros)
             if (want) {
-                lp -= kEncGrpBlock;
+                lp -= kGrpBlock;
                 const u32x4_sym t = __builtin_nontemporal_load(reinterpret_cast<const u32x4_sym RANS_GLOBAL *>(lp));
                 v = u32x4{t.x, t.y, t.z, t.w};
             }
@@ -516,29 +426,7 @@ __global__ void __launch_bounds__(kEncGrpThreads, 8) k_encode_batch_word_groups(
             const u32x4 v = next;
             next = load_line(q + 1u < blocks);
             const uint32_t worst_keep = worst;
-            uint32_t a0, a1, a2, a3;
-            // rows 2 i, 2 i + 1 of the line -> this state's column (k_encode_word_groups' exchange, under full exec: see there)
-            asm volatile("s_nop 1\n\t"
-                         "s_mov_b64 vcc, %[lower]\n\t"
-                         "v_cndmask_b32_dpp %[a0], %[vy], %[vx], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "v_cndmask_b32_dpp %[a1], %[vw], %[vz], vcc row_shr:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "s_mov_b64 vcc, %[upper]\n\t"
-                         "v_cndmask_b32_dpp %[a2], %[vx], %[vy], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-                         "v_cndmask_b32_dpp %[a3], %[vz], %[vw], vcc row_shl:4 row_mask:0xf bank_mask:0xf bound_ctrl:1"
-                         : [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3)
-                         : [vx] "v"(v.x), [vy] "v"(v.y), [vz] "v"(v.z), [vw] "v"(v.w), [lower] "s"(0x0f0f0f0f0f0f0f0full),
-                           [upper] "s"(0xf0f0f0f0f0f0f0f0ull)
-                         : "vcc");
-            a0 = quad_transpose(a0, sel1, sel2); // byte J of a_k: round 8 (k >> 1) + 2 J + (k & 1)
-            a1 = quad_transpose(a1, sel1, sel2);
-            a2 = quad_transpose(a2, sel1, sel2);
-            a3 = quad_transpose(a3, sel1, sel2);
-            if (c >= 64u * (fb + 1u)) // (never true for a dead group: it left with 64 fb >= c, and its c stands still)
-                flush_block(2u * c);
-            encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a2, a3, k4, m_lo, m_hi, k255, ring); // rounds 15 .. 8
-            if (c >= 64u * (fb + 1u))
-                flush_block(2u * c);
-            encode_octet_8rounds<SMALL, TRACK>(x, c, worst, a0, a1, k4, m_lo, m_hi, k255, ring); // rounds 7 .. 0
+            encode_line<SMALL, TRACK>(v, x, c, worst, fb, sel1, sel2, k4, m_lo, m_hi, k255, ring, flush_block); // (under full exec: see there)
             worst = run ? worst : worst_keep;
         }
     }
@@ -557,27 +445,26 @@ bool encode_word_groups_applicable(const EncParams &p)
            (p.slot_bytes & 15u) == 0 && p.slot_bytes >= 48 && p.slot_bytes < (1ull << 28);
 }
 
+// The SMALL / TRACK instantiation a request takes, out of the kernel's four launches [SMALL][TRACK] (word_small: the round-up
+// reciprocal is not needed; dense256: every byte value has a record, nothing to track), and its launch: one octet per wave,
+// the default dynamic-LDS limit, two blocks per CU.
+using EncGroupLaunch = hipError_t (*)(uint64_t, size_t, uint32_t, int, hipStream_t, const EncParams &);
+static hipError_t launch_encode_groups(const EncGroupLaunch (&launches)[2][2], const EncParams &p, int num_cus, hipStream_t stream)
+{
+    const size_t lds = kEncGrpTable + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
+    return launches[p.word_small != 0][p.dense256 == 0]((p.nchunks + 7u) / 8u, lds, 0, num_cus, stream, p);
+}
+
 hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **name)
 {
     if (!p.word_enc_recs || (reinterpret_cast<uintptr_t>(p.scratch) & 15u) != 0)
         return hipErrorInvalidValue;
-    const size_t lds = kEncGrpTable + (size_t)(kEncGrpThreads / 64) * kEncGrpWaveLds;
-    const uint64_t octets = (p.nchunks + 7u) / 8u;
-    const uint64_t want_blocks = (octets + kEncGrpThreads / 64 - 1) / (kEncGrpThreads / 64);
-    const uint64_t cap = (uint64_t)num_cus * 2u;
-    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
     if (name)
         *name = "k_encode_word_groups";
-    const bool small = p.word_small != 0, track = p.dense256 == 0;
-    if (small && track)
-        RANS_LAUNCH((k_encode_word_groups<true, true>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    else if (small)
-        RANS_LAUNCH((k_encode_word_groups<true, false>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    else if (track)
-        RANS_LAUNCH((k_encode_word_groups<false, true>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    else
-        RANS_LAUNCH((k_encode_word_groups<false, false>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    return hipGetLastError();
+    static const EncGroupLaunch launches[2][2] = {
+        {launch_group_kernel<k_encode_word_groups<false, false>, EncParams>, launch_group_kernel<k_encode_word_groups<false, true>, EncParams>},
+        {launch_group_kernel<k_encode_word_groups<true, false>, EncParams>, launch_group_kernel<k_encode_word_groups<true, true>, EncParams>}};
+    return launch_encode_groups(launches, p, num_cus, stream);
 }
 
 // the ragged form: the reference's 8-way word layout over u8 symbols at 12 bits, from eight streams on (everything else stays
@@ -592,23 +479,12 @@ hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipS
 {
     if (!encode_batch_word_groups_applicable(p) || !p.sym_offsets || !p.sym_counts || !p.slot_offsets || !p.lengths || !p.offsets || !p.flags)
         return hipErrorInvalidValue;
-    const size_t lds = kEncGrpTable + (size_t)(kEncGrpThreads / 64) * kEncGrpWaveLds;
-    const uint64_t octets = (p.nchunks + 7u) / 8u;
-    const uint64_t want_blocks = (octets + kEncGrpThreads / 64 - 1) / (kEncGrpThreads / 64);
-    const uint64_t cap = (uint64_t)num_cus * 2u;
-    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
     if (group_batch_enc_kernel)
         *group_batch_enc_kernel = "k_encode_batch_word_groups";
-    const bool small = p.word_small != 0, track = p.dense256 == 0;
-    if (small && track)
-        RANS_LAUNCH((k_encode_batch_word_groups<true, true>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    else if (small)
-        RANS_LAUNCH((k_encode_batch_word_groups<true, false>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    else if (track)
-        RANS_LAUNCH((k_encode_batch_word_groups<false, true>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    else
-        RANS_LAUNCH((k_encode_batch_word_groups<false, false>), dim3(grid), dim3(kEncGrpThreads), lds, stream, p);
-    return hipGetLastError();
+    static const EncGroupLaunch launches[2][2] = {
+        {launch_group_kernel<k_encode_batch_word_groups<false, false>, EncParams>, launch_group_kernel<k_encode_batch_word_groups<false, true>, EncParams>},
+        {launch_group_kernel<k_encode_batch_word_groups<true, false>, EncParams>, launch_group_kernel<k_encode_batch_word_groups<true, true>, EncParams>}};
+    return launch_encode_groups(launches, p, num_cus, stream);
 }
 
 } // namespace rans_amd

@@ -13,8 +13,12 @@ equal.  Without --old / --new both sides take the files named (default: decode_w
 
 --new-default-false: the kernel templates of the tree gained a trailing `bool = false` template argument since the revision
 (a RAGGED form, say).  A kernel of the tree whose last template argument is `false` is then paired under the name it had
-without that argument; the instantiations with `true` stay what they are, kernels only the tree has."""
+without that argument; the instantiations with `true` stay what they are, kernels only the tree has.
+
+--ranges: behind the table, for every kernel whose opcode sequence DIFFERS, the index ranges of the opcodes that differ
+(old range -> new range, indices into the kernel's opcode list as counted in the `instructions` column)."""
 import argparse
+import difflib
 import os
 import re
 import subprocess
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--new", nargs="+", help="files of the new side, in the working tree")
     ap.add_argument("--new-default-false", action="store_true",
                     help="pair a kernel of the tree whose last template argument is `false` with the old kernel without that argument")
+    ap.add_argument("--ranges", action="store_true", help="print the index ranges of the differing opcodes of every DIFFERS row")
     args = ap.parse_args()
     both = args.files or ["decode_wave.hip", "encode_wave.hip"]
     old_files, new_files = args.old or both, args.new or both
@@ -81,7 +86,7 @@ def main():
     print("old: %s at %s; new: %s in the tree\n" % (" ".join(old_files), rev, " ".join(new_files)))
     print("| kernel | now in | instructions | %s | verdict |" % " | ".join(FIELDS))
     print("|---|---|---|---|---|---|---|")
-    same = 0
+    same, differing = 0, []
     for k in sorted(set(a) | set(b)):
         if k not in b:
             verdict = "ONLY AT THE REVISION"
@@ -89,11 +94,15 @@ def main():
             verdict = "ONLY IN THE TREE"
         elif a[k] != b[k]:
             verdict = "DIFFERS (%d instructions, %s at the revision)" % (len(a[k][0]), " / ".join(a[k][1]))
+            differing.append(k)
         else:
             verdict = "same"
             same += 1
         ops, res = b.get(k) or a[k]
         print("| `%s` | %s | %d | %s | %s |" % (k, where.get(k, "-"), len(ops), " | ".join(res), verdict))
+    for k in differing if args.ranges else []:
+        ops = difflib.SequenceMatcher(None, a[k][0], b[k][0], autojunk=False).get_opcodes()
+        print("\n`%s`: %s" % (k, ", ".join("%s [%d, %d) -> [%d, %d)" % op for op in ops if op[0] != "equal") or "the opcodes are equal"))
     print("\n%d kernels at the revision, %d in the tree, %d on both sides with the same opcode sequence, VGPR count, scratch "
           "size and static LDS size" % (len(a), len(b), same))
     sys.exit(0 if same == len(a) == len(b) else 1)
