@@ -130,6 +130,7 @@ struct rans_amd_ctx {
     bool dec_timed = false, enc_timed = false;
     uint32_t launch_seq = 0; // selects one of kWorkSlots chunk counters at d_words + 256
     uint32_t capture_seq = 0; // ... and one of the kCaptureSlots behind them for a launch that is being captured into a graph
+    uint32_t word64_seq = 0;  // k_decode_word64's own counters (take_word64_counters): its launches alone move that ring on
     uint32_t variant = 0;    // kVar* bits (rans_amd_ctx_set_option)
     bool unfused = false;    // RANS_AMD_OPT_FUSED_PLACEMENT = 0: k_encode + k_layout + k_compact
     bool scratch_ring = false; // RANS_AMD_OPT_ENC_SCRATCH_RING = 1
@@ -341,6 +342,24 @@ int take_counter_slot(rans_amd_ctx *ctx, const CaptureScope &capture, hipStream_
     return RANS_AMD_OK;
 }
 
+// k_decode_word64's uniform launches claim from kWord64Pools counters of their own: a ring of the shared one's shape behind it,
+// kWord64SlotWords per slot.  Only these launches use it and only they zero it (launch j slot j + 32), so a sequence number of
+// their own moves it on; a captured launch takes the slot beside its shared capture slot, zeroed by the same kind of node.
+int take_word64_counters(rans_amd_ctx *ctx, const CaptureScope &capture, hipStream_t s, DecParams &dp)
+{
+    unsigned int *ring = reinterpret_cast<unsigned int *>(ctx->d_words + 256) + (size_t)(kWorkSlots + kCaptureSlots) * kWorkSlotWords;
+    if (capture.active) { // (take_counter_slot has moved capture_seq on)
+        dp.word64_counters = ring + (size_t)(kWorkSlots + (ctx->capture_seq + kCaptureSlots - 1) % kCaptureSlots) * kWord64SlotWords;
+        ZeroList zero(s);
+        HIP_TRY(zero.add(dp.word64_counters, (uint64_t)kWord64SlotWords * 4));
+        HIP_TRY(zero.flush());
+    } else {
+        dp.word64_counters = ring + (size_t)(ctx->word64_seq % kWorkSlots) * kWord64SlotWords;
+        dp.word64_counters_reset = ring + (size_t)((ctx->word64_seq + kWorkSlots / 2) % kWorkSlots) * kWord64SlotWords;
+    }
+    return RANS_AMD_OK;
+}
+
 // launch_decode or launch_decode_batch (kernels.h)
 typedef hipError_t (*DecodeLauncher)(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **kernel_name);
 
@@ -355,6 +374,8 @@ int launch_decoder(rans_amd_ctx *ctx, const CaptureScope &capture, hipStream_t s
     // or a later launch would start from a counter nobody reset
     if (dp.work_counter && !capture.active)
         ctx->launch_seq++;
+    if (dp.word64_counters && !capture.active)
+        ctx->word64_seq++;
     if (ctx->timing && !t_capturing) {
         HIP_TRY(hipEventRecord(ctx->ev[1], s));
         ctx->dec_timed = true;
@@ -549,7 +570,7 @@ int rans_amd_ctx_create(int device, rans_amd_ctx **out_ctx)
         return fail(RANS_AMD_E_NOMEM, "ctx");
     ctx->device = device;
     ctx->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    const size_t words_bytes = 256 + (size_t)(kWorkSlots + kCaptureSlots) * kWorkSlotWords * 4;
+    const size_t words_bytes = 256 + (size_t)(kWorkSlots + kCaptureSlots) * (kWorkSlotWords + kWord64SlotWords) * 4;
     e = hipMalloc(reinterpret_cast<void **>(&ctx->d_words), words_bytes);
     if (e == hipSuccess)
         e = hipMemset(ctx->d_words, 0, words_bytes);
@@ -1308,6 +1329,10 @@ int rans_amd_decode(rans_amd_ctx *ctx, const rans_amd_model *model, const void *
         dp.variant = ctx->variant;
         if (nchunks < 0xffffffffull) // (32-bit counters; without one the kernels stride statically)
             RC_TRY(take_counter_slot(ctx, capture, s, dp));
+        // k_decode_word64 (the question launch_decode_wave asks) claims from counters of its own
+        if (dp.work_counter && decoder_kernel_format(model) == RANS_AMD_FMT_WORD &&
+            decode_shape(format, n_ways, dp.sym_bytes, decode_out_aligned(format, reinterpret_cast<uintptr_t>(d_out), chunk_syms), false).word64)
+            RC_TRY(take_word64_counters(ctx, capture, s, dp));
         // wave clocks (rans_amd_set_timing(ctx, 2)) and the debug timeline (RANS_AMD_TRACE=<file>): read_wave_trace
         static const char *trace_path = measure_knob("RANS_AMD_TRACE");
         const bool want_trace = (trace_path || ctx->wave_clocks_on) && !capture.active; // (read back after a sync)

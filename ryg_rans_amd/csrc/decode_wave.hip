@@ -541,11 +541,18 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64_t(const Dec
         p.work_counter_reset[threadIdx.x * kWorkPoolStride] = 0u;
     if (p.span_reset && blockIdx.x == 0 && threadIdx.x < 2)
         p.span_reset[threadIdx.x] = 0ull;
+    if constexpr (!RAGGED)
+        if (p.word64_counters_reset && blockIdx.x == 0 && threadIdx.x < kWord64Pools)
+            p.word64_counters_reset[threadIdx.x * kWorkPoolStride] = 0u;
 
     // ---- chunk hand-out (see k_decode): one counter per XCD, or static striding without counters
+    // (uniform calls: kWord64Pools counters of this launch's own, pool = blockIdx % 32 -- four per XCD; the ragged form keeps
+    //  the shared slot's eight)
+    constexpr uint32_t kPools = RAGGED ? kWorkPools : kWord64Pools;
+    unsigned int *const counters = RAGGED ? p.work_counter : p.word64_counters;
     const uint64_t total_waves = (uint64_t)gridDim.x * waves_per_block;
     uint64_t static_next = (uint64_t)blockIdx.x * waves_per_block + wave;
-    const uint32_t npools = gridDim.x < kWorkPools ? gridDim.x : kWorkPools;
+    const uint32_t npools = gridDim.x < kPools ? gridDim.x : kPools;
     const uint32_t pool = blockIdx.x % npools;
     uint32_t claimed_v = 0; // lane 0: what the atomic returned
 
@@ -561,8 +568,8 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64_t(const Dec
 
 #define RANS_STEP_CLAIM()                                                                   \
     do {                                                                                    \
-        if (p.work_counter && lane == 0)                                                    \
-            claimed_v = atomicAdd(p.work_counter + pool * kWorkPoolStride, 1u);             \
+        if (counters && lane == 0)                                                          \
+            claimed_v = atomicAdd(counters + pool * kWorkPoolStride, 1u);                   \
     } while (0)
     // The index entry comes through the scalar cache (s_load_dwordx2 / s_load_dword + wait, ~0.2 us on an L2
     // hit, once per chunk): it lands in SGPRs, no VGPR is tied up.  off and len come from the caller: compare
@@ -570,7 +577,7 @@ __global__ void __launch_bounds__(kWord64Threads, 8) k_decode_word64_t(const Dec
     // nor beyond the container's last granule.
 #define RANS_STEP_DATA()                                                                    \
     do {                                                                                    \
-        if (p.work_counter) {                                                               \
+        if (counters) {                                                                     \
             n_idx = (uint64_t)uniform(claimed_v) * npools + pool;                           \
         } else {                                                                            \
             n_idx = uniform64(static_next);                                                 \

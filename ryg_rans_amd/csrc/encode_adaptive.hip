@@ -14,7 +14,7 @@
 //                 from run to run, and about as large as the streams themselves (+ ~1.5 %).
 //                 (A bump pointer -- one atomic add per chunk on one word -- was the first version: a single word retires
 //                 ~88 atomics per microsecond and 65 536 chunks made that 0.75 ms of a 1.1 ms launch, whatever the occupancy:
-//                 profiles/r06_adaptive_encoder.md.)
+//                 profiles/r06_adaptive_encoder_variants.log.)
 //   4. records    the hand-written sub-steps' 16-byte records of the chunk's 256 symbols at LDS address 0 (reciprocals by
 //                 frequency from a 32 KiB table in global memory: no division on the device)
 //   5. code       the chunk a second time through (the second read is served by L2 / the memory-side cache), the same

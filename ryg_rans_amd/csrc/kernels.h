@@ -39,6 +39,11 @@ constexpr uint32_t kWorkSlots = 64;      // launches that may reuse the counter 
 constexpr uint32_t kCaptureSlots = 8;    // counter slots behind the ring for launches captured into a hipGraph (api.cpp)
 // one ring slot = kWorkPools counters (a 64-byte line each) + one line for the launch's wave span record
 constexpr uint32_t kWorkSlotWords = (kWorkPools + 1) * kWorkPoolStride;
+// k_decode_word64, uniform calls: kWord64Pools counters of the launch's own in a ring of the same shape behind the shared one
+// (DecParams::word64_counters).  Same-address atomics retire at ~88 per microsecond and counter; a 1 GiB launch makes 32 768
+// claims, twice that at 16 Ki-symbol chunks: 32 against 8 counters -3 % there (profiles/word64_pacing.md)
+constexpr uint32_t kWord64Pools = 32;
+constexpr uint32_t kWord64SlotWords = kWord64Pools * kWorkPoolStride;
 // Kernel-side format number of rans64 with a binary search over the cumulative frequencies instead of the cum2sym
 // table (scale_bits 1..6 and 17..31; kernel_formats.hpp FMT_R64S).  launch_decode / launch_encode take it in place
 // of RANS_AMD_FMT_R64; DecParams::table0 is then the cum table padded with ~0 to 2^log2nsyms words.
@@ -100,6 +105,10 @@ struct DecParams {
     const uint32_t *sym_counts;
     const uint32_t *order;            // or NULL: claim k takes stream k
     uint64_t out_syms;
+    // k_decode_word64, uniform calls (nobody else reads these): its kWord64Pools hand-out counters, a line each, zero at launch
+    // (NULL = static striding), and those of a LATER launch that this launch zeroes
+    unsigned int *word64_counters;
+    unsigned int *word64_counters_reset;
 };
 
 struct EncParams {

@@ -39,8 +39,8 @@ constexpr uint32_t kAdaptMaxScaleBits = 12;
 constexpr uint32_t kAdaptDecWaveLds = (1u << kAdaptMaxScaleBits) + 256u * 4u; // cum2sym + packed {freq | start << 16} records
 constexpr uint32_t kAdaptEncWaveLds = 256u * 16u;                             // EncRec per symbol
 // encode_adaptive.hip: six waves per SIMD (80 registers), 24 one-wave workgroups per CU (the LDS would allow 25): measured the
-// same from 20 to 25 per CU, and with 1, 4 or 8 count loads in flight (profiles/r06_adaptive_encoder.md: the launch is bound by
-// the LDS pipe -- one ds_add per symbol on top of the coder's record gather -- not by latency)
+// same from 20 to 25 per CU, and with 1, 4 or 8 count loads in flight (profiles/r06_adaptive_encoder_variants.log: the
+// launch is bound by the LDS pipe -- one ds_add per symbol on top of the coder's record gather -- not by latency)
 constexpr int kAdaptWavesPerSimd = 6, kAdaptPerCu = 24;
 constexpr uint32_t kAdaptRecBytes = 256u * 16u;                     // the records, at LDS address 0
 constexpr uint32_t kAdaptEncLds = kAdaptRecBytes + kEncStageBytes; // 6 KiB; the counters of step 1 lie over the records
@@ -106,7 +106,7 @@ constexpr WaveLaunch decode_launch(bool word64, bool adaptive, uint32_t table0_b
     // per-chunk models: every wave owns its tables (5 KiB) and window, nothing is shared -- workgroups of FOUR waves, five of
     // them per CU: 20 waves where one 16-wave workgroup held 16, and one wave per SIMD from every workgroup (one- and two-wave
     // workgroups spread unevenly over the CUs when the grid does not fill them: 0.84 / 0.80 ms against 0.73 for the word
-    // format, profiles/r06_adaptive_decoder.md)
+    // format, profiles/r06_adaptive_decoder_variants.log)
     constexpr uint32_t kAdaptDecThreads = 256;
     const uint32_t threads = adaptive ? kAdaptDecThreads : kDecBlockThreads;
     const uint32_t waves = threads / 64;
