@@ -326,7 +326,8 @@ int rans_amd_encode_slots_sized(rans_amd_ctx *ctx, const rans_amd_model *model, 
  * d_dst_offsets[c] = sum_{i<c} align16(d_lengths[i]), d_dst_offsets[n_chunks] = end of the last stream (n_chunks + 1
  * entries).  d_src (src_bytes long) and d_dst (dst_cap) must not overlap.  Asynchronous on `stream` unless h_total_bytes is
  * given (then: synchronises, stores d_dst_offsets[n_chunks], reports RANS_AMD_E_SPACE when dst_cap was too small --
- * nothing is copied in that case; rans_amd_encode_status reports the same later for an asynchronous call).  The source
+ * nothing is copied in that case; rans_amd_encode_status reports the same later for an asynchronous call).  d_dst_offsets
+ * is written in full even then, all n_chunks + 1 entries: that is how a caller learns the capacity it needs.  The source
  * index is data: an entry that does not lie inside [0, src_bytes) is neither read nor written and the call reports
  * RANS_AMD_E_CORRUPT (the other chunks are copied). */
 int rans_amd_container_compact(rans_amd_ctx *ctx, const void *d_src, uint64_t src_bytes, const uint64_t *d_src_offsets,

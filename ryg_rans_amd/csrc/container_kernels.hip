@@ -135,7 +135,9 @@ __global__ void __launch_bounds__(256) k_compact(const CompactParams p)
         gvec_cptr src = reinterpret_cast<gvec_cptr>(sa & ~uint64_t(15));
         u32x4 RANS_GLOBAL *dst = reinterpret_cast<u32x4 RANS_GLOBAL *>(reinterpret_cast<uint64_t>(p.out) + p.offsets[chunk]);
         const uint32_t dsh = uniform((uint32_t)(sa & 15u) >> 2), bsh = uniform((uint32_t)(sa & 3u));
-        const uint32_t n16 = (len + 15u) >> 4;
+        // (the sum in 64 bits: in 32 bits len + 15 wraps for the last 15 lengths below 2^32, and such a chunk would silently
+        //  not be copied.  The count is at most 2^28, so it and the trip index stay 32 bits wide: i + 64 cannot wrap)
+        const uint32_t n16 = (uint32_t)(((uint64_t)len + 15u) >> 4);
         for (uint32_t i = lane; i < n16; i += 64u) {
             const u32x4 a = __builtin_nontemporal_load(src + i); // (below src_limit: the chunk lies inside the source, checked above)
             u32x4 b = {0u, 0u, 0u, 0u}; // (the granule behind the source's last one is not there to be read)
@@ -210,7 +212,7 @@ __global__ void __launch_bounds__(256) k_compact_small(const CompactParams p)
                 sa[q] = reinterpret_cast<uint64_t>(p.scratch) + ((uint64_t)(uint32_t)__shfl((int)(uint32_t)from, src, 64) |
                                                                   ((uint64_t)(uint32_t)__shfl((int)(uint32_t)(from >> 32), src, 64) << 32));
                 da[q] = reinterpret_cast<uint64_t>(p.out) + o;
-                n16[q] = (l + 15u) >> 4; // (0 behind the last chunk)
+                n16[q] = (uint32_t)(((uint64_t)l + 15u) >> 4); // (0 behind the last chunk; 64-bit sum, at most 2^28 as in k_compact)
                 most = n16[q] > most ? n16[q] : most;
             }
 #pragma unroll

@@ -18,6 +18,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+from _around_coders import ref_order_keys
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
 
 WAVES_PER_BLOCK = 16
@@ -324,7 +325,7 @@ def test_batch_order(gpu, oracle, n_streams):
     d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
     order = ctx.batch_order(d_counts).cpu().numpy().view(np.uint32)
     assert np.array_equal(np.sort(order), np.arange(n_streams, dtype=np.uint32)), "not a permutation"
-    keys = np.floor(np.log2(counts[order].astype(np.float64) + 1.0)).astype(np.int64)
+    keys = ref_order_keys(counts[order])  # (in integers: no float log2 next to a power of two)
     assert np.all(np.diff(keys) <= 0), "bucket keys increase"
     if n_streams == 33:
         assert keys.tolist() == list(range(32, -1, -1))

@@ -15,6 +15,9 @@ equal.  Without --old / --new both sides take the files named (default: decode_w
 (a RAGGED form, say).  A kernel of the tree whose last template argument is `false` is then paired under the name it had
 without that argument; the instantiations with `true` stay what they are, kernels only the tree has.
 
+--kernels REGEX: compare the kernels whose names contain REGEX instead of the coders (k_compact, say, with
+container_kernels.hip).
+
 --ranges: behind the table, for every kernel whose opcode sequence DIFFERS, the index ranges of the opcodes that differ
 (old range -> new range, indices into the kernel's opcode list as counted in the `instructions` column)."""
 import argparse
@@ -32,9 +35,12 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-o
 FIELDS = ("next_free_vgpr", "private_segment_fixed_size", "group_segment_fixed_size")
 
 
+KERNELS = r"k_(?:de|en)code"  # --kernels: which kernels are compared, a regex that their names contain
+
+
 def kernels(asm):
     out = {}
-    for m in re.finditer(r"^(_Z\w*k_(?:de|en)code\w*):[^\n]*\n(.*?)\n\.Lfunc_end", asm, re.S | re.M):
+    for m in re.finditer(r"^(_Z\w*(?:%s)\w*):[^\n]*\n(.*?)\n\.Lfunc_end" % KERNELS, asm, re.S | re.M):
         ops = [ln.split()[0] for ln in m.group(2).split("\n")
                if ln.strip() and not ln.strip().startswith((";", ".")) and not ln.strip().endswith(":")]
         meta = re.search(r"\.amdhsa_kernel " + re.escape(m.group(1)) + r"\n(.*?)\.end_amdhsa_kernel", asm, re.S).group(1)
@@ -50,6 +56,7 @@ def compile_asm(job):
 
 
 def main():
+    global KERNELS
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("rev", help="git revision of the old side")
     ap.add_argument("files", nargs="*", help="files of both sides (in %s)" % CSRC)
@@ -58,7 +65,9 @@ def main():
     ap.add_argument("--new-default-false", action="store_true",
                     help="pair a kernel of the tree whose last template argument is `false` with the old kernel without that argument")
     ap.add_argument("--ranges", action="store_true", help="print the index ranges of the differing opcodes of every DIFFERS row")
+    ap.add_argument("--kernels", default=KERNELS, help="regex the compared kernels' names contain (default: %(default)s)")
     args = ap.parse_args()
+    KERNELS = args.kernels
     both = args.files or ["decode_wave.hip", "encode_wave.hip"]
     old_files, new_files = args.old or both, args.new or both
     with tempfile.TemporaryDirectory() as tmp:
