@@ -260,7 +260,13 @@ uint64_t rans_amd_encode_workspace_bytes(int format, uint64_t n, uint32_t n_ways
  * is the container size.  If h_total_bytes != NULL the call synchronises
  * `stream` and stores the container size; it then also reports
  * RANS_AMD_E_SPACE if out_cap was too small and RANS_AMD_E_MODEL if a symbol
- * with frequency 0 was met. */
+ * with frequency 0 was met.
+ * Capacity: the call succeeds iff out_cap >= d_offsets[n_chunks - 1] + align16(d_lengths[n_chunks - 1]), that is
+ * d_offsets[n_chunks] rounded up to 16 -- streams are stored in whole 16-byte granules, whichever kernels place them
+ * (the context options change none of this).  rans_amd_encode_bound() is a multiple of 16 and always enough.  Whatever
+ * the status, no byte outside [d_out, d_out + out_cap) is written, and d_offsets[n_chunks] holds the container size:
+ * that is how a caller whose buffer was too small (RANS_AMD_E_SPACE) learns what to allocate.  Which of the chunks
+ * that fit a failed call has written is unspecified. */
 int rans_amd_encode(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_syms, uint64_t n,
                     uint32_t n_ways, uint32_t chunk_syms, void *d_out, uint64_t out_cap,
                     uint64_t *d_offsets, uint32_t *d_lengths, uint64_t *h_total_bytes, void *stream);
@@ -486,7 +492,9 @@ int rans_amd_decode_errors(rans_amd_ctx *ctx, uint64_t *h_bad_chunks, void *stre
  * rans_amd_chunk_freqs_bytes) travels with the container: rans_amd_encode_adaptive fills it, rans_amd_decode_adaptive
  * reads it (a chunk whose frequencies do not sum to 1 << scale_bits is counted as corrupt, never decoded). */
 uint64_t rans_amd_chunk_freqs_bytes(uint64_t n, uint32_t chunk_syms);
-/* Histograms on the GPU, normalize_freqs on the host (synchronises `stream`), encode + layout + compaction on the GPU. */
+/* Histograms on the GPU, normalize_freqs on the host (synchronises `stream`), encode + layout + compaction on the GPU.
+ * out_cap: the capacity rule of rans_amd_encode (d_offsets[n_chunks] rounded up to 16 must fit; nothing is written outside
+ * [d_out, d_out + out_cap); d_offsets[n_chunks] is stored even when the call ends in RANS_AMD_E_SPACE). */
 int rans_amd_encode_adaptive(rans_amd_ctx *ctx, const void *d_syms, uint64_t n, uint32_t n_ways, uint32_t chunk_syms,
                              uint32_t scale_bits, void *d_out, uint64_t out_cap, uint64_t *d_offsets,
                              uint32_t *d_lengths, uint16_t *d_chunk_freqs, uint64_t *h_total_bytes, void *stream);

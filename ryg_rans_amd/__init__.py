@@ -588,17 +588,22 @@ class Context:
         return bi.value, bj.value, [[ms[i * k + j] for j in range(k)] for i in range(len(d_containers))]
 
     # -- one model per chunk (byte format, 256 symbols, scale_bits 8..12)
-    def encode_adaptive(self, d_syms, n_ways, chunk_syms, scale_bits, sync=True, fmt=FMT_BYTE):
-        """Returns (d_container, d_offsets, d_lengths, d_chunk_freqs, total_bytes).  fmt: FMT_BYTE or FMT_WORD (scale_bits 12)."""
+    def encode_adaptive(self, d_syms, n_ways, chunk_syms, scale_bits, sync=True, fmt=FMT_BYTE, d_out=None, d_offsets=None,
+                        d_lengths=None, d_freqs=None):
+        """Returns (d_container, d_offsets, d_lengths, d_chunk_freqs, total_bytes).  fmt: FMT_BYTE or FMT_WORD (scale_bits 12).
+        d_out / d_offsets / d_lengths / d_freqs may be passed in (d_out.numel() is the call's out_cap)."""
         import torch
         n = d_syms.numel()
         nchunks = num_chunks(n, chunk_syms)
-        cap = encode_bound(fmt, n, n_ways, chunk_syms) + 16
         dev = d_syms.device
-        d_out = torch.empty(cap, dtype=torch.uint8, device=dev)
-        d_offsets = torch.zeros(nchunks + 1, dtype=torch.int64, device=dev)
-        d_lengths = torch.zeros(max(nchunks, 1), dtype=torch.int32, device=dev)
-        d_freqs = torch.zeros(max(nchunks, 1) * 256, dtype=torch.int16, device=dev)
+        if d_out is None:
+            d_out = torch.empty(encode_bound(fmt, n, n_ways, chunk_syms) + 16, dtype=torch.uint8, device=dev)
+        if d_offsets is None:
+            d_offsets = torch.zeros(nchunks + 1, dtype=torch.int64, device=dev)
+        if d_lengths is None:
+            d_lengths = torch.zeros(max(nchunks, 1), dtype=torch.int32, device=dev)
+        if d_freqs is None:
+            d_freqs = torch.zeros(max(nchunks, 1) * 256, dtype=torch.int16, device=dev)
         assert int(_lib.rans_amd_chunk_freqs_bytes(n, chunk_syms)) == nchunks * 512
         total = C.c_uint64(0)
         if fmt == FMT_BYTE:  # (the entry point older callers bind)

@@ -248,7 +248,7 @@ __device__ __forceinline__ void lanes_copy_batch(const EncParams &p, uint64_t ba
         if (chunk + 1 == p.nchunks)
             p.offsets[p.nchunks] = off + len;
     }
-    if (__builtin_amdgcn_ballot_w64(valid && off + len > p.out_cap) != 0) { // (wave-uniform)
+    if (__builtin_amdgcn_ballot_w64(valid && off + alen > p.out_cap) != 0) { // (wave-uniform; alen: whole granules are stored below)
         atomicOr(p.flags, lane == 0 ? 2u : 0u);
         return;
     }

@@ -48,15 +48,22 @@ __device__ __forceinline__ void place_and_copy(const EncParams &p, uint64_t chun
     const unsigned long long alen = (len + 15u) & ~15u;
     unsigned long long base = 0;
     status_lookback(p.status, chunk, lane, p.flags, p.wait_ticks, 32u, base); // (a wait that gave up: bit 5, the launch has failed)
+    // The chunk fits when its whole 16-byte granules do: the copy below stores alen bytes, and k_layout asks the same of the
+    // three-kernel path.  The verdict is held in a scalar and reported by EVERY lane (lane 0 with the bit, the others with
+    // 0).  With `if (lane == 0) atomicOr(..); return;` here the compiler sent only lane 0 out of the copier's loop to do
+    // the atomic and let lanes 1..63 run straight on into the next mailbox_pop -- whose readfirstlane then read a lane that
+    // had claimed nothing, entry 0 again -- with lane 0's atomicOr parked behind that wait: every call that ended in
+    // RANS_AMD_E_SPACE sat through the watchdog's half minute first (encode_lanes.hip, lanes_scan_batch, tells of the
+    // same trap).  No test ran a fused launch that does not fit before tests/test_gpu_capacity.py.
+    const bool fits = uniform64(base + alen) <= p.out_cap;
     if (lane == 0) {
         __hip_atomic_store(p.status + chunk, kStPrefix | (base + alen), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         p.offsets[chunk] = base;
         if (chunk + 1 == p.nchunks)
             p.offsets[p.nchunks] = base + len;
     }
-    if (base + len > p.out_cap) { // wave-uniform
-        if (lane == 0)
-            atomicOr(p.flags, 2u);
+    if (!fits) { // wave-uniform
+        atomicOr(p.flags, lane == 0 ? 2u : 0u);
         return;
     }
     u32x4 RANS_GLOBAL *dst = reinterpret_cast<u32x4 RANS_GLOBAL *>(reinterpret_cast<uint64_t>(p.out) + base);
