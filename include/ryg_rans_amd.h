@@ -61,7 +61,8 @@ extern "C" {
  * rans_amd_encode_adaptive_fmt / rans_amd_decode_adaptive_fmt (0.5.0); rans_amd_encode_adaptive_sized,
  * rans_amd_container_pack_indexed[_adaptive] (0.6.0); ragged batches -- rans_amd_batch_layout, rans_amd_encode_batch,
  * rans_amd_decode_batch, rans_amd_batch_order, rans_amd_batch_slice, rans_amd_encode_batch_adaptive[_bound],
- * rans_amd_decode_batch_adaptive, rans_amd_encode_batch_ordered (still 0.6.0: additions only).  A caller built
+ * rans_amd_decode_batch_adaptive, rans_amd_encode_batch_ordered, RANS_AMD_OPT_BATCH_ENCODE_PAIRS (still 0.6.0: additions
+ * only).  A caller built
  * against an older header keeps working, with two behaviour changes it can observe: since 0.4.0
  * rans_amd_container_parse[_adaptive] want a 4-byte aligned `src` (RANS_AMD_E_ARG otherwise; an mmap at an odd offset must
  * be copied first), and since 0.5.0 rans_amd_container_compact checks its SOURCE index against src_bytes
@@ -172,7 +173,7 @@ enum rans_amd_option {
                                               other shape takes the wave-per-stream kernels as before.  Default 0: one
                                               stream per wavefront (RANS_AMD_OPT_BATCH_GROUPS is the decoder's alone).
                                               Any other value is RANS_AMD_E_ARG. */
-    RANS_AMD_OPT_BATCH_PAIRS = 7           /* 1 = rans_amd_decode_batch decodes THIRTY-TWO streams per wavefront where the
+    RANS_AMD_OPT_BATCH_PAIRS = 7,          /* 1 = rans_amd_decode_batch decodes THIRTY-TWO streams per wavefront where the
                                               batch is the reference's 2-way byte layout (byte format, u8 symbols, n_ways 2,
                                               scale_bits 8..16, at least 32 streams, tables + wave rings within the CU's
                                               160 KiB of LDS): k_decode_batch_byte_pairs; every other shape takes the
@@ -181,6 +182,13 @@ enum rans_amd_option {
                                               181 992 streams of up to 64 Ki symbols: 4.85 ms against 38.52 ms on
                                               k_decode_batch<byte> with the same d_order (7.94 x).
                                               Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
+    RANS_AMD_OPT_BATCH_ENCODE_PAIRS = 8    /* 1 = rans_amd_encode_batch[_ordered] codes THIRTY-TWO streams per wavefront where
+                                              the batch is that same shape (byte format, u8 symbols, n_ways 2, scale_bits
+                                              8..16, at least 32 streams): k_encode_batch_byte_pairs, the same bytes; every
+                                              other shape takes the wave-per-stream kernels as before.  Independent of
+                                              options 5, 6 and 7 (RANS_AMD_OPT_BATCH_PAIRS is the decoder's alone);
+                                              rans_amd_encode_batch_adaptive is not affected.  Default 0: one stream per
+                                              wavefront.  Any other value is RANS_AMD_E_ARG. */
 };
 int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value);
 
@@ -395,12 +403,13 @@ int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, u
  * RANS_AMD_OPT_BATCH_ENCODE_GROUPS = 1; the two options are independent, and the bytes are the same with and without them.
  * A wavefront then lasts as long as the longest of its eight streams: pass the d_order of rans_amd_batch_order, which puts
  * streams of one length bucket next to each other, and lay the symbols out with sym_align = 4 (a stream whose symbols are
- * not 4-byte aligned is decoded, and coded, a round at a time).  A second shape packs THIRTY-TWO streams into a wavefront,
- * in the decoder: the 2-way byte layout main.cpp writes (byte format, u8 symbols, n_ways 2, scale_bits 8..16) in a batch of
- * at least 32 streams, decoded by rans_amd_decode_batch on a context with RANS_AMD_OPT_BATCH_PAIRS = 1 -- the same rules: the
- * wavefront lasts as long as the longest of its 32 streams (pass d_order), and sym_align = 4 is the fast layout.  Every
- * other interleave stays one stream per wavefront in both directions, the 2-way byte layout in the encoder as well; ragged
- * forms of the lane kernels are later work.  A stream of 0 symbols is the n_ways flushed initial states.
+ * not 4-byte aligned is decoded, and coded, a round at a time).  A second shape packs THIRTY-TWO streams into a wavefront:
+ * the 2-way byte layout main.cpp writes (byte format, u8 symbols, n_ways 2, scale_bits 8..16) in a batch of at least 32
+ * streams, decoded by rans_amd_decode_batch on a context with RANS_AMD_OPT_BATCH_PAIRS = 1 and coded by
+ * rans_amd_encode_batch[_ordered] on a context with RANS_AMD_OPT_BATCH_ENCODE_PAIRS = 1 (independent again, the same bytes) --
+ * the same rules: the wavefront lasts as long as the longest of its 32 streams (pass d_order), and sym_align = 4 is the fast
+ * layout.  Every other interleave stays one stream per wavefront in both directions; ragged forms of the lane kernels are
+ * later work.  A stream of 0 symbols is the n_ways flushed initial states.
  * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
  * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).
  *

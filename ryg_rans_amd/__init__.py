@@ -24,6 +24,7 @@ FORMAT_NAMES = {FMT_BYTE: "byte", FMT_WORD: "word", FMT_R64: "r64", FMT_ALIAS: "
 OPT_LANE_KERNELS, OPT_LANE_FUSED_PLACEMENT, OPT_FUSED_PLACEMENT, OPT_DUAL_DECODE, OPT_ENC_SCRATCH_RING, OPT_BATCH_GROUPS = range(6)
 OPT_BATCH_ENCODE_GROUPS = 6
 OPT_BATCH_PAIRS = 7
+OPT_BATCH_ENCODE_PAIRS = 8
 
 OK, E_ARG, E_MODEL, E_SPACE, E_CORRUPT, E_UNSUPPORTED, E_HIP, E_NOMEM = range(8)
 

@@ -673,6 +673,11 @@ int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value)
             return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_PAIRS takes 0 (one stream per wave) or 1 (thirty-two 2-way byte streams per wave)");
         ctx->variant = value ? (ctx->variant | kVarBatchPairs) : (ctx->variant & ~kVarBatchPairs);
         return RANS_AMD_OK;
+    case RANS_AMD_OPT_BATCH_ENCODE_PAIRS:
+        if (value != 0 && value != 1)
+            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_ENCODE_PAIRS takes 0 (one stream per wave) or 1 (thirty-two 2-way byte streams per wave)");
+        ctx->variant = value ? (ctx->variant | kVarBatchEncPairs) : (ctx->variant & ~kVarBatchEncPairs);
+        return RANS_AMD_OK;
     default:
         return fail(RANS_AMD_E_ARG, "set_option: unknown option");
     }

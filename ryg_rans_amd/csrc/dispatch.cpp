@@ -33,9 +33,10 @@ hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_
 // ragged batches: the wave-per-stream kernels, whatever the interleave -- unless the context asked for eight streams per wave
 // (RANS_AMD_OPT_BATCH_GROUPS for the decoder, RANS_AMD_OPT_BATCH_ENCODE_GROUPS for the encoder) and the batch is the
 // reference's 8-way word layout over u8 symbols, from eight streams on, or for thirty-two streams per wave
-// (RANS_AMD_OPT_BATCH_PAIRS, the decoder's alone) and the batch is the reference's 2-way byte layout over u8 symbols, from
-// 32 streams on: the ragged kernels of decode_groups.hip and encode_groups.hip.  Every other shape takes the wave kernels
-// under those options as well (the ragged forms of the lane kernels and of the 2-way byte ENCODER are later work).
+// (RANS_AMD_OPT_BATCH_PAIRS for the decoder, RANS_AMD_OPT_BATCH_ENCODE_PAIRS for the encoder) and the batch is the reference's
+// 2-way byte layout over u8 symbols at scale_bits 8..16, from 32 streams on: the ragged kernels of decode_groups.hip and
+// encode_groups.hip.  Every other shape takes the wave kernels under those options as well (the ragged forms of the lane
+// kernels are later work).
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
 {
     if ((p.variant & kVarBatchGroups) && format == (int)RANS_AMD_FMT_WORD && decode_batch_word_groups_applicable(p))
@@ -54,6 +55,8 @@ hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipS
 {
     if ((p.variant & kVarBatchEncGroups) && format == (int)RANS_AMD_FMT_WORD && encode_batch_word_groups_applicable(p))
         return launch_encode_batch_word_groups(p, num_cus, stream, batch_kernel);
+    if ((p.variant & kVarBatchEncPairs) && format == (int)RANS_AMD_FMT_BYTE && encode_batch_byte_pairs_applicable(p))
+        return launch_encode_batch_byte_pairs(p, num_cus, stream, batch_kernel);
     return launch_encode_batch_wave(format == kKernelFormatWord16 ? (int)RANS_AMD_FMT_WORD : format, p, num_cus, stream, batch_kernel);
 }
 

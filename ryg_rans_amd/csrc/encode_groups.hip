@@ -23,7 +23,8 @@
 // Chunks of a multiple of 4 symbols (launcher: the symbol loads are dword-aligned); what a chunk size off 128 leaves, and the
 // input's last octet when its last chunk is a ragged one, go round by round.  The ragged form for rans_amd_encode_batch --
 // eight STREAMS per wave, each with its own symbol count, symbol address and slot -- is k_encode_batch_word_groups, behind the
-// uniform kernel.
+// uniform kernel.  Behind that one: k_encode_batch_byte_pairs, the ragged encoder of the byte format's 2-way layout
+// (main.cpp:226-246), thirty-two STREAMS per wave; it has no uniform form here (the uniform byte 2-way encoder is the lane kernel).
 //
 // No MFMA: integer, table-driven, serial per state.
 
@@ -434,6 +435,322 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_word_groups(con
         atomicOr(p.flags, 1u);
 }
 
+// ---------------------------------------------------------------------------
+// k_encode_batch_byte_pairs -- the byte format's 2-way layout (rans_byte.h:62-90, main.cpp:226-246: two states, one pointer
+// that moves DOWN) for rans_amd_encode_batch[_ordered] under RANS_AMD_OPT_BATCH_ENCODE_PAIRS: THIRTY-TWO streams per wave,
+// the mirror image of decode_groups.hip's k_decode_batch_byte_pairs.  The unit of work is one wave-load of the hand-out
+// order: lane 2 g + i holds state i of the stream at position 32 w + g -- stream order[32 w + g], or 32 w + g without an
+// order; a position at or past nchunks has no stream.
+//   * the coder runs from a stream's last symbol to its first; round r holds symbols 2 r (state 0) and 2 r + 1 (state 1), an
+//     odd count's last symbol is state 0's alone and is coded first (main.cpp:232-236);
+//   * a state emits 0, 1 or 2 bytes (`while x >= x_max`, scale_bits <= 16), its low byte first -- highest.  Inside a round
+//     state 1 puts first: the odd lane writes from the pair's cursor c (bytes emitted so far), the even lane from c + the odd
+//     lane's count, which comes through one DPP swap of the pair (the decoder's sequence with odd and even exchanged); a lane's
+//     count is its own two compares, there is no ballot;
+//   * stream byte k (0 = the first emitted) lives at offset 63 - (k & 63) of the pair's 64-byte ring in LDS, two 32-byte
+//     blocks; rows kPairRow = 68 bytes apart, so that equal positions of the 32 pairs fall on 32 banks.  Eight rounds emit at
+//     most 8 x 2 x 2 = 32 bytes per pair: one compare per lane every eight rounds decides whether a finished block leaves,
+//     16 bytes per lane, to its place below the end of the stream's slot (slot_end is a multiple of 16, blocks are counted
+//     down from it: k_encode_batch_word_groups' flush_block with its two guards);
+//   * records {rcp, cmpl | rshift << 24, bias, x_max} (encode_common.hpp enc_byte_full's), 256 of them at LDS address 0, built
+//     in the prologue from EncParams::enc_recs; a byte value without a record never emits, leaves x alone and carries bit 31
+//     in its second word: TRACK (models that have such values) ORs those words together, bit 0 of the flags at the end;
+//   * symbols: whole 32-byte pieces of a stream whose first symbol is 4-byte aligned -- sixteen rounds, 16 bytes per lane, the
+//     next piece in flight while this one is coded -- are taken apart into per-state dwords by the inverse of the decoder's
+//     pair_lines and coded by a hand-scheduled eight-round sequence under FULL exec (it sets exec = -1 itself, and its DPP
+//     moves read the pair's other lane).  The count_g - 32 pieces_g symbols behind the last whole piece (all of them where
+//     the first symbol is not 4-byte aligned) go one compiler-scheduled round at a time, a byte load per lane, lanes without
+//     a symbol sitting out -- FIRST, because they are the end of the stream.
+// The 32 pairs START together and finish at different times.  A pair is FINALISED -- its last block check, the two flushed
+// states (RansEncFlush(rans1), then rans0: state 0's dword lowest), the last one or two blocks, lengths[s] and offsets[s]
+// -- at the top of the iteration q == pieces_g: right behind its last round, before the wave runs another one.  From then
+// on it is DEAD, and so is, from the start, a pair without a stream or with a rejected one.  A dead pair rides along under
+// full exec and, unlike a dead group of the word encoder, its cursor DOES move (its count is its own compares).  It is left
+// to run free -- it is never resumed, so there is nothing to put back -- and that is safe:
+//   * nothing of it ever leaves: flush_block and the index stores test `live`, which is cleared for good;
+//   * its ring writes go to top - (position & 63), inside its own row whatever its cursor is, and everything of its
+//     stream had left the ring when it was finalised;
+//   * it loads no symbol (load_piece fetches under q + 1 < pieces_g) and codes zeros: it reads only the record of byte value 0;
+//   * it cannot raise the model flag, even when byte value 0 has no record: `worst` is put back from a copy behind every
+//     piece for the pairs that did not run it (the rounds of the tail track under `active` only);
+//   * it cannot raise any other flag: bits 1 and 11 are set in the claim's set-up alone.
+// Index entries are the caller's data and checked exactly as k_encode_batch_word_groups checks them, with need = align16(2 *
+// count + 2 * 4) = rans_amd_chunk_bound(): a slot that fails is not written, lengths[s] = 0, offsets[s] = the slot's end, bit
+// 1 of the flags; an order entry that names no stream codes nothing, writes no index entry and sets bit 11.  Every lane
+// addresses symbols and slots in 64 bits.  A stream of 0 symbols is the two flushed initial states.
+// What follows from the lane number is worked out per claim (lane_number_now) and the claim compare is scalar, as in the pair
+// decoder: nothing of it stays in registers across the piece loop.  No MFMA: integer, table-driven, serial per state.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kEncPairTable = 256 * 16; // the records, at LDS address 0
+
+// One round of the eight, 21 VALU (+ 1 with TRACK) + 3 LDS; vcc = the odd lanes for the whole sequence, v56..v59 the record:
+//   v_lshlrev (SDWA byte J)     LDS address of the symbol's record
+//   ds_read_b128, v_lshrrev     {rcp, cmpl | rshift << 24, bias, x_max}; t1 = x >> 8
+//   v_cmp x2                    n1 = x >= x_max (at least one byte leaves), n2 = x >> 8 >= x_max (two)
+//   v_addc x2                   t2 = c + n1 + n2: where this lane's bytes END if it is the pair's first
+//   v_cndmask_dpp               my position = odd lane: the cursor; even lane: the odd lane's t2
+//   v_add_dpp, v_sub            the pair's next cursor = t2 + the other lane's t2 - c
+//   v_and, v_sub / v_add, v_and, v_sub   position, position + 1 -> LDS addresses in the pair's ring (downwards from `top`)
+//   ds_write_b8 x2, v_mov, v_lshrrev     under exec = n1 / n2: the low byte leaves, then the next one
+//   v_mul_hi .. v_add           x = x + bias + (x / freq) * cmpl (enc_byte_full's tail)
+#define RANS_PE_ROUND(ACC, SEL, TRACKSTR)                                                                              \
+    "v_lshlrev_b32_sdwa %[t0], %[k4], " ACC " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" SEL "\n\t"   \
+    "ds_read_b128 v[56:59], %[t0]\n\t"                                                                                 \
+    "v_lshrrev_b32_e32 %[t1], 8, %[x]\n\t"                                                                             \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                         \
+    "v_cmp_ge_u32_e64 %[n1], %[x], v59\n\t"                                                                            \
+    "v_cmp_ge_u32_e64 %[n2], %[t1], v59\n\t"                                                                           \
+    TRACKSTR                                                                                                           \
+    "v_addc_co_u32_e64 %[t2], %[dm], %[c], 0, %[n1]\n\t"                                                               \
+    "v_addc_co_u32_e64 %[t2], %[dm], %[t2], 0, %[n2]\n\t"                                                              \
+    "s_nop 1\n\t"                                                                                                      \
+    "v_cndmask_b32_dpp %[t3], %[t2], %[c], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"                      \
+    "v_add_u32_dpp %[t0], %[t2], %[t2] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"                              \
+    "v_sub_u32_e32 %[c], %[t0], %[c]\n\t"                                                                              \
+    "v_and_b32_e32 %[t0], 63, %[t3]\n\t"                                                                               \
+    "v_sub_u32_e32 %[t0], %[top], %[t0]\n\t"                                                                           \
+    "v_add_u32_e32 %[t3], 1, %[t3]\n\t"                                                                                \
+    "v_and_b32_e32 %[t3], 63, %[t3]\n\t"                                                                               \
+    "v_sub_u32_e32 %[t3], %[top], %[t3]\n\t"                                                                           \
+    "s_mov_b64 exec, %[n1]\n\t"                                                                                        \
+    "ds_write_b8 %[t0], %[x]\n\t"                                                                                      \
+    "v_mov_b32_e32 %[x], %[t1]\n\t"                                                                                    \
+    "s_mov_b64 exec, %[n2]\n\t"                                                                                        \
+    "ds_write_b8 %[t3], %[t1]\n\t"                                                                                     \
+    "v_lshrrev_b32_e32 %[x], 8, %[x]\n\t"                                                                              \
+    "s_mov_b64 exec, -1\n\t"                                                                                           \
+    "v_mul_hi_u32 %[t0], %[x], v56\n\t"                                                                                \
+    "v_lshrrev_b32_sdwa %[t0], v57, %[t0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD\n\t"        \
+    "v_mad_u32_u24 %[t0], %[t0], v57, %[x]\n\t"                                                                        \
+    "v_add_u32_e32 %[x], %[t0], v58\n\t"
+#define RANS_PE_FOUR(ACC, TRACKSTR)                                                                                    \
+    RANS_PE_ROUND(ACC, "BYTE_3", TRACKSTR) RANS_PE_ROUND(ACC, "BYTE_2", TRACKSTR) RANS_PE_ROUND(ACC, "BYTE_1", TRACKSTR) \
+    RANS_PE_ROUND(ACC, "BYTE_0", TRACKSTR)
+#define RANS_PE_EIGHT(TRACKSTR)                                                                                        \
+    asm volatile("s_mov_b64 vcc, %[odds]\n\t" RANS_PE_FOUR("%[hi]", TRACKSTR) RANS_PE_FOUR("%[lo]", TRACKSTR)            \
+                 : [x] "+v"(x), [c] "+v"(c), [worst] "+v"(worst), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), \
+                   [n1] "=&s"(n1), [n2] "=&s"(n2), [dm] "=&s"(dm)                                                       \
+                 : [hi] "v"(hi), [lo] "v"(lo), [k4] "v"(k4), [top] "v"(top), [odds] "s"(0xaaaaaaaaaaaaaaaaull)         \
+                 : "vcc", "memory", "v56", "v57", "v58", "v59")
+// eight rounds of a pair, the last first: bytes 3 .. 0 of `hi` (four rounds of this lane's state), then of `lo`
+template <bool TRACK>
+__device__ __forceinline__ void encode_pairs_8rounds(uint32_t &x, uint32_t &c, uint32_t &worst, uint32_t hi, uint32_t lo, uint32_t k4, uint32_t top)
+{
+    uint32_t t0, t1, t2, t3;
+    uint64_t n1, n2, dm;
+    if constexpr (TRACK)
+        RANS_PE_EIGHT("v_or_b32_e32 %[worst], %[worst], v57\n\t");
+    else
+        RANS_PE_EIGHT("s_nop 0\n\t");
+}
+#undef RANS_PE_EIGHT
+#undef RANS_PE_FOUR
+#undef RANS_PE_ROUND
+
+// The inverse of decode_groups.hip's pair_lines: 32 bytes of a pair's stream of symbols, bytes [0, 16) in the even lane and
+// [16, 32) in the odd one, -> d0..d3, the four dwords of this lane's state (byte J of d_m: round 4 m + J of the piece's
+// sixteen).  The lanes first swap dwords so that the even lane holds dwords 0, 2, 4, 6 of the piece and the odd lane 1, 3, 5,
+// 7; then every lane picks its state's bytes out of its own dword and the other lane's (sel: v_perm(theirs, mine)).
+__device__ __forceinline__ void piece_to_states(const u32x4 &v, uint32_t &d0, uint32_t &d1, uint32_t &d2, uint32_t &d3, uint32_t sel)
+{
+    uint32_t e0, e1, e2, e3;
+    asm volatile("s_nop 1\n\t"
+                 "s_mov_b64 vcc, %[evens]\n\t"
+                 "v_cndmask_b32_dpp %[e0], %[vy], %[vx], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t" // even ? mine : the even lane's y
+                 "v_cndmask_b32_dpp %[e1], %[vw], %[vz], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_mov_b64 vcc, %[odds]\n\t"
+                 "v_cndmask_b32_dpp %[e2], %[vx], %[vy], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t" // odd ? mine : the odd lane's x
+                 "v_cndmask_b32_dpp %[e3], %[vz], %[vw], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "s_nop 1\n\t"
+                 "v_mov_b32_dpp %[d0], %[e0] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_mov_b32_dpp %[d1], %[e1] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_mov_b32_dpp %[d2], %[e2] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_mov_b32_dpp %[d3], %[e3] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+                 "v_perm_b32 %[d0], %[d0], %[e0], %[sel]\n\t" // even: [mine.0, mine.2, theirs.0, theirs.2]; odd: [theirs.1, theirs.3, mine.1, mine.3]
+                 "v_perm_b32 %[d1], %[d1], %[e1], %[sel]\n\t"
+                 "v_perm_b32 %[d2], %[d2], %[e2], %[sel]\n\t"
+                 "v_perm_b32 %[d3], %[d3], %[e3], %[sel]"
+                 : [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [e0] "=&v"(e0), [e1] "=&v"(e1), [e2] "=&v"(e2),
+                   [e3] "=&v"(e3)
+                 : [vx] "v"(v.x), [vy] "v"(v.y), [vz] "v"(v.z), [vw] "v"(v.w), [sel] "v"(sel), [evens] "s"(0x5555555555555555ull),
+                   [odds] "s"(0xaaaaaaaaaaaaaaaaull)
+                 : "vcc");
+}
+
+// The sixteen rounds of a piece that piece_to_states has taken apart, last round first.  flush(have_bytes) is the kernel's
+// flush_block: the block that the eight rounds before may have finished leaves in front of the next eight.  (A dead pair's
+// check may be true -- its cursor moves -- and its flush_block then only counts the block.)
+template <bool TRACK, class FLUSH>
+__device__ __forceinline__ void encode_piece(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t &x, uint32_t &c, uint32_t &worst,
+                                             const uint32_t &fb, uint32_t k4, uint32_t top, FLUSH &&flush)
+{
+    if (c >= kPairBlock * (fb + 1u))
+        flush(c);
+    encode_pairs_8rounds<TRACK>(x, c, worst, d3, d2, k4, top); // rounds 15 .. 8
+    if (c >= kPairBlock * (fb + 1u))
+        flush(c);
+    encode_pairs_8rounds<TRACK>(x, c, worst, d1, d0, k4, top); // rounds 7 .. 0
+}
+
+template <bool TRACK>
+__global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_byte_pairs(const EncParams p)
+{
+    using Tr = FmtTraits<FMT_BYTE>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    {   // EncRec {freq | rshift << 24, bias, rcp, -} -> the sequence's records (k_encode<byte>'s prologue), 256 of them
+        const uint4 *g0 = reinterpret_cast<const uint4 *>(p.enc_recs);
+        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
+        for (uint32_t k = threadIdx.x; k < 256u; k += blockDim.x) {
+            const uint4 r = k < p.nsyms ? g0[k] : uint4{0u, 0u, 0u, 0u};
+            const uint32_t freq = r.x & 0xffffffu;
+            l0[k] = freq ? uint4{r.z, (((1u << p.scale_bits) - freq) & 0xffffffu) | (r.x & 0xff000000u), r.y, freq << (31u - p.scale_bits)}
+                         : uint4{0u, 0xffffffffu, 0u, 0xffffffffu}; // no frequency: nothing leaves, x stays, bit 31 for TRACK
+        }
+    }
+    __syncthreads();
+    if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never code on a wrong assumption
+        if (threadIdx.x == 0)
+            atomicOr(p.flags, 4u);
+        return;
+    }
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    uint32_t ring = kEncPairTable + wave * kPairWaveLds + (lane >> 1) * kPairRow; // raw LDS byte address of the pair's ring
+    uint32_t ring_i = ring + 16u * (lane & 1u);                                   // where this lane's 16 bytes of a block lie
+    uint32_t top = ring + (kPairRing - 1u), k4 = 4u;
+    uint32_t sel = (lane & 1u) ? 0x03010705u : 0x06040200u;
+    pin_vgpr(ring);
+    pin_vgpr(ring_i);
+    pin_vgpr(top);
+    pin_vgpr(k4);
+    pin_vgpr(sel);
+    const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 31u) >> 5); // wave-loads, one per claim (the last one may hold fewer than 32
+                                                                         // streams); stream indices are 32-bit
+
+    uint32_t worst = 0;
+    WorkClaims work;
+    work.init(p.claims, wave, waves_per_block);
+    for (;;) {
+        const uint64_t load = work.take(lane);
+        if ((load >> 32) != 0 || (uint32_t)load >= loads) // (scalar compares)
+            break;
+        // ---- this pair's stream: its index entries, all of them the caller's data
+        const uint32_t ln = lane_number_now();
+        const uint32_t g = ln >> 1, i = ln & 1u;
+        const uint64_t pos = load * 32u + g;
+        const bool exists = pos < p.nchunks;
+        uint64_t s = pos;
+        if (exists && p.order)
+            s = p.order[pos];
+        const bool named = exists && s < p.nchunks;
+        if (exists && !named && i == 0) // an order entry that names no stream: nothing coded, no index entry
+            atomicOr(p.flags, 2048u);
+        uint64_t first = 0, slot_at = 0, slot_end = 0;
+        uint32_t count = 0;
+        if (named) {
+            first = p.sym_offsets[s];
+            count = p.sym_counts[s];
+            slot_at = p.slot_offsets[s];
+            slot_end = p.slot_offsets[s + 1];
+        }
+        // what rans_amd_chunk_bound() asks for this stream: two bytes per symbol + the two flushed states
+        const uint64_t need = ((uint64_t)count * 2u + 2u * 4u + 15u) & ~15ull;
+        const uint64_t slot_size = slot_end - slot_at;
+        const bool fits = ((slot_at | slot_end) & 15u) == 0 && slot_end >= slot_at && slot_end <= p.out_cap && slot_size >= need &&
+                          slot_size <= 0xfffffff0ull;
+        if (named && !fits && i == 0) { // nothing of this stream is written
+            atomicOr(p.flags, 2u);
+            p.lengths[s] = 0u;
+            p.offsets[s] = slot_end;
+        }
+        bool live = named && fits; // the pair holds a stream that is still being coded
+        const uint32_t slot = (uint32_t)slot_size;
+        const uint64_t out_end = reinterpret_cast<uint64_t>(p.scratch) + slot_end; // (live: 16-byte aligned, inside the container)
+        const uint64_t src = reinterpret_cast<uint64_t>(p.syms) + first;
+        const uint32_t pieces = (live && (src & 3u) == 0) ? count >> 5 : 0u;
+        const uint32_t tail = live ? count - (pieces << 5) : 0u; // (< 2^31: count < 2^31 follows from the slot's size)
+        const uint32_t tail_rounds = (tail + 1u) >> 1;
+        const uint32_t max_pieces = wave_max32(pieces), max_tail_rounds = wave_max32(tail_rounds);
+
+        uint32_t x = Tr::kL, c = 0, fb = 0; // state, bytes emitted so far (the pair's), blocks flushed
+        // block fb of the ring -> its place below the slot's end; a piece that would start below the slot's first byte is dropped,
+        // and so is one that lies wholly below the stream (k_encode_batch_word_groups' two guards); nothing leaves a dead pair
+        auto flush_block = [&](uint32_t have_bytes) { // have_bytes: the pair's stream so far
+            const uint64_t below = (uint64_t)kPairBlock * (fb + 1u) - (ring_i - ring); // this lane's 16 bytes start `below` bytes under the slot's end
+            if (live && below <= slot && below - 16u < have_bytes) {
+                RANS_LDS const uint32_t *b = reinterpret_cast<RANS_LDS const uint32_t *>((uintptr_t)(ring_i + ((fb & 1u) ? 0u : kPairBlock)));
+                const u32x4 v = {b[0], b[1], b[2], b[3]}; // (rows are 4-byte aligned: four dword reads)
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(out_end - below) = v;
+            }
+            fb += 1u;
+        };
+        // ---- tail: the rounds behind the stream's last whole piece, the pair's last round first
+        {
+            const uint8_t RANS_GLOBAL *tsrc = reinterpret_cast<const uint8_t RANS_GLOBAL *>(src + ((uint64_t)pieces << 5) + i);
+            const int lane_o = (int)(4u * (ln ^ 1u)); // the pair's other lane
+            for (uint32_t k = 0; k < max_tail_rounds; ++k) {
+                const bool in = k < tail_rounds; // (the same for both lanes of a pair)
+                const uint32_t r = tail_rounds - 1u - k;
+                const bool active = in && 2u * r + i < tail; // (an odd count: state 1 sits the first round out)
+                encode_pair_round(x, c, worst, active ? (uint32_t)tsrc[(uint64_t)r * 2u] : 0u, active, i, top, lane_o);
+                // (at least every eight rounds of any pair; never true for a pair that sits out: its c stands still)
+                if ((k & 7u) == 7u && c >= kPairBlock * (fb + 1u))
+                    flush_block(c);
+            }
+        }
+        // ---- pieces: sixteen rounds each, the pair's last piece first
+        uint64_t lp = src + ((uint64_t)pieces << 5) + (ring_i - ring); // 32 bytes above this lane's half of the next piece to load
+        auto load_piece = [&](bool want) -> u32x4 {
+            u32x4 v = {0u, 0u, 0u, 0u}; // (a dead pair codes zeros)
+            if (want) {
+                lp -= kPairBlock;
+                const u32x4_sym t = *reinterpret_cast<const u32x4_sym RANS_GLOBAL *>(lp);
+                v = u32x4{t.x, t.y, t.z, t.w};
+            }
+            return v;
+        };
+        u32x4 next = load_piece(pieces != 0u);
+        for (uint32_t q = 0;; ++q) {
+            if (live && q == pieces) { // ---- finalise: this pair's last round is behind it
+                if (c >= kPairBlock * (fb + 1u)) // (the last eight rounds' block)
+                    flush_block(c);
+                // RansEncFlush(rans1), then (rans0): state 1's dword ends c bytes below the slot's end, state 0's dword below it;
+                // byte J of a dword is stream byte k + 3 - J, k the position of its top byte
+                const uint32_t k = c + (ring_i == ring ? 4u : 0u);
+#pragma unroll
+                for (uint32_t j = 0; j < 4u; ++j)
+                    *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(top - ((k + 3u - j) & 63u))) = (uint8_t)(x >> (8u * j));
+                c += 2u * 4u;
+                const uint32_t len = c;
+                if (kPairBlock * fb < c)
+                    flush_block(len);
+                if (kPairBlock * fb < c)
+                    flush_block(len);
+                if (ring_i == ring) {
+                    p.lengths[s] = len;
+                    p.offsets[s] = slot_end - len;
+                }
+                live = false; // dead: no block, no index store ever again
+            }
+            if (q == max_pieces)
+                break;
+            const bool run = q < pieces;
+            // (the next piece is asked for BEHIND the exchange that consumes this one: the compiler cannot count a conditional
+            //  load, its s_waitcnt vmcnt(0) stands in front of the first use of a loaded register -- the exchange -- and in
+            //  this order the load it waits for was issued sixteen rounds ago)
+            uint32_t d0, d1, d2, d3;
+            piece_to_states(next, d0, d1, d2, d3, sel);
+            next = load_piece(q + 1u < pieces);
+            const uint32_t worst_keep = worst;
+            encode_piece<TRACK>(d0, d1, d2, d3, x, c, worst, fb, k4, top, flush_block); // (under full exec: see the head)
+            worst = run ? worst : worst_keep;
+        }
+    }
+    if (TRACK && __builtin_amdgcn_ballot_w64((worst >> 31) != 0) != 0 && lane == 0)
+        atomicOr(p.flags, 1u);
+}
+
 } // namespace
 
 // (api.cpp asks this while it still fills the parameters in: only what it sets first counts -- the shape, the symbol buffer, the
@@ -485,6 +802,29 @@ hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipS
         {launch_group_kernel<k_encode_batch_word_groups<false, false>, EncParams>, launch_group_kernel<k_encode_batch_word_groups<false, true>, EncParams>},
         {launch_group_kernel<k_encode_batch_word_groups<true, false>, EncParams>, launch_group_kernel<k_encode_batch_word_groups<true, true>, EncParams>}};
     return launch_encode_groups(launches, p, num_cus, stream);
+}
+
+// the ragged form of the byte format's 2-way layout over u8 symbols, from 32 streams on, at the scale_bits the pair decoder
+// takes (a batch that decodes on pairs also encodes on pairs); counts, symbol addresses and slots are the kernel's to check
+bool encode_batch_byte_pairs_applicable(const EncParams &p)
+{
+    return p.n_ways == 2 && p.sym_bytes == 1 && p.nsyms <= 256 && p.scale_bits >= 8 && p.scale_bits <= 16 && p.nchunks >= 32 &&
+           (reinterpret_cast<uintptr_t>(p.scratch) & 15u) == 0;
+}
+
+// one wave-load per wave; 4 KiB of records and sixteen waves of ring rows: inside the default dynamic-LDS limit, two blocks
+// per CU whatever the model's scale_bits
+hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, const char **pair_batch_enc_kernel)
+{
+    if (!encode_batch_byte_pairs_applicable(p) || !p.enc_recs || !p.sym_offsets || !p.sym_counts || !p.slot_offsets || !p.lengths || !p.offsets ||
+        !p.flags)
+        return hipErrorInvalidValue;
+    if (pair_batch_enc_kernel)
+        *pair_batch_enc_kernel = "k_encode_batch_byte_pairs";
+    const size_t lds = kEncPairTable + (size_t)(kGrpThreads / 64) * kPairWaveLds;
+    const uint64_t loads = (p.nchunks + 31u) / 32u;
+    return p.dense256 ? launch_group_kernel<k_encode_batch_byte_pairs<false>, EncParams>(loads, lds, 0, num_cus, stream, p)
+                      : launch_group_kernel<k_encode_batch_byte_pairs<true>, EncParams>(loads, lds, 0, num_cus, stream, p);
 }
 
 } // namespace rans_amd

@@ -1,6 +1,6 @@
-// groups_common.hpp -- what the six group kernels share (internal): decode_groups.hip's k_decode_word_groups,
+// groups_common.hpp -- what the seven group kernels share (internal): decode_groups.hip's k_decode_word_groups,
 // k_decode_batch_word_groups, k_decode_byte_pairs, k_decode_batch_byte_pairs and encode_groups.hip's k_encode_word_groups,
-// k_encode_batch_word_groups.  Every piece is written once here, forceinline, and where the kernels differ the difference is
+// k_encode_batch_word_groups, k_encode_batch_byte_pairs.  Every piece is written once here, forceinline, and where the kernels differ the difference is
 // an argument or a template parameter that is constant at the call site (profiles/groups_common_isa.md: what each kernel
 // compiles to with them).  The hand-scheduled sequences stay with their kernels.  Helpers that took the place of a lambda
 // take their arguments as the lambda did -- what it captured by `const T &`, its own parameters by value: the register
@@ -418,6 +418,61 @@ __device__ __forceinline__ void encode_word_round(uint32_t &x, uint32_t &c, uint
         x = x + rec.w + (q & 0xffffffu) * (rec.z & 0xffffffu);
         worst |= rec.z;
     }
+}
+
+// The byte format's pair (rans_byte.h:62-90, main.cpp:226-246), one compiler-scheduled round: state 1 puts first, so the odd
+// lane's bytes start at the pair's cursor c (bytes emitted so far) and the even lane's behind them -- the other lane's count
+// comes through ds_bpermute with lane_o, the byte address of the lane to read.  Stream byte k (0 = the first emitted, the
+// stream's LAST byte) lives at `top` - (k & 63) of the pair's 64-byte ring (top: raw LDS address of the ring's byte 63); a
+// state emits its low byte first.  Lanes without a symbol sit the round out: they emit nothing, track nothing, keep their x.
+// Record {rcp, cmpl | rshift << 24, bias, x_max} at LDS address sym << 4 (encode_common.hpp enc_byte_full's).
+__device__ __forceinline__ void encode_pair_round(uint32_t &x, uint32_t &c, uint32_t &worst, uint32_t sym, bool active, uint32_t odd, uint32_t top,
+                                                  int lane_o)
+{
+    const u32x4 rec = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(sym << 4));
+    uint32_t n = 0;
+    if (active)
+        n = (uint32_t)(x >= rec.w) + (uint32_t)((x >> 8) >= rec.w); // `while (x >= x_max)`: never more than twice for scale_bits <= 16
+    const uint32_t n_other = (uint32_t)__builtin_amdgcn_ds_bpermute(lane_o, (int)n);
+    const uint32_t at = c + (odd ? 0u : n_other);
+    c += n + n_other;
+    if (n >= 1u)
+        *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(top - (at & 63u))) = (uint8_t)x;
+    if (n >= 2u)
+        *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(top - ((at + 1u) & 63u))) = (uint8_t)(x >> 8);
+    x >>= 8u * n;
+    if (active) { // x = bias + x + (x / freq) * cmpl_freq, the quotient by Alverson's reciprocal: exact for x < 2^31
+        const uint32_t q = __umulhi(x, rec.x) >> ((rec.y >> 24) & 31u);
+        x = x + rec.z + q * (rec.y & 0xffffffu);
+        worst |= rec.y;
+    }
+}
+
+// The lane number, worked out on the spot (volatile: not hoisted out of a claim loop, so that nothing that follows from it
+// stays in registers across the loop's hand-scheduled part).
+__device__ __forceinline__ uint32_t lane_number_now()
+{
+    uint32_t l;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+    return l;
+}
+
+// over the 32 pairs (v is the same in a pair's lanes): a butterfly over lane ^ 2, 4, 8, 16 inside each half of the wave
+// (ds_swizzle in bit-mask mode: and 0x1f, or 0, xor d -- no address register), then the larger of the two halves
+// (k_decode_batch_byte_pairs keeps its own copy of this and of the lane number as lambdas: it is left as it compiles)
+__device__ __forceinline__ uint32_t wave_max32(uint32_t v)
+{
+    uint32_t t;
+    t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x081f);
+    v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x101f);
+    v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x201f);
+    v = t > v ? t : v;
+    t = (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401f);
+    v = t > v ? t : v;
+    const uint32_t lo = __builtin_amdgcn_readlane(v, 0), hi = __builtin_amdgcn_readlane(v, 32);
+    return lo > hi ? lo : hi;
 }
 
 // ---- index entries of a ragged stream (the decoders') --------------------------------------------------------------

@@ -96,6 +96,11 @@ hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_
 // symbol count, symbol address and slot, from eight streams on; the name goes to *group_batch_enc_kernel
 bool encode_batch_word_groups_applicable(const EncParams &p);
 hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **group_batch_enc_kernel);
+// the byte format's 2-way layout, ragged (rans_amd_encode_batch[_ordered] under kVarBatchEncPairs): 32 STREAMS per wave, each
+// with its own symbol count, symbol address and slot, from 32 streams on, scale_bits 8..16; the name goes to
+// *pair_batch_enc_kernel
+bool encode_batch_byte_pairs_applicable(const EncParams &p);
+hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, const char **pair_batch_enc_kernel);
 
 // lane-per-stream kernels (N = 1, 2, 4, 8 with at least kLaneKernelMinChunks chunks): decode_lanes.hip, encode_lanes.hip
 constexpr uint64_t kLaneKernelMinChunks = 64;

@@ -1,0 +1,163 @@
+"""Ragged batches CODED with thirty-two 2-way byte streams per wave (RANS_AMD_OPT_BATCH_ENCODE_PAIRS), the part that needs no
+GPU: the name test of the pair batch ENCODER, the option's constant, and the proof that the inputs of
+tests/test_gpu_batch_encode_pairs.py reach the bounds that file claims.
+
+test_no_pair_batch_enc_kernel_without_a_row: the launcher of the encoder that packs 32 ragged byte streams into a wave
+reports its kernel through an out-parameter spelled `*pair_batch_enc_kernel = ...;` -- a seventh spelling beside `*name =
+...;` (tests/test_gpu_kernel_matrix.py), `*batch_kernel = ...;` (tests/test_batch_host.py), `*models_batch_kernel = ...;`
+(tests/test_batch_models_host.py), `*group_batch_kernel = ...;` (tests/test_batch_groups_host.py), `*group_batch_enc_kernel =
+...;` (tests/test_batch_encode_groups_host.py) and `*pair_batch_kernel = ...;` (tests/test_batch_pairs_host.py), invisible to
+those six tests, which anchor on the `*`.  Every literal of such a statement in ryg_rans_amd/csrc/*.hip must be the encode
+name of a row of ENC_PAIR_ROWS in tests/test_gpu_batch_encode_pairs.py, and ENC_PAIR_ROWS must name no encoder the sources
+do not contain."""
+import glob
+import os
+import re
+
+import numpy as np
+
+import _stream_rate as S
+import ryg_rans_amd as R
+from _oracle import FMT_BYTE
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
+_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
+
+
+def source_pair_batch_enc_kernel_names(csrc=CSRC):
+    """Every string literal of a statement `*pair_batch_enc_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
+    names, sites = set(), 0
+    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
+        for m in re.finditer(r"\*pair_batch_enc_kernel\s*=\s*([^;]*);", open(path).read()):
+            sites += 1
+            names.update(_LITERAL.findall(m.group(1)))
+    return names, sites
+
+
+def test_no_pair_batch_enc_kernel_without_a_row():
+    from test_gpu_batch_encode_pairs import ENC_PAIR_ROWS
+    names, sites = source_pair_batch_enc_kernel_names()
+    assert sites >= 1, sites
+    assert "k_encode_batch_byte_pairs" in names
+    rows = {r["encode"] for r in ENC_PAIR_ROWS}
+    assert names == rows, ("kernels no row of ENC_PAIR_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
+    assert all(r["ways"] == 2 and r["fmt"] == FMT_BYTE for r in ENC_PAIR_ROWS)
+    assert sorted((r["sb"], r["K"]) for r in ENC_PAIR_ROWS) == [(8, 256), (10, 64), (12, 256), (14, 256), (16, 256)]
+    # the decoder is named where the issue names it, and asked of the default context elsewhere (None)
+    assert {(r["sb"], r["decode"]) for r in ENC_PAIR_ROWS} == {(14, "k_decode_batch<byte>"), (16, "k_decode_batch<byte>"), (12, None), (8, None),
+                                                              (10, None)}
+    # disjoint from what the six other spellings' scans find
+    from test_batch_encode_groups_host import source_group_batch_enc_kernel_names
+    from test_batch_groups_host import source_group_batch_kernel_names
+    from test_batch_host import source_batch_kernel_names
+    from test_batch_models_host import source_models_batch_kernel_names
+    from test_batch_pairs_host import source_pair_batch_kernel_names
+    from test_gpu_kernel_matrix import source_kernel_names
+    for scan in (source_kernel_names, source_batch_kernel_names, source_models_batch_kernel_names, source_group_batch_kernel_names,
+                 source_group_batch_enc_kernel_names, source_pair_batch_kernel_names):
+        assert not names & scan()[0], scan.__name__
+    # the check has teeth: without its rows the kernel is reported missing
+    less = {r["encode"] for r in ENC_PAIR_ROWS if not r["id"].startswith("byte-2-enc-pairs")}
+    assert "k_encode_batch_byte_pairs" in names - less
+
+
+def test_batch_encode_pairs_option_constant():
+    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
+    m = re.search(r"RANS_AMD_OPT_BATCH_ENCODE_PAIRS\s*=\s*(\d+)", header)
+    assert m and int(m.group(1)) == 8
+    assert R.OPT_BATCH_ENCODE_PAIRS == 8
+    # options 0..7 are where they were, and the version has not moved (additions only)
+    for name, value in (("LANE_KERNELS", 0), ("LANE_FUSED_PLACEMENT", 1), ("FUSED_PLACEMENT", 2), ("DUAL_DECODE", 3),
+                        ("ENC_SCRATCH_RING", 4), ("BATCH_GROUPS", 5), ("BATCH_ENCODE_GROUPS", 6), ("BATCH_PAIRS", 7)):
+        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % name, header)
+        assert m and int(m.group(1)) == value, name
+        assert getattr(R, "OPT_" + name) == value, name
+    assert re.search(r"#define\s+RANS_AMD_VERSION\s+600\b", header)
+    # (a NULL context is refused before the option is looked at; the values need a context: tests/test_gpu_batch_encode_pairs.py)
+    assert R.lib().rans_amd_ctx_set_option(None, 8, 1) == R.E_ARG
+    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+
+
+def _full_windows(rb, n):
+    """Sums over every window of eight FULL rounds (an odd count's last round holds state 0 alone)."""
+    return S.windows(rb[:n // 2])
+
+
+def test_rate_inputs_reach_the_rings_bound():
+    """1. Under 255 x 1 + one common symbol at 16 bits (test_gpu_batch_pairs.rate_model) a state that meets a frequency-1
+    symbol puts two bytes, in every round: the frequency-1-only streams of the GPU file with at least eight rounds hold 32
+    bytes in every window of eight full rounds -- a block per check of the pair's ring, its bound --, the common-only ones
+    emit nothing (the 65536-symbol one: a thousand and more silent rounds in a row)."""
+    import test_gpu_batch_encode_pairs as G
+    from test_gpu_batch_pairs import RATE_WAVES, rate_kind, rate_model
+    assert G.OPT_BATCH_ENCODE_PAIRS == R.OPT_BATCH_ENCODE_PAIRS and G.OPT_BATCH_PAIRS == R.OPT_BATCH_PAIRS
+    assert G.E16["sb"] == 16 and G.EMAIN["sb"] == 14
+    freqs, counts, contents, _ = G.rate_batch(16)
+    assert np.array_equal(freqs, rate_model(16)) and counts.size == 64
+    rare_long = 0
+    for k in range(64):
+        n = int(counts[k])
+        rb = S.round_bytes(FMT_BYTE, freqs, 16, contents[k], 2)
+        if rate_kind(k) == "rare":
+            assert np.all(freqs[contents[k]] == 1)
+            if n // 2 >= 8:
+                w = _full_windows(rb, n)
+                assert w.min() == 32 and w.max() == 32, (k, n, w.min(), w.max())
+                rare_long += 1
+        else:
+            assert np.all(contents[k] == S.COMMON) and rb.sum() == 0, (k, n)
+    assert rare_long >= 20, rare_long
+    silent = 0
+    for name, (w_counts, w_kinds) in RATE_WAVES.items():
+        freqs, counts, contents, _ = G.rate_wave(16, name)
+        assert counts.size == 32
+        for k in range(32):
+            n = int(counts[k])
+            rb = S.round_bytes(FMT_BYTE, freqs, 16, contents[k], 2)
+            if w_kinds[k] == "rare":
+                if n // 2 >= 8:
+                    w = _full_windows(rb, n)
+                    assert w.min() == 32 and w.max() == 32, (name, k, n)
+            elif n == 65536:
+                assert S.longest_silence(rb) >= 1000, (name, k, S.longest_silence(rb))
+                silent += 1
+            else:
+                assert rb.sum() == 0, (name, k)
+    assert silent >= 1
+
+
+def test_a_dead_pair_is_fed_the_rings_bound():
+    """2. The MIRRORED model, f = ones(256), f[255] = 2^16 - 255: byte value 0 -- what a dead pair codes -- is a frequency-1
+    symbol.  A stream of zeros holds 32 bytes in every window of eight full rounds (4097 zeros: 30..32, and a window below 32
+    holds the odd count's half round); a stream of 255s is silent (4096 of them: 2 bytes in all).
+    3. The finish inputs begin with at least 64 frequency-1 symbols other than 0 and never contain 0.
+    4. The no-zero model has f[0] == 0, and no content under it holds a 0."""
+    import test_gpu_batch_encode_pairs as G
+    f = G.mirrored_model()
+    want = np.ones(256, dtype=np.uint32)
+    want[255] = (1 << 16) - 255
+    assert np.array_equal(f, want) and int(f.sum()) == 1 << 16 and f[0] == 1
+    rb = S.round_bytes(FMT_BYTE, f, 16, np.zeros(4096, dtype=np.uint8), 2)
+    w = S.windows(rb)
+    assert w.min() == 32 and w.max() == 32, (w.min(), w.max())
+    rb = S.round_bytes(FMT_BYTE, f, 16, np.zeros(4097, dtype=np.uint8), 2)
+    w = S.windows(rb)
+    assert rb.size == 2049 and w.min() == 30 and w.max() == 32, (w.min(), w.max())
+    assert np.all(_full_windows(rb, 4097) == 32) and np.all(np.nonzero(w < 32)[0] + 8 == rb.size)  # (the window with the half round)
+    rb = S.round_bytes(FMT_BYTE, f, 16, np.full(4096, 255, dtype=np.uint8), 2)
+    assert rb.sum() == 2 and S.longest_silence(rb) >= 1000, (int(rb.sum()), S.longest_silence(rb))
+    # 3.
+    freqs, counts, contents = G.finish_batch()
+    assert np.array_equal(freqs, f) and counts.tolist() == [128 * (g % 8 + 1) for g in range(32)]
+    for g in range(32):
+        c = contents[g]
+        assert c.size == counts[g] and not np.any(c == 0)
+        assert np.all(freqs[c[:64]] == 1) and np.all(c[:64] != 0)
+        S.simulate(FMT_BYTE, freqs, 16, c, 2)  # (a valid stream under the model)
+    # 4.
+    freqs, counts, contents = G.no_zero_batch()
+    assert freqs[0] == 0 and int(freqs.sum()) == 1 << 14 and counts.size == 96 and int(np.count_nonzero(counts == 0)) >= 1
+    assert all(contents[k].size == counts[k] and not np.any(contents[k] == 0) for k in range(96))
+    assert len({int(c) >> 5 for c in counts[32:64]}) >= 16 and counts[32:64].max() >= 256  # (the pairs die at different pieces)

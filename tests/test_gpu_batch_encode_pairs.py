@@ -1,0 +1,534 @@
+"""Ragged batches of the reference's 2-way byte layout CODED with thirty-two streams per wave: k_encode_batch_byte_pairs, the
+kernel rans_amd_encode_batch[_ordered] launches on a context with RANS_AMD_OPT_BATCH_ENCODE_PAIRS = 1.
+
+ENC_PAIR_ROWS names the kernel the library must report (tests/test_batch_encode_pairs_host.py holds the rows to the names the
+launchers can report).  The helpers are tests/test_gpu_batch.py's: run_row checks the reported kernel, every stream byte for
+byte against the oracle's, each ending at its slot's end, and decodes the result.  The decoder a row names is the one the
+context reports for that shape with the option at its default: "k_decode_batch<byte>" for the 14-bit and 16-bit rows, and
+for the other three whatever the default context reports (asked at run time, decoder_of; run_row then asserts it).
+
+The coder works from a stream's last symbol to its first, so a wave's 32 pairs start together and finish at different
+times: a pair is finalised (states, last blocks, index entry) right behind its last round and is dead from then on, while
+the wave's eight-round sequence -- full exec, every lane's byte count its own two compares -- runs on for the others: a dead
+pair's cursor moves, and its lanes keep writing into its ring.  The shapes below are the smallest at which that can go wrong;
+the rate inputs are proved to reach their bounds without a GPU by tests/test_batch_encode_pairs_host.py, which imports the
+generators below.
+
+Containers of two encodes are compared over the bytes of their streams: the 16-byte piece that holds a stream's first byte
+is stored whole, and what it holds below the stream is whatever the pair's ring held (as with the wave kernels' flushes).
+Wall time on an MI355X: 7.3 s for the 40 cases of this file -- 2.7 s of it the captured graph's child process, 1.7 s the first
+case's setup and 0.6 s its call (they load the kernels), 0.4 s the `half` regime, 0.26 s the 65536-symbol rare stream beside
+dead pairs, 0.13 s the `several` regime and the per-stream-models case, 0.06 s and less for each of the others."""
+import os
+
+import numpy as np
+import pytest
+
+import _stream_rate as S
+from _oracle import FMT_BYTE, FMT_WORD
+from test_gpu_batch import POISON, ROW, Batch, draw_lengths, mandatory_lengths, resident_waves, run_row
+from test_gpu_batch_encode_groups import encode_poisoned, same_result
+from test_gpu_batch_pairs import POOL, PoolBatch, draw_log_uniform, rate_batch, rate_wave
+from test_gpu_batch_pairs import PMAIN as DEC_PAIR_ROW
+
+OPT_BATCH_ENCODE_GROUPS = 6
+OPT_BATCH_PAIRS = 7
+OPT_BATCH_ENCODE_PAIRS = 8
+KERNEL = "k_encode_batch_byte_pairs"
+WAVE = "k_encode_batch<byte>"
+
+
+def _enc_pair_row(rid, sb, K, decode):
+    return {"id": rid, "fmt": FMT_BYTE, "sb": sb, "K": K, "ways": 2, "decode": decode, "encode": KERNEL}
+
+
+# decode None: the decoder the default context reports for the shape (decoder_of)
+ENC_PAIR_ROWS = [
+    _enc_pair_row("byte-2-enc-pairs", 14, 256, "k_decode_batch<byte>"),       # the reference's scale_bits (main.cpp:139)
+    _enc_pair_row("byte-2-enc-pairs-16bit", 16, 256, "k_decode_batch<byte>"),
+    _enc_pair_row("byte-2-enc-pairs-12bit", 12, 256, None),
+    _enc_pair_row("byte-2-enc-pairs-8bit", 8, 256, None),
+    _enc_pair_row("byte-2-enc-pairs-64sym-10bit", 10, 64, None),                # (the record table is padded to 256)
+]
+EROWS = {r["id"]: r for r in ENC_PAIR_ROWS}
+EMAIN, E16 = EROWS["byte-2-enc-pairs"], EROWS["byte-2-enc-pairs-16bit"]
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the GPU box"
+    import ryg_rans_amd as R
+    ctx = R.Context(0)
+    ctx.set_option(OPT_BATCH_ENCODE_PAIRS, 1)  # (only the new option)
+    off = R.Context(0)  # everything at its default: the wave-per-stream kernels
+    yield R, ctx, torch, off
+    off.close()
+    ctx.close()
+
+
+_DECODERS = {}
+
+
+def decoder_of(gpu, oracle, row):
+    """The row with the decoder's name filled in: what the default context reports when it decodes the shape."""
+    if row["decode"] is not None:
+        return row
+    if row["id"] not in _DECODERS:
+        R, _, torch, off = gpu
+        b = Batch(R, off, torch, oracle, dict(row, encode=WAVE), np.array([300] * 33, dtype=np.uint32))
+        d_buf, sym_offs, slot_offs = b.laid_out(4)
+        d_sym = b.dev(sym_offs, np.int64)
+        cont, offs, lens = off.encode_batch(b.gm, d_buf, d_sym, b.d_counts, 2, b.dev(slot_offs, np.int64))
+        off.encode_status()
+        assert off.last_encode_kernel()[0] == WAVE, off.last_encode_kernel()
+        out = torch.full_like(d_buf, b.poison())
+        off.decode_batch(b.gm, cont, int(slot_offs[-1]), offs, lens, d_sym, b.d_counts, 2, out)
+        assert torch.equal(out, d_buf)
+        _DECODERS[row["id"]] = off.last_decode_kernel()
+    return dict(row, decode=_DECODERS[row["id"]])
+
+
+# ---- inputs that the host test proves to sit at their bounds (tests/test_batch_encode_pairs_host.py) -----------------
+def mirrored_model():
+    """255 x 1 and one common symbol at 2^16, the common one LAST: byte value 0 -- what a dead pair is fed -- has frequency 1."""
+    f = np.ones(256, dtype=np.uint32)
+    f[255] = (1 << 16) - 255
+    return f
+
+
+def finish_batch():
+    """One wave-load under the mirrored model, counts 128 (g % 8 + 1): whole pieces only, every pair finishes at a piece
+    boundary while others run on.  Every stream BEGINS with 64 frequency-1 symbols other than 0 -- the last the coder sees --
+    and holds no 0; runs of 64 frequency-1 and 64 common symbols in turn.  A dead pair is fed zeros: two bytes per lane and
+    round, 32 bytes per eight rounds, the ring's bound -> (freqs, counts, {stream: symbols})."""
+    freqs = mirrored_model()
+    counts = np.array([128 * (g % 8 + 1) for g in range(32)], dtype=np.uint32)
+    contents = {}
+    for g in range(32):
+        n = int(counts[g])
+        c = np.random.default_rng(40 + g).integers(1, 255, n).astype(np.uint8)
+        c[(np.arange(n) // 64) % 2 == 1] = 255
+        contents[g] = c
+    return freqs, counts, contents
+
+
+def no_zero_model():
+    """Byte value 0 has no record (frequency 0), every other value has: 16130 + 254 x 1 at 14 bits.  dense256 is false: TRACK."""
+    f = np.ones(256, dtype=np.uint32)
+    f[0] = 0
+    f[1] = (1 << 14) - 254
+    return f
+
+
+def no_zero_batch():
+    """96 streams (three wave-loads) of uneven counts, one of them 0, drawn from no_zero_model: pairs die at different times,
+    some from the start."""
+    freqs = no_zero_model()
+    counts = np.array([(37 * k * k + 11 * k) % 1500 for k in range(96)], dtype=np.uint32)
+    return freqs, counts, {k: S.drawn(freqs, int(counts[k]), 80 + k) for k in range(96)}
+
+
+def _padded(lengths, n=32, pad=200):
+    return list(lengths) + [pad] * (n - len(lengths))
+
+
+WAVE_LOADS = {
+    "one-piece-x4-each": [128] * 32,
+    "boundaries": _padded([0, 1, 2, 3, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256]),
+    "31-dead-one-flushing": [65536] + [255] * 31,
+    "every-pair-finishes-elsewhere": [128 * (g + 1) + 3 * g for g in range(32)],
+    "quad-mates-differ": [640, 0, 128, 385] * 8,
+    "all-empty": [0] * 32,
+    "second-load-of-one": [300] * 33,
+    "mandatory-and-200s": _padded(mandatory_lengths(2)),
+}
+
+
+def _wave_load_cases():
+    for name in WAVE_LOADS:
+        for row in (ENC_PAIR_ROWS if name == "one-piece-x4-each" else (EMAIN, E16)):
+            yield pytest.param(name, row, id="%s-%s" % (name, row["id"]), marks=pytest.mark.gpu)
+
+
+@pytest.mark.parametrize("name,row", list(_wave_load_cases()))
+def test_single_wave_loads(gpu, oracle, name, row):
+    """One or two wave-loads: four whole pieces each and no tail; every piece and tail boundary in one wave; 31 pairs dead for
+    2040 pieces while one keeps flushing; every pair finishing at another piece, some with an odd count; quad-mates that
+    differ; 32 empty streams (8 bytes each: the flushed initial states); a second wave-load of one stream; the mandatory
+    lengths.  Each at sym_align 1 (every symbol a round at a time, byte loads) and 4."""
+    R, ctx, torch, _ = gpu
+    b = Batch(R, ctx, torch, oracle, decoder_of(gpu, oracle, row), np.array(WAVE_LOADS[name], dtype=np.uint32))
+    for align in (1, 4):
+        run_row(b, align)
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_dead_pair_at_the_rings_bound(gpu, oracle):
+    """finish_batch: every pair finishes at a piece boundary while others run on, and is then fed the frequency-1 symbol 0:
+    its lanes write two bytes each in every round, wherever its cursor is.  Every stream equals the oracle's (run_row) -- in
+    particular its first 10 bytes, the last written: the two flushed states and the two bytes below them."""
+    R, ctx, torch, _ = gpu
+    freqs, counts, contents = finish_batch()
+    b = Batch(R, ctx, torch, oracle, E16, counts, contents=contents, freqs=freqs)
+    cont, offs, lens = run_row(b, 4)[:3]  # (asks encode_status())
+    h, h_offs = cont.cpu().numpy(), offs.cpu().numpy()
+    for g in range(32):
+        a = int(h_offs[g])
+        assert b.lens[g] >= 10 and np.array_equal(h[a:a + 10], b.streams[g][:10]), ("states and last bytes of pair", g)
+    ctx.encode_status()
+
+
+def _rate_cases():
+    for which in ("fast-beside-parked", "stalled-beside-draining", 16, 14):
+        yield pytest.param(which, id=str(which), marks=pytest.mark.gpu)
+
+
+@pytest.mark.parametrize("which", list(_rate_cases()))
+def test_rate_extremes_in_one_wave(gpu, oracle, which):
+    """tests/test_gpu_batch_pairs.py's rate inputs on the encoder: a frequency-1-only stream of 65536 symbols (32 bytes per
+    eight rounds: a block per check) beside 31 common-only ones that are dead for most of it; a common-only stream of 65536
+    (no block for a thousand rounds and more) beside rare-only ones that drain one after the other; and the 64-stream batches
+    at 16 and 14 bits.  At sym_align 4 and 1, without an order (run_row) and under batch_order's (the same result)."""
+    R, ctx, torch, _ = gpu
+    if isinstance(which, str):
+        freqs, counts, contents, _ = rate_wave(16, which)
+        row = E16
+    else:
+        freqs, counts, contents, _ = rate_batch(which)
+        row = E16 if which == 16 else EMAIN
+    b = Batch(R, ctx, torch, oracle, row, counts, contents=contents, freqs=freqs)
+    d_order = ctx.batch_order(b.d_counts)
+    for align in (4, 1):
+        cont, offs, lens, d_buf, d_sym, d_slot, _, _ = run_row(b, align)
+        ordered = ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, 2, d_slot, d_order=d_order)
+        assert ctx.last_encode_kernel()[0] == KERNEL, ctx.last_encode_kernel()
+        ctx.encode_status()
+        same_result(torch, (cont, offs, lens), ordered, b.n, "under batch_order, align %d" % align)
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_no_false_e_model_from_dead_pairs(gpu, oracle):
+    """A model without byte value 0, contents that never use it, uneven counts: dead pairs are fed zeros and read the record
+    of byte value 0, which must not reach the flags.  encode_status() is OK (run_row asks) and every stream is the oracle's,
+    at both alignments."""
+    R, ctx, torch, _ = gpu
+    freqs, counts, contents = no_zero_batch()
+    assert freqs[0] == 0 and all(not np.any(c == 0) for c in contents.values())
+    b = Batch(R, ctx, torch, oracle, EMAIN, counts, contents=contents, freqs=freqs)
+    for align in (4, 1):
+        run_row(b, align)
+
+
+@pytest.mark.gpu
+def test_true_e_model_is_reported_and_contained(gpu, oracle):
+    """The same batch with one symbol of the longest stream of the second wave-load overwritten by 0 on the device: E_MODEL, as
+    the default context reports for the same batch; every stream of the other wave-loads is the oracle's; the poison behind
+    out_cap is intact; the next call succeeds."""
+    R, ctx, torch, off = gpu
+    freqs, counts, contents = no_zero_batch()
+    b = Batch(R, ctx, torch, oracle, EMAIN, counts, contents=contents, freqs=freqs)
+    gm_off = off.model(FMT_BYTE, freqs, 14)
+    d_buf, sym_offs, slot_offs = b.laid_out(4)
+    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
+    victim = 32 + int(np.argmax(counts[32:64]))
+    assert counts[victim] >= 256
+    bad = d_buf.clone()
+    bad[int(sym_offs[victim]) + int(counts[victim]) // 2] = 0
+    cap = int(slot_offs[-1])
+    for cx, gm, kernel in ((ctx, b.gm, KERNEL), (off, gm_off, WAVE)):
+        cont, offs, lens = encode_poisoned(b, cx, gm, bad, d_sym, d_slot, cap)
+        assert cx.last_encode_kernel()[0] == kernel, cx.last_encode_kernel()
+        with pytest.raises(R.RansAmdError) as e:
+            cx.encode_status()
+        assert e.value.status == R.E_MODEL, kernel
+        h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
+        for c in range(b.n):
+            if c // 32 != victim // 32:
+                a = int(h_offs[c])
+                assert h_lens[c] == b.lens[c] and a + int(h_lens[c]) == int(slot_offs[c + 1]), (kernel, c)
+                assert np.array_equal(h[a:a + int(h_lens[c])], b.streams[c]), (kernel, "stream", c)
+        assert np.all(h[cap:] == POISON), (kernel, "written behind the container")
+    ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, 2, d_slot)  # the next call succeeds
+    assert ctx.last_encode_kernel()[0] == KERNEL
+    ctx.encode_status()
+
+
+@pytest.mark.gpu
+def test_order(gpu, oracle):
+    """70 streams (two wave-loads and a partial third).  No order, the reversed identity and batch_order's result give the same
+    streams, offsets and lengths; an order with one entry replaced by n_streams reports E_ARG, every stream still named is
+    exact, and the stream that lost its position keeps its slot's poison and its pre-filled index entries."""
+    R, ctx, torch, _ = gpu
+    n = 70
+    counts = draw_lengths(n, 2, 23)
+    b = Batch(R, ctx, torch, oracle, EMAIN, counts)
+    d_buf, sym_offs, slot_offs = b.laid_out(4)
+    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
+    cap = int(slot_offs[-1])
+    d_order = ctx.batch_order(b.d_counts)
+    assert sorted(d_order.cpu().tolist()) == list(range(n))
+    results = []
+    for name, order in (("no order", None), ("reversed identity", b.dev(np.arange(n)[::-1], np.int32)), ("batch_order", d_order)):
+        res = encode_poisoned(b, ctx, b.gm, d_buf, d_sym, d_slot, cap, d_order=order)
+        assert ctx.last_encode_kernel()[0] == KERNEL and ctx.last_encode_placement() == 2, (name, ctx.last_encode_kernel())
+        ctx.encode_status()
+        b.check_streams(res[0].cpu().numpy(), res[1].cpu().numpy().astype(np.uint64), res[2].cpu().numpy().view(np.uint32), name)
+        assert np.all(res[0].cpu().numpy()[cap:] == POISON)
+        results.append(res)
+    same_result(torch, results[0], results[1], n, "reversed identity")
+    same_result(torch, results[0], results[2], n, "batch_order")
+    lost = int(np.argmax(counts))
+    order = np.arange(n)
+    order[lost] = n
+    cont, offs, lens = encode_poisoned(b, ctx, b.gm, d_buf, d_sym, d_slot, cap, d_order=b.dev(order, np.int32), sentinel=-77)
+    assert ctx.last_encode_kernel()[0] == KERNEL, ctx.last_encode_kernel()
+    with pytest.raises(R.RansAmdError) as e:
+        ctx.encode_status()
+    assert e.value.status == R.E_ARG
+    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
+    for c in range(n):
+        lo, hi = int(slot_offs[c]), int(slot_offs[c + 1])
+        if c == lost:
+            assert h_offs[c] == -77 and h_lens[c] == -77, "the index entry of the stream without a position was written"
+            assert np.all(h[lo:hi] == POISON), "the slot of the stream without a position was written"
+        else:
+            ln = int(h_lens[c])
+            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, c
+            assert np.array_equal(h[hi - ln:hi], b.streams[c]), ("stream", c)
+    assert np.all(h[cap:] == POISON)
+
+
+@pytest.mark.gpu
+def test_bad_slots(gpu, oracle):
+    """test_batch_encode_rejects_bad_slots' construction on 400 2-way streams with the option on: every slot 32 bytes larger
+    than its bound; a slot off 16 bytes on both sides (two streams), one a granule too small, one beyond out_cap -- each in a
+    wave-load with valid streams.  E_SPACE, the rejected slots keep their poison and get lengths 0, every other stream is
+    exact, the first 16 bytes of every accepted slot are still poison, nothing is written behind the container."""
+    R, ctx, torch, _ = gpu
+    counts = draw_lengths(400, 2, 71)
+    b = Batch(R, ctx, torch, oracle, EMAIN, counts)
+    d_buf, sym_offs, _ = b.laid_out(4)
+    bound = np.array([R.chunk_bound(FMT_BYTE, int(c), 2) for c in counts], dtype=np.int64)
+    sizes = bound + 32
+    idx = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    cap = int(idx[-1])
+    big = np.nonzero(counts >= 1000)[0]
+    off16, past = int(big[0]), 399
+    small = int(big[(big > off16 + 2) & (big < past - 1)][0])
+    bad_idx = idx.copy()
+    bad_idx[off16 + 1] += 8
+    bad_idx[small] = bad_idx[small + 1] - (bound[small] - 16)
+    rejected = {off16, off16 + 1, small, past}
+    assert len(rejected) == 4
+    for c in rejected:  # (its wave-load holds valid streams as well)
+        assert any(k not in rejected for k in range(32 * (c // 32), min(32 * (c // 32) + 32, 400)))
+    d_out = torch.full((cap + 4096,), POISON, dtype=torch.uint8, device="cuda")
+    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, b.dev(sym_offs, np.int64), b.d_counts, 2, b.dev(bad_idx, np.int64), d_out=d_out,
+                                        out_cap=cap - 16)
+    assert ctx.last_encode_kernel()[0] == KERNEL, ctx.last_encode_kernel()
+    with pytest.raises(R.RansAmdError) as e:
+        ctx.encode_status()
+    assert e.value.status == R.E_SPACE
+    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
+    for c in range(b.n):
+        lo, hi = int(bad_idx[c]), int(bad_idx[c + 1])
+        if c in rejected:
+            assert h_lens[c] == 0 and int(h_offs[c]) == hi, c
+            if hi > lo:
+                assert np.all(h[lo:hi] == POISON), ("a rejected slot was written", c)
+        else:
+            ln = int(h_lens[c])
+            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, c
+            assert np.array_equal(h[hi - ln:hi], b.streams[c]), ("stream", c)
+            assert np.all(h[lo:lo + 16] == POISON), ("the head of a slot was written", c)
+    assert np.all(h[cap:] == POISON), "written behind the container"
+
+
+def _streams_equal_prototypes(torch, pb, cont, offs, lens, what):
+    """Every stream of a coded PoolBatch, on the device: ends at its slot's end, has its prototype's length and bytes."""
+    n = pb.counts.size
+    assert torch.equal(lens[:n], pb.d_lens), (what, "lengths differ from the prototypes'")
+    ln = pb.d_lens.to(torch.int64)
+    assert torch.equal(offs[:n] + ln, pb.d_slot[1:]), (what, "a stream does not end at its slot's end")
+    within = torch.arange(int(ln.sum()), device="cuda") - torch.repeat_interleave(torch.cumsum(ln, 0) - ln, ln)
+    got = cont[torch.repeat_interleave(offs[:n], ln) + within]
+    want = pb.cont[torch.repeat_interleave(pb.d_offs, ln) + within]
+    assert torch.equal(got, want), (what, "stream bytes differ from the prototypes'")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("regime", ["half", "several"])
+def test_half_and_several(gpu, oracle, regime):
+    """half: fewer wave-loads than the launch has resident waves, prototype lengths log-uniform up to 64 Ki with the
+    mandatory ones.  several: at least 1.25 x as many wave-loads as resident waves, so that waves come back for further
+    claims and must reset state, cursor, block count and ring; prototype lengths log-uniform up to 1024.  Every stream is one
+    of at most 4096 prototypes the oracle coded once (tests/test_gpu_batch_pairs.py PoolBatch); every stream of the batch is
+    compared on the device with its prototype's.  The last wave-load is partial; with and without d_order at sym_align = 4;
+    the result decodes back on the wave kernel and, on a third context with RANS_AMD_OPT_BATCH_PAIRS, on
+    k_decode_batch_byte_pairs."""
+    import bench
+    R, ctx, torch, _ = gpu
+    resident = resident_waves(torch)
+    if regime == "half":
+        loads = resident // 32
+        protos = draw_lengths(1024, 2, 7)
+        assert 0 < loads < resident and set(mandatory_lengths(2)) <= set(protos.tolist())
+    else:
+        loads = resident + resident // 4 + 1
+        protos = draw_log_uniform(POOL, 1024, 9)
+        assert 4 * loads >= 5 * resident
+    n = loads * 32 - 5
+    pb = PoolBatch(R, ctx, torch, oracle, EMAIN, protos, n, 31)
+    assert pb.counts.size == n and n % 32 != 0 and protos.size <= POOL
+    cap = int(pb.slot_offs[-1])
+    dec = R.Context(0)
+    dec.set_option(OPT_BATCH_PAIRS, 1)
+    try:
+        sample = bench.gen_zipf(torch, 1 << 20, EMAIN["K"], 1.0, 3, "cuda")  # (PoolBatch's model)
+        freqs, _ = R.normalize_freqs(dec.count_freqs_device(sample, EMAIN["K"]), 1 << EMAIN["sb"])
+        gm_dec = dec.model(FMT_BYTE, freqs, EMAIN["sb"])
+        for order in (None, ctx.batch_order(pb.d_counts)):
+            what = "order" if order is not None else "no order"
+            cont, offs, lens = ctx.encode_batch(pb.gm, pb.d_buf, pb.d_sym, pb.d_counts, 2, pb.d_slot, d_order=order)
+            assert ctx.last_encode_kernel()[0] == KERNEL, ctx.last_encode_kernel()
+            ctx.encode_status()
+            _streams_equal_prototypes(torch, pb, cont, offs, lens, what)
+            for cx, gm, kernel in ((ctx, pb.gm, EMAIN["decode"]), (dec, gm_dec, DEC_PAIR_ROW["decode"])):
+                out = torch.full_like(pb.d_buf, POISON)
+                cx.decode_batch(gm, cont, cap, offs, lens, pb.d_sym, pb.d_counts, 2, out)
+                assert cx.last_decode_kernel() == kernel, cx.last_decode_kernel()
+                assert torch.equal(out, pb.d_buf), (what, kernel)
+                assert cx.decode_errors() == 0
+    finally:
+        dec.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rid,n_streams", [("byte-2", 31), ("byte-64-14bit", 40), ("byte-64-12bit", 40), ("word-8", 40), ("alias256-64", 40), ("r64-2", 40)])
+def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_streams):
+    """Fewer than 32 2-way byte streams, the 64-way byte rows, the 8-way word layout, the alias and the rans64 2-way rows take
+    the wave-per-stream kernels on the context with the option on, and code right."""
+    R, ctx, torch, _ = gpu
+    row = ROW[rid]
+    assert row["encode"] != KERNEL
+    b = Batch(R, ctx, torch, oracle, row, draw_lengths(n_streams, row["ways"], 29))
+    run_row(b, 4)  # (asserts the row's kernel names)
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_per_stream_models_keep_their_kernel_with_the_option_on(gpu, oracle):
+    """encode_batch_adaptive of 40 2-way byte streams, each with its own model, on the context with the option on: the wave
+    kernel with one model per stream, every stream against the oracle."""
+    from test_gpu_batch_models import ROW as MODEL_ROW
+    from test_gpu_batch_models import ModelBatch
+    from test_gpu_batch_models import run_row as run_model_row
+    R, ctx, torch, _ = gpu
+    row = MODEL_ROW["byte-2-12bit"]
+    assert row["encode"] != KERNEL
+    run_model_row(ModelBatch(R, ctx, torch, oracle, row, draw_lengths(40, 2, 37).clip(0, 4096)), 4)  # (asserts the row's kernel names)
+    assert ctx.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_options_are_independent(gpu, oracle):
+    """With RANS_AMD_OPT_BATCH_ENCODE_GROUPS and RANS_AMD_OPT_BATCH_ENCODE_PAIRS both on, nine 8-way word streams report
+    k_encode_batch_word_groups and forty 2-way byte streams the pair kernel; the decoder's option 7 alone leaves the encoder
+    on k_encode_batch<byte>."""
+    R, ctx, torch, off = gpu
+    ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 1)
+    try:
+        word = dict(ROW["word-8"], encode="k_encode_batch_word_groups")
+        run_row(Batch(R, ctx, torch, oracle, word, draw_lengths(9, 8, 43)), 4)
+        run_row(Batch(R, ctx, torch, oracle, EMAIN, draw_lengths(40, 2, 47)), 4)
+    finally:
+        ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 0)
+    off.set_option(OPT_BATCH_PAIRS, 1)
+    try:
+        assert DEC_PAIR_ROW["encode"] == WAVE
+        run_row(Batch(R, off, torch, oracle, DEC_PAIR_ROW, draw_lengths(40, 2, 47)), 4)
+    finally:
+        off.set_option(OPT_BATCH_PAIRS, 0)
+    assert ctx.decode_errors() == 0 and off.decode_errors() == 0
+
+
+@pytest.mark.gpu
+def test_option_takes_zero_or_one(gpu, oracle):
+    """Any other value is E_ARG and changes nothing; 0 restores the wave-per-stream kernel, 1 the pair kernel."""
+    R, ctx, torch, _ = gpu
+    b = Batch(R, ctx, torch, oracle, EMAIN, np.array([300] * 33, dtype=np.uint32))
+    for bad in (2, -1):
+        with pytest.raises(R.RansAmdError) as e:
+            ctx.set_option(OPT_BATCH_ENCODE_PAIRS, bad)
+        assert e.value.status == R.E_ARG
+    run_row(b, 4)
+    ctx.set_option(OPT_BATCH_ENCODE_PAIRS, 0)
+    try:
+        run_row(Batch(R, ctx, torch, oracle, ROW["byte-2"], b.counts), 4)
+    finally:
+        ctx.set_option(OPT_BATCH_ENCODE_PAIRS, 1)
+    run_row(b, 4)
+
+
+_GRAPH_SCRIPT = r"""
+import os, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import numpy as np, torch
+import bench, ryg_rans_amd as R
+from test_gpu_batch import draw_lengths, POISON
+from test_gpu_batch_encode_groups import stream_mask
+ctx = R.Context(0)
+ctx.set_option(R.OPT_BATCH_ENCODE_PAIRS, 1)
+counts = draw_lengths(3000, 2, 61)
+n = counts.size
+sym_offs, slot_offs = R.batch_layout(counts, R.FMT_BYTE, 2, 4)
+d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
+freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, 256), 1 << 14)
+gm = ctx.model(R.FMT_BYTE, freqs, 14)
+d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
+d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda(); d_slot = torch.from_numpy(slot_offs.astype(np.int64)).cuda()
+cap = int(slot_offs[-1])
+want, w_offs, w_lens = ctx.encode_batch(gm, d_syms, d_sym, d_counts, 2, d_slot)   # (outside the capture first)
+ctx.encode_status()
+assert ctx.last_encode_kernel()[0] == "k_encode_batch_byte_pairs", ctx.last_encode_kernel()
+back = torch.full_like(d_syms, POISON)
+ctx.decode_batch(gm, want, cap, w_offs, w_lens, d_sym, d_counts, 2, back)
+m = stream_mask(torch, cap, w_offs, w_lens, n)
+out = torch.full((cap,), POISON, dtype=torch.uint8, device="cuda")
+offs = torch.zeros(n, dtype=torch.int64, device="cuda"); lens = torch.zeros(n, dtype=torch.int32, device="cuda")
+s = torch.cuda.Stream()
+g = torch.cuda.CUDAGraph()
+with torch.cuda.stream(s):
+    with torch.cuda.graph(g, stream=s):
+        ctx.encode_batch(gm, d_syms, d_sym, d_counts, 2, d_slot, d_out=out, d_offsets=offs, d_lengths=lens, out_cap=cap)
+for _ in range(3):
+    out.fill_(POISON); offs.zero_(); lens.zero_()
+    g.replay()
+    torch.cuda.synchronize()
+    ctx.encode_status()
+    assert torch.equal(offs, w_offs[:n]) and torch.equal(lens, w_lens[:n]), "replay: index entries differ"
+    assert torch.equal(out[m], want[:cap][m]), "replay: stream bytes differ"
+assert ctx.last_encode_kernel()[0] == "k_encode_batch_byte_pairs"
+print("graph ok")
+"""
+
+
+@pytest.mark.gpu
+def test_pair_batch_encode_in_a_captured_graph(tmp_path):
+    """One captured encode_batch of 3000 2-way byte streams with the option on: one eager call first, then three replays into a
+    poison-refilled container, each equal to the eager result (stream bytes, offsets, lengths), in a child process under a
+    time limit of its own.  Graph replay needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set
+    below that the test does not apply."""
+    import subprocess
+    import sys
+    q = os.environ.get("GPU_MAX_HW_QUEUES")
+    if q is not None and int(q) < 4:
+        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
+    script = tmp_path / "graph_batch_encode_pairs.py"
+    script.write_text(_GRAPH_SCRIPT)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
