@@ -367,7 +367,14 @@ int rans_amd_encode_status(rans_amd_ctx *ctx, void *stream);
  * failed chunks and returns RANS_AMD_E_CORRUPT when it is non-zero.  Otherwise
  * the call is asynchronous; fetch the count later with rans_amd_decode_errors.
  * No kernel ever reads outside the 16-byte granules covering
- * [d_container, d_container + container_bytes). */
+ * [d_container, d_container + container_bytes).
+ * A failed chunk counts ONCE.  A chunk whose index entry is rejected before anything is read -- d_offsets[c] no multiple of
+ * the unit, d_lengths[c] < n_ways * state bytes, d_offsets[c] > container_bytes or d_lengths[c] > container_bytes -
+ * d_offsets[c] (the two compares cannot wrap) -- is SKIPPED: none of its bytes is read and none of its symbols is written,
+ * d_out keeps what it held there; the same holds for a chunk of rans_amd_decode_adaptive[_fmt] whose frequency row does not
+ * sum to 1 << scale_bits.  A chunk whose stream fails its check has been decoded: its symbols are written (they are what
+ * the reference's loops make of those bytes) and must not be used.  Every other chunk is decoded exactly, whatever its
+ * neighbours -- in the index, in the container or in the same wavefront -- held (tests/test_gpu_verdict.py). */
 int rans_amd_decode(rans_amd_ctx *ctx, const rans_amd_model *model, const void *d_container,
                     uint64_t container_bytes, const uint64_t *d_offsets, const uint32_t *d_lengths,
                     uint64_t n, uint32_t n_ways, uint32_t chunk_syms, void *d_out,

@@ -473,9 +473,13 @@ class Context:
             d_out = torch.empty(n, dtype=torch.uint8 if model.sym_bytes == 1 else torch.int16,
                                 device=d_container.device)
         bad = C.c_uint64(0)
-        _check(_lib.rans_amd_decode(self._h, model._h, d_container.data_ptr(), container_bytes, d_offsets.data_ptr(),
-                                    d_lengths.data_ptr(), n, n_ways, chunk_syms, d_out.data_ptr(),
-                                    C.byref(bad) if sync else None, _torch_stream()), "decode")
+        rc = _lib.rans_amd_decode(self._h, model._h, d_container.data_ptr(), container_bytes, d_offsets.data_ptr(),
+                                  d_lengths.data_ptr(), n, n_ways, chunk_syms, d_out.data_ptr(),
+                                  C.byref(bad) if sync else None, _torch_stream())
+        if rc != OK:  # (with sync a failed chunk raises E_CORRUPT whose `bad_chunks` is the count the call wrote to h_bad_chunks)
+            err = RansAmdError(rc, "decode", _lib.rans_amd_last_error().decode())
+            err.bad_chunks = int(bad.value)
+            raise err
         return d_out
 
     # -- ragged batches: many independent streams, each with its own symbol count
