@@ -134,8 +134,8 @@ struct rans_amd_ctx {
     uint32_t variant = 0;    // kVar* bits (rans_amd_ctx_set_option)
     bool unfused = false;    // RANS_AMD_OPT_FUSED_PLACEMENT = 0: k_encode + k_layout + k_compact
     bool scratch_ring = false; // RANS_AMD_OPT_ENC_SCRATCH_RING = 1
-    const char *last_kernel = "";
-    const char *last_enc_kernel = ""; // the coding kernel of the last encode call
+    KernelId last_kernel = KernelId::none;
+    KernelId last_enc_kernel = KernelId::none; // the coding kernel of the last encode call
     bool last_enc_fused = false;      // ... and whether it placed its chunks itself (no k_layout / k_compact)
     bool last_enc_slots = false;      // ... or left them in their slots (rans_amd_encode_slots)
     std::mutex mu;
@@ -361,7 +361,7 @@ int take_word64_counters(rans_amd_ctx *ctx, const CaptureScope &capture, hipStre
 }
 
 // launch_decode or launch_decode_batch (kernels.h)
-typedef hipError_t (*DecodeLauncher)(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **kernel_name);
+typedef hipError_t (*DecodeLauncher)(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // time (rans_amd_set_timing), launch, advance the counter ring
 int launch_decoder(rans_amd_ctx *ctx, const CaptureScope &capture, hipStream_t s, DecodeLauncher launch, int dec_format,
@@ -2215,13 +2215,13 @@ int rans_amd_last_kernel_ms(rans_amd_ctx *ctx, float *decode_ms, float *encode_m
     return RANS_AMD_OK;
 }
 
-const char *rans_amd_last_decode_kernel(rans_amd_ctx *ctx) { return ctx ? ctx->last_kernel : ""; }
+const char *rans_amd_last_decode_kernel(rans_amd_ctx *ctx) { return kernel_name(ctx ? ctx->last_kernel : KernelId::none); }
 
 const char *rans_amd_last_encode_kernel(rans_amd_ctx *ctx, int *fused_placement)
 {
     if (fused_placement)
         *fused_placement = ctx && ctx->last_enc_slots ? 2 : (ctx && ctx->last_enc_fused ? 1 : 0);
-    return ctx ? ctx->last_enc_kernel : "";
+    return kernel_name(ctx ? ctx->last_enc_kernel : KernelId::none);
 }
 
 int rans_amd_launch_spans(rans_amd_ctx *ctx, uint32_t count, double *span_ms, void *stream)

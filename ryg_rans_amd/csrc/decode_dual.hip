@@ -301,7 +301,7 @@ __global__ void __launch_bounds__(kDecBlockThreads, 4) k_decode_dual(const DecPa
 }
 
 template <int FMT, bool SYM16>
-hipError_t launch_dual_t(const DecParams &p, int num_cus, hipStream_t stream, const char **name, const char *kname)
+hipError_t launch_dual_t(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name, KernelId id)
 {
     const uint32_t waves = kDecBlockThreads / 64;
     const uint32_t t0 = (p.table0_bytes + 15u) & ~15u, t1 = (p.table1_bytes + 15u) & ~15u;
@@ -317,7 +317,7 @@ hipError_t launch_dual_t(const DecParams &p, int num_cus, hipStream_t stream, co
     const uint64_t cap = (uint64_t)num_cus; // one block per CU
     const uint32_t grid = (uint32_t)(want < cap ? (want ? want : 1) : cap);
     if (name)
-        *name = kname;
+        *name = id;
     RANS_LAUNCH(kern, dim3(grid), dim3(kDecBlockThreads), lds, stream, p);
     return hipGetLastError();
 }
@@ -332,16 +332,16 @@ bool decode_dual_fits(uint32_t table0_bytes, uint32_t table1_bytes)
 
 // format: kKernelFormatAlias2 / kKernelFormatAlias2W (tables in the FMT_ALIAS2 form).
 // The caller has checked n_ways == 64 and the alignment of the output.
-hipError_t launch_decode_dual(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_decode_dual(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     const bool sym16 = p.sym_bytes == 2;
     switch (format) {
     case FMT_ALIAS2:
-        return sym16 ? launch_dual_t<FMT_ALIAS2, true>(p, num_cus, stream, name, "k_decode_dual<alias>")
-                     : launch_dual_t<FMT_ALIAS2, false>(p, num_cus, stream, name, "k_decode_dual<alias>");
+        return sym16 ? launch_dual_t<FMT_ALIAS2, true>(p, num_cus, stream, name, KernelId::decode_dual_alias)
+                     : launch_dual_t<FMT_ALIAS2, false>(p, num_cus, stream, name, KernelId::decode_dual_alias);
     case FMT_ALIAS2W:
-        return sym16 ? launch_dual_t<FMT_ALIAS2W, true>(p, num_cus, stream, name, "k_decode_dual<alias>")
-                     : launch_dual_t<FMT_ALIAS2W, false>(p, num_cus, stream, name, "k_decode_dual<alias>");
+        return sym16 ? launch_dual_t<FMT_ALIAS2W, true>(p, num_cus, stream, name, KernelId::decode_dual_alias)
+                     : launch_dual_t<FMT_ALIAS2W, false>(p, num_cus, stream, name, KernelId::decode_dual_alias);
     default:
         return hipErrorInvalidValue;
     }

@@ -942,11 +942,11 @@ bool decode_word_groups_applicable(const DecParams &p)
            ((p.table0_bytes + 15u) & ~15u) % kGrpRing == 0;
 }
 
-hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     const size_t lds = ((p.table0_bytes + 15u) & ~15u) + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
     if (name)
-        *name = "k_decode_word_groups";
+        *name = KernelId::decode_word_groups;
     return launch_group_kernel<k_decode_word_groups>((p.nchunks + 7u) / 8u, lds, kGrpLdsCap, num_cus, stream, p);
 }
 
@@ -958,11 +958,11 @@ bool decode_batch_word_groups_applicable(const DecParams &p)
            ((p.table0_bytes + 15u) & ~15u) % kGrpRing == 0;
 }
 
-hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **group_batch_kernel)
+hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     const size_t lds = ((p.table0_bytes + 15u) & ~15u) + (size_t)(kGrpThreads / 64) * kGrpWaveLds;
-    if (group_batch_kernel)
-        *group_batch_kernel = "k_decode_batch_word_groups";
+    if (name)
+        *name = KernelId::decode_batch_word_groups;
     return launch_group_kernel<k_decode_batch_word_groups>((p.nchunks + 7u) / 8u, lds, kGrpLdsCap, num_cus, stream, p); // one octet per wave
 }
 
@@ -978,10 +978,10 @@ bool decode_byte_pairs_applicable(const DecParams &p)
            pair_lds(p) <= kGrpLdsCap;
 }
 
-hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (name)
-        *name = "k_decode_byte_pairs";
+        *name = KernelId::decode_byte_pairs;
     return launch_group_kernel<k_decode_byte_pairs>((p.nchunks + 31u) / 32u, pair_lds(p), kGrpLdsCap, num_cus, stream, p);
 }
 
@@ -993,10 +993,10 @@ bool decode_batch_byte_pairs_applicable(const DecParams &p)
            !p.trace && pair_lds(p) <= kGrpLdsCap;
 }
 
-hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **pair_batch_kernel)
+hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
-    if (pair_batch_kernel)
-        *pair_batch_kernel = "k_decode_batch_byte_pairs";
+    if (name)
+        *name = KernelId::decode_batch_byte_pairs;
     return launch_group_kernel<k_decode_batch_byte_pairs>((p.nchunks + 31u) / 32u, pair_lds(p), kGrpLdsCap, num_cus, stream, p); // one wave-load per wave
 }
 

@@ -992,7 +992,7 @@ __global__ void __launch_bounds__(256) k_decode_lanes(const DecParams p)
 }
 
 template <int FMT, int NW>
-hipError_t launch_decode_lanes_t(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_decode_lanes_t(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     const uint32_t t0 = (p.table0_bytes + 15u) & ~15u, t1 = (p.table1_bytes + 15u) & ~15u;
     // staged kernel: the tables are shared by the block, every wave adds kLaneWaveLds of rings, so one
@@ -1034,7 +1034,7 @@ hipError_t launch_decode_lanes_t(const DecParams &p, int num_cus, hipStream_t st
                 q.table1_bytes = 0;
             }
             if (name)
-                *name = packed ? "k_decode_lanes_r64x2<packed slots>" : "k_decode_lanes_r64x2";
+                *name = packed ? KernelId::decode_lanes_r64x2_packed : KernelId::decode_lanes_r64x2;
             if (hipError_t e = launch_lanes(kern3, lds_ok3[packed], 160 * 1024, lanes_grid(batches3, sw3, num_cus), 64 * sw3,
                                             table_lds3 + (size_t)sw3 * kR64WaveLds, stream, q);
                 e != hipSuccess)
@@ -1056,7 +1056,7 @@ hipError_t launch_decode_lanes_t(const DecParams &p, int num_cus, hipStream_t st
     static std::atomic<uint64_t> lds_ok[2] = {{0}, {0}}; // per kernel generation, one bit per device
     if (staged) {
         if (name)
-            *name = "k_decode_lanes_staged";
+            *name = KernelId::decode_lanes_staged;
         return launch_lanes(k_decode_lanes_staged<FMT, NW>, lds_ok[1], 160 * 1024, lanes_grid(batches, sw, num_cus), 64 * sw,
                             table_lds + (size_t)sw * kLaneWaveLds, stream, p);
     }
@@ -1066,12 +1066,12 @@ hipError_t launch_decode_lanes_t(const DecParams &p, int num_cus, hipStream_t st
     const size_t lds_room = table_lds ? (160 * 1024) / table_lds : 8;
     const uint64_t cap = (uint64_t)num_cus * (lds_room >= 8 ? 8 : (lds_room >= 1 ? lds_room : 1));
     if (name)
-        *name = "k_decode_lanes";
+        *name = KernelId::decode_lanes;
     return launch_lanes(k_decode_lanes<FMT, NW>, lds_ok[0], 160 * 1024, (uint32_t)(want < cap ? want : cap), 256, table_lds, stream,
                         p);
 }
 
-template <int FMT> hipError_t launch_decode_lanes_f(const DecParams &p, int num_cus, hipStream_t s, const char **name)
+template <int FMT> hipError_t launch_decode_lanes_f(const DecParams &p, int num_cus, hipStream_t s, KernelId *name)
 {
     switch (p.n_ways) {
     case 1: return launch_decode_lanes_t<FMT, 1>(p, num_cus, s, name);
@@ -1084,7 +1084,7 @@ template <int FMT> hipError_t launch_decode_lanes_f(const DecParams &p, int num_
 
 } // namespace
 
-hipError_t launch_decode_lanes(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_decode_lanes(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     switch (format) {
     case FMT_WORD: return launch_decode_lanes_f<FMT_WORD>(p, num_cus, stream, name);

@@ -748,7 +748,7 @@ template <int FMT, int K, int OUT, bool RAGGED> hipError_t launch_decode_t(const
 }
 
 // `name`: the uniform launcher's; the ragged launchers report names of their own and pass nullptr
-template <int FMT, bool RAGGED> hipError_t launch_decode_f(const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+template <int FMT, bool RAGGED> hipError_t launch_decode_f(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     const bool aligned = decode_out_aligned(FMT, reinterpret_cast<uintptr_t>(p.out), p.chunk_syms);
     const DecodeShape s = decode_shape(FMT, p.n_ways, p.sym_bytes, aligned, RAGGED);
@@ -758,11 +758,11 @@ template <int FMT, bool RAGGED> hipError_t launch_decode_f(const DecParams &p, i
     if (kIsAdaptive<FMT> && (!p.chunk_freqs || p.scale_bits > kAdaptMaxScaleBits || p.scale_bits < 8 || (FMT == FMT_WORDA && p.scale_bits != 12)))
         return hipErrorInvalidValue;
     if (name)
-        *name = s.word64 ? "k_decode_word64"
-                : FMT == FMT_WORD ? "k_decode<word>" : FMT == FMT_BYTE ? "k_decode<byte>" : FMT == FMT_BYTEF ? "k_decode<byte, slot records>"
-                : FMT == FMT_R64 ? "k_decode<r64>" : FMT == FMT_R64S ? "k_decode<r64 search>"
-                : FMT == FMT_WORD16 ? "k_decode<word, u16 symbols>"
-                : FMT == FMT_BYTEA ? "k_decode<byte, per-chunk models>" : FMT == FMT_WORDA ? "k_decode<word, per-chunk models>" : "k_decode<alias>";
+        *name = s.word64 ? KernelId::decode_word64
+                : FMT == FMT_WORD ? KernelId::decode_word : FMT == FMT_BYTE ? KernelId::decode_byte : FMT == FMT_BYTEF ? KernelId::decode_byte_slot_records
+                : FMT == FMT_R64 ? KernelId::decode_r64 : FMT == FMT_R64S ? KernelId::decode_r64_search
+                : FMT == FMT_WORD16 ? KernelId::decode_word_u16
+                : FMT == FMT_BYTEA ? KernelId::decode_byte_chunk_models : FMT == FMT_WORDA ? KernelId::decode_word_chunk_models : KernelId::decode_alias;
     return with_states_per_lane(s.K, [&](auto k) {
         constexpr int K = decltype(k)::value;
         switch (s.out) {
@@ -773,7 +773,7 @@ template <int FMT, bool RAGGED> hipError_t launch_decode_f(const DecParams &p, i
     });
 }
 
-template <bool RAGGED> hipError_t launch_decode_fmt(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+template <bool RAGGED> hipError_t launch_decode_fmt(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     switch (format) {
     case FMT_WORD: return launch_decode_f<FMT_WORD, RAGGED>(p, num_cus, stream, name);
@@ -791,44 +791,44 @@ template <bool RAGGED> hipError_t launch_decode_fmt(int format, const DecParams 
 
 } // namespace
 
-hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!p.sym_offsets || !p.sym_counts)
         return hipErrorInvalidValue;
     const bool word64 = format == FMT_WORD && p.n_ways == 64 && p.sym_bytes == 1;
-    if (batch_kernel)
-        *batch_kernel = word64                ? "k_decode_batch_word64"
-                        : format == FMT_WORD  ? "k_decode_batch<word>"
-                        : format == FMT_BYTE  ? "k_decode_batch<byte>"
-                        : format == FMT_BYTEF ? "k_decode_batch<byte, slot records>"
-                        : format == FMT_R64   ? "k_decode_batch<r64>"
-                        : format == FMT_R64S  ? "k_decode_batch<r64 search>"
-                        : format == FMT_WORD16 ? "k_decode_batch<word, u16 symbols>"
-                                              : "k_decode_batch<alias>";
+    if (name)
+        *name = word64                 ? KernelId::decode_batch_word64
+                : format == FMT_WORD   ? KernelId::decode_batch_word
+                : format == FMT_BYTE   ? KernelId::decode_batch_byte
+                : format == FMT_BYTEF  ? KernelId::decode_batch_byte_slot_records
+                : format == FMT_R64    ? KernelId::decode_batch_r64
+                : format == FMT_R64S   ? KernelId::decode_batch_r64_search
+                : format == FMT_WORD16 ? KernelId::decode_batch_word_u16
+                                       : KernelId::decode_batch_alias;
     if (format == FMT_BYTEA || format == FMT_WORDA) // (one model per stream: launch_decode_batch_models_wave)
         return hipErrorInvalidValue;
     return launch_decode_fmt<true>(format, p, num_cus, stream, nullptr);
 }
 
 // ... with one model per stream (rans_amd_decode_batch_adaptive): the uniform adaptive decoder's four-wave workgroups
-hipError_t launch_decode_batch_models_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel)
+hipError_t launch_decode_batch_models_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!p.sym_offsets || !p.sym_counts || p.sym_bytes != 1)
         return hipErrorInvalidValue;
     switch (format) {
     case FMT_WORDA:
-        if (models_batch_kernel)
-            *models_batch_kernel = "k_decode_batch_models<word>";
+        if (name)
+            *name = KernelId::decode_batch_models_word;
         return launch_decode_f<FMT_WORDA, true>(p, num_cus, stream, nullptr);
     case FMT_BYTEA:
-        if (models_batch_kernel)
-            *models_batch_kernel = "k_decode_batch_models<byte>";
+        if (name)
+            *name = KernelId::decode_batch_models_byte;
         return launch_decode_f<FMT_BYTEA, true>(p, num_cus, stream, nullptr);
     default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_decode_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_decode_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     return launch_decode_fmt<false>(format, p, num_cus, stream, name);
 }

@@ -14,20 +14,20 @@ bool ways_supported(int format, uint32_t n_ways)
 
 // narrow interleaves with enough chunks to fill wavefronts run one chunk per lane; everything else
 // one chunk per wave
-hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **kernel_name)
+hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (format == kKernelFormatAlias2 || format == kKernelFormatAlias2W) // (api.cpp has checked the shape)
-        return launch_decode_dual(format, p, num_cus, stream, kernel_name);
+        return launch_decode_dual(format, p, num_cus, stream, name);
     // the reference's 8-way word layout, u8 symbols, from eight full chunks on: eight chunks per wave (decode_groups.hip)
     if (format == (int)RANS_AMD_FMT_WORD && decode_word_groups_applicable(p))
-        return launch_decode_word_groups(p, num_cus, stream, kernel_name);
+        return launch_decode_word_groups(p, num_cus, stream, name);
     if (format == (int)RANS_AMD_FMT_BYTE && decode_byte_pairs_applicable(p))
-        return launch_decode_byte_pairs(p, num_cus, stream, kernel_name);
+        return launch_decode_byte_pairs(p, num_cus, stream, name);
     if (format != kKernelFormatR64Search && format != kKernelFormatWord16 && format != kKernelFormatByteAdaptive &&
         format != kKernelFormatWordAdaptive &&
         format != kKernelFormatByteFused && lanes_applicable(p.nchunks, p.n_ways))
-        return launch_decode_lanes(format, p, num_cus, stream, kernel_name);
-    return launch_decode_wave(format, p, num_cus, stream, kernel_name);
+        return launch_decode_lanes(format, p, num_cus, stream, name);
+    return launch_decode_wave(format, p, num_cus, stream, name);
 }
 
 // ragged batches: the wave-per-stream kernels, whatever the interleave -- unless the context asked for eight streams per wave
@@ -37,27 +37,27 @@ hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_
 // 2-way byte layout over u8 symbols at scale_bits 8..16, from 32 streams on: the ragged kernels of decode_groups.hip and
 // encode_groups.hip.  Every other shape takes the wave kernels under those options as well (the ragged forms of the lane
 // kernels are later work).
-hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if ((p.variant & kVarBatchGroups) && format == (int)RANS_AMD_FMT_WORD && decode_batch_word_groups_applicable(p))
-        return launch_decode_batch_word_groups(p, num_cus, stream, batch_kernel);
+        return launch_decode_batch_word_groups(p, num_cus, stream, name);
     if ((p.variant & kVarBatchPairs) && format == (int)RANS_AMD_FMT_BYTE && decode_batch_byte_pairs_applicable(p))
-        return launch_decode_batch_byte_pairs(p, num_cus, stream, batch_kernel);
-    return launch_decode_batch_wave(format, p, num_cus, stream, batch_kernel);
+        return launch_decode_batch_byte_pairs(p, num_cus, stream, name);
+    return launch_decode_batch_wave(format, p, num_cus, stream, name);
 }
 
-hipError_t launch_decode_batch_models(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel)
+hipError_t launch_decode_batch_models(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
-    return launch_decode_batch_models_wave(format, p, num_cus, stream, models_batch_kernel);
+    return launch_decode_batch_models_wave(format, p, num_cus, stream, name);
 }
 
-hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if ((p.variant & kVarBatchEncGroups) && format == (int)RANS_AMD_FMT_WORD && encode_batch_word_groups_applicable(p))
-        return launch_encode_batch_word_groups(p, num_cus, stream, batch_kernel);
+        return launch_encode_batch_word_groups(p, num_cus, stream, name);
     if ((p.variant & kVarBatchEncPairs) && format == (int)RANS_AMD_FMT_BYTE && encode_batch_byte_pairs_applicable(p))
-        return launch_encode_batch_byte_pairs(p, num_cus, stream, batch_kernel);
-    return launch_encode_batch_wave(format == kKernelFormatWord16 ? (int)RANS_AMD_FMT_WORD : format, p, num_cus, stream, batch_kernel);
+        return launch_encode_batch_byte_pairs(p, num_cus, stream, name);
+    return launch_encode_batch_wave(format == kKernelFormatWord16 ? (int)RANS_AMD_FMT_WORD : format, p, num_cus, stream, name);
 }
 
 // Fused placement needs a mailbox for the block's coders and copier (encode_wave.hip launch_encode_t computes the same
@@ -96,7 +96,7 @@ bool encode_lanes_can_fuse(int format, const EncParams &p, int num_cus)
     return encode_uses_lanes(format, p.nchunks, p.n_ways) && encode_lanes_fused(p, num_cus);
 }
 
-hipError_t launch_encode(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_encode(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     // (the lane encoders know the public formats: a narrow alias interleave gathers alias_remap from L2)
     if (format == kKernelFormatByteAdaptive) // one model per chunk: the wave encoder builds them, whatever the interleave

@@ -577,31 +577,31 @@ template <int FMT, bool RAGGED> hipError_t launch_f(const AdaptEncParams &p, int
 
 } // namespace
 
-hipError_t launch_encode_batch_models(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel)
+hipError_t launch_encode_batch_models(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!p.rcp || !p.claims || !p.status || !p.sym_offsets || !p.sym_counts || p.scale_bits < 8 || p.scale_bits > kAdaptMaxScaleBits ||
         (format == FMT_WORD && p.scale_bits != 12))
         return hipErrorInvalidValue;
     switch (format) {
     case FMT_WORD:
-        if (models_batch_kernel)
-            *models_batch_kernel = "k_encode_batch_models<word>";
+        if (name)
+            *name = KernelId::encode_batch_models_word;
         return launch_f<FMT_WORD, true>(p, num_cus, stream);
     case FMT_BYTE:
-        if (models_batch_kernel)
-            *models_batch_kernel = "k_encode_batch_models<byte>";
+        if (name)
+            *name = KernelId::encode_batch_models_byte;
         return launch_f<FMT_BYTE, true>(p, num_cus, stream);
     default: return hipErrorInvalidValue;
     }
 }
 
-hipError_t launch_encode_adaptive(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_encode_adaptive(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!p.rcp || !p.claims || !p.status || p.scale_bits < 8 || p.scale_bits > kAdaptMaxScaleBits ||
         (format == FMT_WORD && p.scale_bits != 12))
         return hipErrorInvalidValue;
     if (name)
-        *name = format == FMT_WORD ? "k_encode_adaptive<word>" : "k_encode_adaptive<byte>";
+        *name = format == FMT_WORD ? KernelId::encode_adaptive_word : KernelId::encode_adaptive_byte;
     switch (format) {
     case FMT_WORD: return launch_f<FMT_WORD, false>(p, num_cus, stream);
     case FMT_BYTE: return launch_f<FMT_BYTE, false>(p, num_cus, stream);

@@ -772,12 +772,12 @@ static hipError_t launch_encode_groups(const EncGroupLaunch (&launches)[2][2], c
     return launches[p.word_small != 0][p.dense256 == 0]((p.nchunks + 7u) / 8u, lds, 0, num_cus, stream, p);
 }
 
-hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!p.word_enc_recs || (reinterpret_cast<uintptr_t>(p.scratch) & 15u) != 0)
         return hipErrorInvalidValue;
     if (name)
-        *name = "k_encode_word_groups";
+        *name = KernelId::encode_word_groups;
     static const EncGroupLaunch launches[2][2] = {
         {launch_group_kernel<k_encode_word_groups<false, false>, EncParams>, launch_group_kernel<k_encode_word_groups<false, true>, EncParams>},
         {launch_group_kernel<k_encode_word_groups<true, false>, EncParams>, launch_group_kernel<k_encode_word_groups<true, true>, EncParams>}};
@@ -792,12 +792,12 @@ bool encode_batch_word_groups_applicable(const EncParams &p)
            (reinterpret_cast<uintptr_t>(p.scratch) & 15u) == 0;
 }
 
-hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **group_batch_enc_kernel)
+hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!encode_batch_word_groups_applicable(p) || !p.sym_offsets || !p.sym_counts || !p.slot_offsets || !p.lengths || !p.offsets || !p.flags)
         return hipErrorInvalidValue;
-    if (group_batch_enc_kernel)
-        *group_batch_enc_kernel = "k_encode_batch_word_groups";
+    if (name)
+        *name = KernelId::encode_batch_word_groups;
     static const EncGroupLaunch launches[2][2] = {
         {launch_group_kernel<k_encode_batch_word_groups<false, false>, EncParams>, launch_group_kernel<k_encode_batch_word_groups<false, true>, EncParams>},
         {launch_group_kernel<k_encode_batch_word_groups<true, false>, EncParams>, launch_group_kernel<k_encode_batch_word_groups<true, true>, EncParams>}};
@@ -814,13 +814,13 @@ bool encode_batch_byte_pairs_applicable(const EncParams &p)
 
 // one wave-load per wave; 4 KiB of records and sixteen waves of ring rows: inside the default dynamic-LDS limit, two blocks
 // per CU whatever the model's scale_bits
-hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, const char **pair_batch_enc_kernel)
+hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!encode_batch_byte_pairs_applicable(p) || !p.enc_recs || !p.sym_offsets || !p.sym_counts || !p.slot_offsets || !p.lengths || !p.offsets ||
         !p.flags)
         return hipErrorInvalidValue;
-    if (pair_batch_enc_kernel)
-        *pair_batch_enc_kernel = "k_encode_batch_byte_pairs";
+    if (name)
+        *name = KernelId::encode_batch_byte_pairs;
     const size_t lds = kEncPairTable + (size_t)(kGrpThreads / 64) * kPairWaveLds;
     const uint64_t loads = (p.nchunks + 31u) / 32u;
     return p.dense256 ? launch_group_kernel<k_encode_batch_byte_pairs<false>, EncParams>(loads, lds, 0, num_cus, stream, p)

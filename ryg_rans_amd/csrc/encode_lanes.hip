@@ -1015,7 +1015,7 @@ static uint64_t encode_lanes_min_batches(int format, const EncParams &p, int num
     return encode_lanes_r64x2_shape(format, p, num_cus) && !p.status ? 1 : 6;
 }
 
-template <int FMT, int NW> hipError_t launch_encode_lanes_t(const EncParams &p_in, int num_cus, hipStream_t stream, const char **name)
+template <int FMT, int NW> hipError_t launch_encode_lanes_t(const EncParams &p_in, int num_cus, hipStream_t stream, KernelId *name)
 {
     EncParams p = p_in;
     const size_t table_lds = (size_t)p.nsyms * sizeof(EncRec);
@@ -1052,7 +1052,7 @@ template <int FMT, int NW> hipError_t launch_encode_lanes_t(const EncParams &p_i
                     waves3 += kLaneCopiers;
                 }
                 if (name)
-                    *name = "k_encode_lanes_r64x2";
+                    *name = KernelId::encode_lanes_r64x2;
                 if (hipError_t e = launch_lanes(kern3, lds_ok3[p.dense256 ? 0 : 1], 160 * 1024,
                                                 lanes_grid(full_batches, sw3, num_cus), 64 * waves3, lds3, stream, q);
                     e != hipSuccess)
@@ -1076,7 +1076,7 @@ template <int FMT, int NW> hipError_t launch_encode_lanes_t(const EncParams &p_i
             waves += kLaneCopiers;
         }
         if (name && p.batch_begin == 0)
-            *name = "k_encode_lanes_staged";
+            *name = KernelId::encode_lanes_staged;
         return launch_lanes(k_encode_lanes_staged<FMT, NW>, lds_ok, 160 * 1024, lanes_grid(batches, sw, num_cus), 64 * waves, lds,
                             stream, p);
     }
@@ -1084,12 +1084,12 @@ template <int FMT, int NW> hipError_t launch_encode_lanes_t(const EncParams &p_i
     const uint64_t want = (p.nchunks + 255) / 256;
     const uint64_t cap = (uint64_t)num_cus * 8;
     if (name)
-        *name = "k_encode_lanes16";
+        *name = KernelId::encode_lanes16;
     return launch_lanes(k_encode_lanes16<FMT, NW>, lds_ok, 128 * 1024, (uint32_t)(want < cap ? want : cap), 256, table_lds, stream,
                         p);
 }
 
-template <int FMT> hipError_t launch_encode_lanes_f(const EncParams &p, int num_cus, hipStream_t s, const char **name)
+template <int FMT> hipError_t launch_encode_lanes_f(const EncParams &p, int num_cus, hipStream_t s, KernelId *name)
 {
     switch (p.n_ways) {
     case 1: return launch_encode_lanes_t<FMT, 1>(p, num_cus, s, name);
@@ -1114,7 +1114,7 @@ bool encode_lanes_sized_ok(int format, const EncParams &p, int num_cus)
     return encode_lanes_staged_waves(p, num_cus, encode_lanes_min_batches(format, p, num_cus)) >= 1;
 }
 
-hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     switch (format) {
     case FMT_WORD: return launch_encode_lanes_f<FMT_WORD>(p, num_cus, stream, name);

@@ -768,15 +768,15 @@ template <int FMT> hipError_t launch_encode_t(const EncParams &p, int num_cus, h
 
 } // namespace
 
-hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **name)
+hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (name)
-        *name = format == FMT_WORD    ? "k_encode<word>"
-                : format == FMT_BYTE  ? (p.chunk_freqs ? "k_encode<byte, per-chunk models>" : "k_encode<byte>")
-                : format == FMT_WORDA ? "k_encode<word, per-chunk models>"
-                : format == FMT_R64   ? "k_encode<r64>"
-                : format == FMT_R64S  ? "k_encode<r64 full-width>"
-                                      : "k_encode<alias, LDS remap>";
+        *name = format == FMT_WORD    ? KernelId::encode_word
+                : format == FMT_BYTE  ? (p.chunk_freqs ? KernelId::encode_byte_chunk_models : KernelId::encode_byte)
+                : format == FMT_WORDA ? KernelId::encode_word_chunk_models
+                : format == FMT_R64   ? KernelId::encode_r64
+                : format == FMT_R64S  ? KernelId::encode_r64_full_width
+                                      : KernelId::encode_alias_lds_remap;
     switch (format) {
     case FMT_WORD: return launch_encode_t<FMT_WORD>(p, num_cus, stream);
     case FMT_WORDA: return p.chunk_freqs ? launch_encode_t<FMT_WORDA>(p, num_cus, stream) : hipErrorInvalidValue;
@@ -791,17 +791,17 @@ hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipSt
 }
 
 // ragged batches (k_encode's MODE 4): the same kernels under names of their own
-hipError_t launch_encode_batch_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel)
+hipError_t launch_encode_batch_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (!p.slot_offsets || !p.sym_offsets || !p.sym_counts || !p.slot_layout || !p.claims || p.status || p.chunk_freqs ||
         format == FMT_WORDA)
         return hipErrorInvalidValue;
-    if (batch_kernel)
-        *batch_kernel = format == FMT_WORD   ? "k_encode_batch<word>"
-                        : format == FMT_BYTE ? "k_encode_batch<byte>"
-                        : format == FMT_R64  ? "k_encode_batch<r64>"
-                        : format == FMT_R64S ? "k_encode_batch<r64 full-width>"
-                                             : "k_encode_batch<alias, LDS remap>";
+    if (name)
+        *name = format == FMT_WORD   ? KernelId::encode_batch_word
+                : format == FMT_BYTE ? KernelId::encode_batch_byte
+                : format == FMT_R64  ? KernelId::encode_batch_r64
+                : format == FMT_R64S ? KernelId::encode_batch_r64_full_width
+                                     : KernelId::encode_batch_alias_lds_remap;
     return launch_encode_wave(format, p, num_cus, stream, nullptr);
 }
 

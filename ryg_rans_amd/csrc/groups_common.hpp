@@ -509,8 +509,7 @@ __device__ __forceinline__ void fetch_stream_entry(const DecParams &p, const uin
 // ---- host side -----------------------------------------------------------------------------------------------------
 // The launch of a group kernel, one instantiation per kernel: `units` of work (octets or wave-loads), one per wave, in blocks of
 // kGrpThreads.  lds_cap: what the kernel's dynamic-LDS limit is raised to, and then a CU takes two blocks only where two fit
-// under it; 0: the kernel stays within the default limit, two blocks per CU (the encoders).  The launchers report the
-// kernel's name themselves (`*name = "...";` in the .hip files: the tests' completeness checks read those statements).
+// under it; 0: the kernel stays within the default limit, two blocks per CU (the encoders).
 template <auto KERN, class Params>
 hipError_t launch_group_kernel(uint64_t units, size_t lds, uint32_t lds_cap, int num_cus, hipStream_t stream, const Params &p)
 {

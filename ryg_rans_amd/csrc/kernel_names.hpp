@@ -1,0 +1,106 @@
+// kernel_names.hpp -- the registry of the kernels a launcher can report (rans_amd_last_decode_kernel /
+// rans_amd_last_encode_kernel).  Host-only and free of HIP: tests/kernel_names_driver.cpp prints it with g++.
+//
+// One row per kernel: identifier, the string the public getters return, family.  The launchers report a KernelId, so a name
+// that is not in this table does not compile; the tests hold every row of a family to a row of expectations
+// (tests/_kernel_rows.py).  The families:
+//   uniform                   uniform chunks (rans_amd_decode / _encode* / _adaptive*)
+//   batch                     ragged batches, one stream per wave
+//   batch_models              ... with one model per stream
+//   batch_word_groups_decode  ragged 8-way word streams, eight per wave, decoder (RANS_AMD_OPT_BATCH_GROUPS)
+//   batch_word_groups_encode  ... encoder (RANS_AMD_OPT_BATCH_ENCODE_GROUPS)
+//   batch_byte_pairs_decode   ragged 2-way byte streams, 32 per wave, decoder (RANS_AMD_OPT_BATCH_PAIRS)
+//   batch_byte_pairs_encode   ... encoder (RANS_AMD_OPT_BATCH_ENCODE_PAIRS)
+#pragma once
+
+namespace rans_amd {
+
+#define RANS_AMD_KERNEL_NAMES(X)                                                                  \
+    X(decode_word64, "k_decode_word64", uniform)                                                  \
+    X(decode_word, "k_decode<word>", uniform)                                                     \
+    X(decode_word_u16, "k_decode<word, u16 symbols>", uniform)                                    \
+    X(decode_word_chunk_models, "k_decode<word, per-chunk models>", uniform)                      \
+    X(decode_byte, "k_decode<byte>", uniform)                                                     \
+    X(decode_byte_slot_records, "k_decode<byte, slot records>", uniform)                          \
+    X(decode_byte_chunk_models, "k_decode<byte, per-chunk models>", uniform)                      \
+    X(decode_r64, "k_decode<r64>", uniform)                                                       \
+    X(decode_r64_search, "k_decode<r64 search>", uniform)                                         \
+    X(decode_alias, "k_decode<alias>", uniform)                                                   \
+    X(decode_dual_alias, "k_decode_dual<alias>", uniform)                                         \
+    X(decode_word_groups, "k_decode_word_groups", uniform)                                        \
+    X(decode_byte_pairs, "k_decode_byte_pairs", uniform)                                          \
+    X(decode_lanes, "k_decode_lanes", uniform)                                                    \
+    X(decode_lanes_staged, "k_decode_lanes_staged", uniform)                                      \
+    X(decode_lanes_r64x2, "k_decode_lanes_r64x2", uniform)                                        \
+    X(decode_lanes_r64x2_packed, "k_decode_lanes_r64x2<packed slots>", uniform)                   \
+    X(encode_word, "k_encode<word>", uniform)                                                     \
+    X(encode_word_chunk_models, "k_encode<word, per-chunk models>", uniform)                      \
+    X(encode_byte, "k_encode<byte>", uniform)                                                     \
+    X(encode_byte_chunk_models, "k_encode<byte, per-chunk models>", uniform)                      \
+    X(encode_r64, "k_encode<r64>", uniform)                                                       \
+    X(encode_r64_full_width, "k_encode<r64 full-width>", uniform)                                 \
+    X(encode_alias_lds_remap, "k_encode<alias, LDS remap>", uniform)                              \
+    X(encode_adaptive_word, "k_encode_adaptive<word>", uniform)                                   \
+    X(encode_adaptive_byte, "k_encode_adaptive<byte>", uniform)                                   \
+    X(encode_word_groups, "k_encode_word_groups", uniform)                                        \
+    X(encode_lanes16, "k_encode_lanes16", uniform)                                                \
+    X(encode_lanes_staged, "k_encode_lanes_staged", uniform)                                      \
+    X(encode_lanes_r64x2, "k_encode_lanes_r64x2", uniform)                                        \
+    X(decode_batch_word64, "k_decode_batch_word64", batch)                                        \
+    X(decode_batch_word, "k_decode_batch<word>", batch)                                           \
+    X(decode_batch_word_u16, "k_decode_batch<word, u16 symbols>", batch)                          \
+    X(decode_batch_byte, "k_decode_batch<byte>", batch)                                           \
+    X(decode_batch_byte_slot_records, "k_decode_batch<byte, slot records>", batch)                \
+    X(decode_batch_r64, "k_decode_batch<r64>", batch)                                             \
+    X(decode_batch_r64_search, "k_decode_batch<r64 search>", batch)                               \
+    X(decode_batch_alias, "k_decode_batch<alias>", batch)                                         \
+    X(encode_batch_word, "k_encode_batch<word>", batch)                                           \
+    X(encode_batch_byte, "k_encode_batch<byte>", batch)                                           \
+    X(encode_batch_r64, "k_encode_batch<r64>", batch)                                             \
+    X(encode_batch_r64_full_width, "k_encode_batch<r64 full-width>", batch)                       \
+    X(encode_batch_alias_lds_remap, "k_encode_batch<alias, LDS remap>", batch)                    \
+    X(decode_batch_models_word, "k_decode_batch_models<word>", batch_models)                      \
+    X(decode_batch_models_byte, "k_decode_batch_models<byte>", batch_models)                      \
+    X(encode_batch_models_word, "k_encode_batch_models<word>", batch_models)                      \
+    X(encode_batch_models_byte, "k_encode_batch_models<byte>", batch_models)                      \
+    X(decode_batch_word_groups, "k_decode_batch_word_groups", batch_word_groups_decode)           \
+    X(encode_batch_word_groups, "k_encode_batch_word_groups", batch_word_groups_encode)           \
+    X(decode_batch_byte_pairs, "k_decode_batch_byte_pairs", batch_byte_pairs_decode)              \
+    X(encode_batch_byte_pairs, "k_encode_batch_byte_pairs", batch_byte_pairs_encode)
+
+enum class KernelFamily {
+    uniform,
+    batch,
+    batch_models,
+    batch_word_groups_decode,
+    batch_word_groups_encode,
+    batch_byte_pairs_decode,
+    batch_byte_pairs_encode,
+};
+
+enum class KernelId {
+    none, // no launch yet: the name is ""
+#define X(id, name, family) id,
+    RANS_AMD_KERNEL_NAMES(X)
+#undef X
+};
+
+struct KernelEntry {
+    KernelId id;
+    const char *name;
+    KernelFamily family;
+    const char *family_name;
+};
+
+// every entry, in the table's order (KernelId::none is not one)
+constexpr KernelEntry kKernelEntries[] = {
+#define X(id, name, family) {KernelId::id, name, KernelFamily::family, #family},
+    RANS_AMD_KERNEL_NAMES(X)
+#undef X
+};
+constexpr int kKernelEntryCount = (int)(sizeof(kKernelEntries) / sizeof(kKernelEntries[0]));
+
+constexpr const char *kernel_name(KernelId id) { return id == KernelId::none ? "" : kKernelEntries[(int)id - 1].name; }
+constexpr KernelFamily kernel_family(KernelId id) { return kKernelEntries[(int)id - 1].family; } // (not for KernelId::none)
+
+} // namespace rans_amd

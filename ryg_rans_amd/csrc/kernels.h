@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "kernel_names.hpp" // KernelId: what a launcher reports through `name`
 #include "wave_shape.hpp" // block sizes, LDS windows and the shapes of the wave-per-chunk launches (host-only)
 
 namespace rans_amd {
@@ -237,9 +238,9 @@ struct ZeroParams {
 };
 hipError_t launch_zero(const ZeroParams &p, hipStream_t stream);
 
-// All launchers return hipSuccess or the launch error; they never synchronise.
-hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **kernel_name);
-hipError_t launch_encode(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **kernel_names);
+// All launchers return hipSuccess or the launch error; they never synchronise.  *name receives the kernel that was launched.
+hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+hipError_t launch_encode(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 bool decode_dual_fits(uint32_t table0_bytes, uint32_t table1_bytes); // LDS room for two stream windows per wave (decode_dual.hip)
 bool encode_uses_lanes(int format, uint64_t nchunks, uint32_t n_ways);
 // 0: the fused placement does not fit; 1: mailbox in the block's LDS; 2: the tables fill the LDS, mailbox in global memory
@@ -251,10 +252,9 @@ hipError_t launch_compact(const CompactParams &p, int num_cus, hipStream_t strea
 // Ragged batches (rans_amd_decode_batch / rans_amd_encode_batch[_ordered]): one stream per wave, whatever the interleave -- but
 // for the 8-way word layout eight streams per wave, in the decoder under kVarBatchGroups and in the encoder under
 // kVarBatchEncGroups, and for the 2-way byte layout 32 streams per wave, in the decoder under kVarBatchPairs and in the
-// encoder under kVarBatchEncPairs; *batch_kernel receives the name of the kernel that was launched.  `format` is the kernel-side format
-// number.
-hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
-hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
+// encoder under kVarBatchEncPairs.  `format` is the kernel-side format number.
+hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // rans_amd_batch_order: a permutation of the stream indices in which floor(log2(count + 1)) never increases.
 // d_hist: 2 * kOrderBuckets words of workspace.
 constexpr uint32_t kOrderBuckets = 33;
@@ -297,11 +297,11 @@ struct AdaptEncParams {
     const uint32_t *sym_counts;
 };
 constexpr uint32_t kAdaptRcpEntries = 4097; // frequencies 0 .. 4096 (per-chunk models: scale_bits <= 12)
-hipError_t launch_encode_adaptive(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **name);
-// ... its ragged form and the ragged decoder with one model per stream (decode_wave.hip); *models_batch_kernel receives the
-// name of the kernel that was launched.  The decoder's `format` is kKernelFormatByteAdaptive / kKernelFormatWordAdaptive.
-hipError_t launch_encode_batch_models(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel);
-hipError_t launch_decode_batch_models(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel);
+hipError_t launch_encode_adaptive(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, KernelId *name);
+// ... its ragged form and the ragged decoder with one model per stream (decode_wave.hip).  The decoder's `format` is
+// kKernelFormatByteAdaptive / kKernelFormatWordAdaptive.
+hipError_t launch_encode_batch_models(int format, const AdaptEncParams &p, int num_cus, hipStream_t stream, KernelId *name);
+hipError_t launch_decode_batch_models(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // (format, n_ways) combinations with a kernel.
 bool ways_supported(int format, uint32_t n_ways);

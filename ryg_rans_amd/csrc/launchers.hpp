@@ -1,5 +1,6 @@
 // launchers.hpp -- entry points of the kernel translation units (internal; the public launchers of
-// kernels.h are assembled from these in dispatch.cpp).
+// kernels.h are assembled from these in dispatch.cpp).  Every launcher reports the kernel it launched as a KernelId
+// through `name` (may be null): an entry of the one registry in kernel_names.hpp, which also holds its family.
 #pragma once
 
 #include "kernels.h"
@@ -59,48 +60,46 @@ template <class F> hipError_t with_states_per_lane(int K, F &&f)
 }
 
 // wave-per-chunk kernels (N-way streams with N = 64 K lanes): decode_wave.hip, encode_wave.hip
-hipError_t launch_decode_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name);
-hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **name);
+hipError_t launch_decode_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+hipError_t launch_encode_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
-// ... their ragged forms (one stream per wave, per-stream symbol ranges): the names go to *batch_kernel
-hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
-hipError_t launch_encode_batch_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **batch_kernel);
+// ... their ragged forms (one stream per wave, per-stream symbol ranges)
+hipError_t launch_decode_batch_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+hipError_t launch_encode_batch_wave(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // ... and the ragged decoder with one model per stream (format: kKernelFormatByteAdaptive / kKernelFormatWordAdaptive)
-hipError_t launch_decode_batch_models_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **models_batch_kernel);
+hipError_t launch_decode_batch_models_wave(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // two chunks per wave, 64-way, byte-stream formats (decode_dual.hip); format: kKernelFormatAlias2[W] or RANS_AMD_FMT_BYTE
-hipError_t launch_decode_dual(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name);
+hipError_t launch_decode_dual(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // eight chunks per wave, the reference's 8-way word layout over u8 symbols (decode_groups.hip): chunks of a multiple of 4
 // symbols on a 4-byte aligned output, a partial last octet and a ragged last chunk included
 bool decode_word_groups_applicable(const DecParams &p);
-hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **name);
+hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // ... its ragged form (rans_amd_decode_batch under kVarBatchGroups): eight STREAMS per wave, each with its own symbol count
-// and output address, from eight streams on; the name goes to *group_batch_kernel
+// and output address, from eight streams on
 bool decode_batch_word_groups_applicable(const DecParams &p);
-hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, const char **group_batch_kernel);
+hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // 32 chunks per wave, the byte format's 2-way layout over u8 symbols (cum2sym tables), same file
 bool decode_byte_pairs_applicable(const DecParams &p);
-hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **name);
+hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // ... its ragged form (rans_amd_decode_batch under kVarBatchPairs): 32 STREAMS per wave, each with its own symbol count and
-// output address, from 32 streams on, the tables and the wave rings inside the CU's 160 KiB of LDS; the name goes to
-// *pair_batch_kernel
+// output address, from 32 streams on, the tables and the wave rings inside the CU's 160 KiB of LDS
 bool decode_batch_byte_pairs_applicable(const DecParams &p);
-hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, const char **pair_batch_kernel);
+hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // the 8-way word layout's encoder, eight chunks per wave (encode_groups.hip): chunks of a multiple of 4 u8 symbols, the
 // three-kernel placement, the slot layout or sized slots (no fused placement)
 bool encode_word_groups_applicable(const EncParams &p);
-hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **name);
+hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // ... its ragged form (rans_amd_encode_batch[_ordered] under kVarBatchEncGroups): eight STREAMS per wave, each with its own
-// symbol count, symbol address and slot, from eight streams on; the name goes to *group_batch_enc_kernel
+// symbol count, symbol address and slot, from eight streams on
 bool encode_batch_word_groups_applicable(const EncParams &p);
-hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, const char **group_batch_enc_kernel);
+hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // the byte format's 2-way layout, ragged (rans_amd_encode_batch[_ordered] under kVarBatchEncPairs): 32 STREAMS per wave, each
-// with its own symbol count, symbol address and slot, from 32 streams on, scale_bits 8..16; the name goes to
-// *pair_batch_enc_kernel
+// with its own symbol count, symbol address and slot, from 32 streams on, scale_bits 8..16
 bool encode_batch_byte_pairs_applicable(const EncParams &p);
-hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, const char **pair_batch_enc_kernel);
+hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // lane-per-stream kernels (N = 1, 2, 4, 8 with at least kLaneKernelMinChunks chunks): decode_lanes.hip, encode_lanes.hip
 constexpr uint64_t kLaneKernelMinChunks = 64;
@@ -108,8 +107,8 @@ inline bool lanes_applicable(uint64_t nchunks, uint32_t n_ways)
 {
     return nchunks >= kLaneKernelMinChunks && (n_ways == 1 || n_ways == 2 || n_ways == 4 || n_ways == 8);
 }
-hipError_t launch_decode_lanes(int format, const DecParams &p, int num_cus, hipStream_t stream, const char **name);
-hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipStream_t stream, const char **name);
+hipError_t launch_decode_lanes(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // true when launch_encode_lanes would take the staged kernel for this request -- the one that can place its chunks
 // itself (EncParams::status); everything but status / offsets / out / out_cap must be filled in
 bool encode_lanes_fused(const EncParams &p, int num_cus);

@@ -30,7 +30,8 @@ import numpy as np
 from _around_coders import align16, aligned_total, ref_offsets  # (the offset scan's reference says it already)
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
 from ryg_rans_amd import OPT_ENC_SCRATCH_RING
-from test_gpu_kernel_matrix import B, FUSED, KERNEL_ROWS, L16, LANE_FUSED, RX, ST, W, WAVES_PER_BLOCK, WG, pick, regime_symbols
+from _batch import WAVES_PER_BLOCK
+from _kernel_rows import B, FUSED, KERNEL_ROWS, L16, LANE_FUSED, RX, ST, W, WG, pick, regime_symbols
 
 POISON = 0xA5
 GUARD_BYTES = 4096

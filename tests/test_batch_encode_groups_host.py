@@ -3,13 +3,9 @@ hand-out order (rans_amd_encode_batch_ordered), the part that needs no GPU: the 
 option's constant, the entry point, and the proof that the rate inputs of tests/test_gpu_batch_encode_groups.py reach the
 bounds that file claims.
 
-test_no_group_batch_enc_kernel_without_a_row: the launchers of the encoders that pack several ragged streams into a wave
-report their kernel through an out-parameter spelled `*group_batch_enc_kernel = ...;` -- a fifth spelling beside
-`*name = ...;` (tests/test_gpu_kernel_matrix.py), `*batch_kernel = ...;` (tests/test_batch_host.py), `*models_batch_kernel
-= ...;` (tests/test_batch_models_host.py) and `*group_batch_kernel = ...;` (tests/test_batch_groups_host.py), invisible to
-those four tests.  Every literal of such a statement in ryg_rans_amd/csrc/*.hip must be the encode name of a row of
-ENC_GROUP_ROWS in tests/test_gpu_batch_encode_groups.py, and ENC_GROUP_ROWS must name no encoder the sources do not contain."""
-import glob
+test_no_group_batch_enc_kernel_without_a_row: every name of the registry's batch_word_groups_encode family
+(tests/_kernel_rows.py reads ryg_rans_amd/csrc/kernel_names.hpp) must be the encode name of a row of ENC_GROUP_ROWS, and
+ENC_GROUP_ROWS must name no encoder the registry does not hold."""
 import os
 import re
 
@@ -17,40 +13,18 @@ import numpy as np
 
 import _stream_rate as S
 import ryg_rans_amd as R
+from _batch import NO_ZERO_OCTETS, RATE_OCTET_KINDS, finish_octet, no_zero_batch, rate_octet
+from _kernel_rows import BATCH_WORD_GROUPS_ENCODE, ENC_GROUP_ROWS, ROOT, registry
 from _oracle import FMT_WORD
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
-_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
-
-
-def source_group_batch_enc_kernel_names(csrc=CSRC):
-    """Every string literal of a statement `*group_batch_enc_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
-    names, sites = set(), 0
-    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        for m in re.finditer(r"\*group_batch_enc_kernel\s*=\s*([^;]*);", open(path).read()):
-            sites += 1
-            names.update(_LITERAL.findall(m.group(1)))
-    return names, sites
 
 
 def test_no_group_batch_enc_kernel_without_a_row():
-    from test_gpu_batch_encode_groups import ENC_GROUP_ROWS
-    names, sites = source_group_batch_enc_kernel_names()
-    assert sites >= 1, sites
+    """(No count of assignment statements and no disjointness from other scans any more: the launchers report a KernelId, and
+    registry() asserts that no name occurs twice.)"""
+    names = registry()[BATCH_WORD_GROUPS_ENCODE]
     assert "k_encode_batch_word_groups" in names
     rows = {r["encode"] for r in ENC_GROUP_ROWS}
     assert names == rows, ("kernels no row of ENC_GROUP_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
-    # disjoint from what the four other spellings' scans find
-    from test_batch_groups_host import source_group_batch_kernel_names
-    from test_batch_host import source_batch_kernel_names
-    from test_batch_models_host import source_models_batch_kernel_names
-    from test_gpu_kernel_matrix import source_kernel_names
-    assert not names & source_kernel_names()[0]
-    assert not names & source_batch_kernel_names()[0]
-    assert not names & source_models_batch_kernel_names()[0]
-    assert not names & source_group_batch_kernel_names()[0]
     # the check has teeth: without its row a kernel is reported missing
     less = {r["encode"] for r in ENC_GROUP_ROWS if r["id"] != "word-8-enc-groups"}
     assert "k_encode_batch_word_groups" in names - less
@@ -82,11 +56,10 @@ def test_rate_inputs_reach_their_bounds():
     """The rare-only streams of the GPU file's rate octet hold a window of eight rounds with 96 bytes -- a 128-byte block
     per check of the group's ring, the most a valid stream can emit --, its quiet streams have at least 1000 consecutive
     rounds without a byte, and its bursts hold both; the finish octet's streams begin with rare symbols."""
-    from test_gpu_batch_encode_groups import RATE_KINDS, finish_octet, no_zero_batch, rate_octet
     freqs, counts, contents = rate_octet()
     assert np.array_equal(freqs, S.quiet_model()) and counts.size == 8
     seen = {"rare": 0, "quiet": 0, "bursts": 0}
-    for g, kind in enumerate(RATE_KINDS):
+    for g, kind in enumerate(RATE_OCTET_KINDS):
         assert contents[g].size == counts[g]
         rb = S.round_bytes(FMT_WORD, freqs, 12, contents[g], 8)
         if kind.startswith("rare+"):
@@ -108,7 +81,7 @@ def test_rate_inputs_reach_their_bounds():
     assert common == 0 and counts.tolist() == [128 * k for k in range(1, 9)]
     for g in range(8):  # whole lines only; the symbols the coder sees last are rare: the state it leaves is large
         assert np.all(np.isin(contents[g][:64], rare)) and S.windows(S.round_bytes(FMT_WORD, freqs, 12, contents[g], 8)).max() == 96
-    freqs, counts, contents = no_zero_batch()
+    freqs, counts, contents = no_zero_batch(*NO_ZERO_OCTETS)
     assert freqs[0] == 0 and int(freqs.sum()) == 4096 and counts.size == 24
     assert all(contents[k].size == counts[k] and not np.any(contents[k] == 0) for k in range(24))
     assert len({int(c) >> 7 for c in counts[8:16]}) >= 4 and counts[8:16].max() >= 256

@@ -2,44 +2,27 @@
 GPU: the name test of the pair batch ENCODER, the option's constant, and the proof that the inputs of
 tests/test_gpu_batch_encode_pairs.py reach the bounds that file claims.
 
-test_no_pair_batch_enc_kernel_without_a_row: the launcher of the encoder that packs 32 ragged byte streams into a wave
-reports its kernel through an out-parameter spelled `*pair_batch_enc_kernel = ...;` -- a seventh spelling beside `*name =
-...;` (tests/test_gpu_kernel_matrix.py), `*batch_kernel = ...;` (tests/test_batch_host.py), `*models_batch_kernel = ...;`
-(tests/test_batch_models_host.py), `*group_batch_kernel = ...;` (tests/test_batch_groups_host.py), `*group_batch_enc_kernel =
-...;` (tests/test_batch_encode_groups_host.py) and `*pair_batch_kernel = ...;` (tests/test_batch_pairs_host.py), invisible to
-those six tests, which anchor on the `*`.  Every literal of such a statement in ryg_rans_amd/csrc/*.hip must be the encode
-name of a row of ENC_PAIR_ROWS in tests/test_gpu_batch_encode_pairs.py, and ENC_PAIR_ROWS must name no encoder the sources
-do not contain."""
-import glob
+test_no_pair_batch_enc_kernel_without_a_row: every name of the registry's batch_byte_pairs_encode family (tests/_kernel_rows.py
+reads ryg_rans_amd/csrc/kernel_names.hpp) must be the encode name of a row of ENC_PAIR_ROWS, and ENC_PAIR_ROWS must name no
+encoder the registry does not hold."""
 import os
 import re
 
 import numpy as np
 
+import _batch as G
+import _kernel_rows as K
 import _stream_rate as S
 import ryg_rans_amd as R
+from _batch import NO_ZERO_WAVE_LOADS, RATE_WAVES, rate_kind, rate_model
+from _kernel_rows import BATCH_BYTE_PAIRS_ENCODE, ENC_PAIR_ROWS, ROOT, registry
 from _oracle import FMT_BYTE
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
-_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
-
-
-def source_pair_batch_enc_kernel_names(csrc=CSRC):
-    """Every string literal of a statement `*pair_batch_enc_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
-    names, sites = set(), 0
-    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        for m in re.finditer(r"\*pair_batch_enc_kernel\s*=\s*([^;]*);", open(path).read()):
-            sites += 1
-            names.update(_LITERAL.findall(m.group(1)))
-    return names, sites
 
 
 def test_no_pair_batch_enc_kernel_without_a_row():
-    from test_gpu_batch_encode_pairs import ENC_PAIR_ROWS
-    names, sites = source_pair_batch_enc_kernel_names()
-    assert sites >= 1, sites
+    """(No count of assignment statements and no disjointness from other scans any more: the launchers report a KernelId, and
+    registry() asserts that no name occurs twice.)"""
+    names = registry()[BATCH_BYTE_PAIRS_ENCODE]
     assert "k_encode_batch_byte_pairs" in names
     rows = {r["encode"] for r in ENC_PAIR_ROWS}
     assert names == rows, ("kernels no row of ENC_PAIR_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
@@ -48,16 +31,6 @@ def test_no_pair_batch_enc_kernel_without_a_row():
     # the decoder is named where the issue names it, and asked of the default context elsewhere (None)
     assert {(r["sb"], r["decode"]) for r in ENC_PAIR_ROWS} == {(14, "k_decode_batch<byte>"), (16, "k_decode_batch<byte>"), (12, None), (8, None),
                                                               (10, None)}
-    # disjoint from what the six other spellings' scans find
-    from test_batch_encode_groups_host import source_group_batch_enc_kernel_names
-    from test_batch_groups_host import source_group_batch_kernel_names
-    from test_batch_host import source_batch_kernel_names
-    from test_batch_models_host import source_models_batch_kernel_names
-    from test_batch_pairs_host import source_pair_batch_kernel_names
-    from test_gpu_kernel_matrix import source_kernel_names
-    for scan in (source_kernel_names, source_batch_kernel_names, source_models_batch_kernel_names, source_group_batch_kernel_names,
-                 source_group_batch_enc_kernel_names, source_pair_batch_kernel_names):
-        assert not names & scan()[0], scan.__name__
     # the check has teeth: without its rows the kernel is reported missing
     less = {r["encode"] for r in ENC_PAIR_ROWS if not r["id"].startswith("byte-2-enc-pairs")}
     assert "k_encode_batch_byte_pairs" in names - less
@@ -86,14 +59,12 @@ def _full_windows(rb, n):
 
 
 def test_rate_inputs_reach_the_rings_bound():
-    """1. Under 255 x 1 + one common symbol at 16 bits (test_gpu_batch_pairs.rate_model) a state that meets a frequency-1
+    """1. Under 255 x 1 + one common symbol at 16 bits (_batch.rate_model) a state that meets a frequency-1
     symbol puts two bytes, in every round: the frequency-1-only streams of the GPU file with at least eight rounds hold 32
     bytes in every window of eight full rounds -- a block per check of the pair's ring, its bound --, the common-only ones
     emit nothing (the 65536-symbol one: a thousand and more silent rounds in a row)."""
-    import test_gpu_batch_encode_pairs as G
-    from test_gpu_batch_pairs import RATE_WAVES, rate_kind, rate_model
-    assert G.OPT_BATCH_ENCODE_PAIRS == R.OPT_BATCH_ENCODE_PAIRS and G.OPT_BATCH_PAIRS == R.OPT_BATCH_PAIRS
-    assert G.E16["sb"] == 16 and G.EMAIN["sb"] == 14
+    assert K.OPT_BATCH_ENCODE_PAIRS == R.OPT_BATCH_ENCODE_PAIRS and K.OPT_BATCH_PAIRS == R.OPT_BATCH_PAIRS
+    assert K.E16["sb"] == 16 and K.EMAIN["sb"] == 14
     freqs, counts, contents, _ = G.rate_batch(16)
     assert np.array_equal(freqs, rate_model(16)) and counts.size == 64
     rare_long = 0
@@ -134,7 +105,6 @@ def test_a_dead_pair_is_fed_the_rings_bound():
     holds the odd count's half round); a stream of 255s is silent (4096 of them: 2 bytes in all).
     3. The finish inputs begin with at least 64 frequency-1 symbols other than 0 and never contain 0.
     4. The no-zero model has f[0] == 0, and no content under it holds a 0."""
-    import test_gpu_batch_encode_pairs as G
     f = G.mirrored_model()
     want = np.ones(256, dtype=np.uint32)
     want[255] = (1 << 16) - 255
@@ -157,7 +127,7 @@ def test_a_dead_pair_is_fed_the_rings_bound():
         assert np.all(freqs[c[:64]] == 1) and np.all(c[:64] != 0)
         S.simulate(FMT_BYTE, freqs, 16, c, 2)  # (a valid stream under the model)
     # 4.
-    freqs, counts, contents = G.no_zero_batch()
+    freqs, counts, contents = G.no_zero_batch(*NO_ZERO_WAVE_LOADS)
     assert freqs[0] == 0 and int(freqs.sum()) == 1 << 14 and counts.size == 96 and int(np.count_nonzero(counts == 0)) >= 1
     assert all(contents[k].size == counts[k] and not np.any(contents[k] == 0) for k in range(96))
     assert len({int(c) >> 5 for c in counts[32:64]}) >= 16 and counts[32:64].max() >= 256  # (the pairs die at different pieces)

@@ -1,33 +1,22 @@
 """Ragged batches, the part that needs no GPU: rans_amd_batch_layout and rans_amd_batch_slice against numpy, their argument
 errors, and the name test of the batch kernels.
 
-test_no_batch_kernel_without_a_row: the batch launchers report their kernel through an out-parameter spelled
-`*batch_kernel = ...;` (tests/test_gpu_kernel_matrix.py owns the `*name = ...;` statements and the uniform kernels).  Every
-literal of such a statement in ryg_rans_amd/csrc/*.hip must be named by a row of BATCH_ROWS in tests/test_gpu_batch.py, and
-BATCH_ROWS must name no kernel the sources do not contain."""
+test_no_batch_kernel_without_a_row: every name of the registry's batch family (tests/_kernel_rows.py reads
+ryg_rans_amd/csrc/kernel_names.hpp) must be named by a row of BATCH_ROWS, and BATCH_ROWS must name no kernel the registry does
+not hold."""
 import ctypes as C
-import glob
-import os
-import re
 
 import numpy as np
 import pytest
 
 import ryg_rans_amd as R
+from _batch import edge_counts
+from _kernel_rows import BATCH, BATCH_ROWS, registry, row_batch_kernel_names
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "ryg_rans_amd", "csrc")
 FORMATS = (FMT_BYTE, FMT_WORD, FMT_R64, FMT_ALIAS)
 WAYS = (1, 2, 8, 64, 128, 500)
 u32p, u64p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
-
-
-def _counts(seed, n=300):
-    rng = np.random.default_rng(seed)
-    c = (np.exp(rng.random(n) * np.log(65537.0)) - 1).astype(np.uint32)
-    c[:7] = (0, 1, 63, 64, 65, 259, 65536)
-    return c
 
 
 def _up(v, a):
@@ -36,7 +25,7 @@ def _up(v, a):
 
 @pytest.mark.parametrize("fmt", FORMATS)
 def test_batch_layout_equals_numpy(fmt):
-    counts = _counts(3)
+    counts = edge_counts(3)
     for ways in WAYS:
         bound = np.array([R.chunk_bound(fmt, int(c), ways) for c in counts], dtype=np.uint64)
         for align in (1, 4, 16):
@@ -126,27 +115,12 @@ def test_batch_argument_errors():
 
 # ---- the name test --------------------------------------------------------------------------------------------------
 
-_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
-
-
-def source_batch_kernel_names(csrc=CSRC):
-    """Every string literal of a statement `*batch_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
-    names, sites = set(), 0
-    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        for m in re.finditer(r"\*batch_kernel\s*=\s*([^;]*);", open(path).read()):
-            sites += 1
-            names.update(_LITERAL.findall(m.group(1)))
-    return names, sites
-
-
-def row_batch_kernel_names(rows):
-    return {r[k] for r in rows for k in ("decode", "encode")}
-
 
 def test_no_batch_kernel_without_a_row():
-    from test_gpu_batch import BATCH_ROWS
-    names, sites = source_batch_kernel_names()
-    assert sites >= 2, sites  # decode_wave.hip's chain and encode_wave.hip's
+    """(The scan of the sources this test once read counted its assignment statements to guard its own completeness, and was
+    held disjoint from the other families' scans; the launchers now report a KernelId, and registry() asserts that no name
+    occurs twice.)"""
+    names = registry()[BATCH]
     for must in ("k_decode_batch_word64", "k_decode_batch<word>", "k_decode_batch<byte>", "k_decode_batch<byte, slot records>",
                  "k_decode_batch<r64>", "k_decode_batch<r64 search>", "k_decode_batch<alias>", "k_decode_batch<word, u16 symbols>",
                  "k_encode_batch<word>"):
@@ -155,9 +129,6 @@ def test_no_batch_kernel_without_a_row():
     rows = row_batch_kernel_names(BATCH_ROWS)
     assert not names - rows, ("batch kernels no row of BATCH_ROWS expects", sorted(names - rows))
     assert not rows - names, ("BATCH_ROWS names kernels no launcher reports", sorted(rows - names))
-    # the batch names stay out of the uniform kernels' table, whose test reads `*name = ...;`
-    from test_gpu_kernel_matrix import source_kernel_names
-    assert not names & source_kernel_names()[0]
     # the check has teeth: without its row a kernel is reported missing
     less = [r for r in BATCH_ROWS if r["decode"] != "k_decode_batch<alias>"]
     assert "k_decode_batch<alias>" in names - row_batch_kernel_names(less)

@@ -1,25 +1,19 @@
 """Ragged batches with one model per stream, the part that needs no GPU: rans_amd_encode_batch_adaptive_bound against numpy
 and against the oracle's streams, the argument errors of the three entry points, and the name test of their kernels.
 
-test_no_models_batch_kernel_without_a_row: the launchers of these kernels report through a third out-parameter, spelled
-`*models_batch_kernel = ...;` (tests/test_gpu_kernel_matrix.py owns `*name = ...;`, tests/test_batch_host.py owns
-`*batch_kernel = ...;`).  Every literal of such a statement in ryg_rans_amd/csrc/*.hip must be named by a row of MODEL_ROWS
-in tests/test_gpu_batch_models.py, MODEL_ROWS must name no kernel the sources do not contain, and the names are disjoint from
-what the other two tests find."""
+test_no_models_batch_kernel_without_a_row: every name of the registry's batch_models family (tests/_kernel_rows.py reads
+ryg_rans_amd/csrc/kernel_names.hpp) must be named by a row of MODEL_ROWS, and MODEL_ROWS must name no kernel the registry does
+not hold."""
 import ctypes as C
-import glob
-import os
-import re
 
 import numpy as np
 import pytest
 
 import ryg_rans_amd as R
+from _batch import edge_counts
+from _kernel_rows import BATCH_MODELS, MODEL_ROWS, registry
 from _oracle import FMT_BYTE, FMT_R64, FMT_WORD
-from test_batch_host import _LITERAL, _counts, source_batch_kernel_names
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "ryg_rans_amd", "csrc")
 WAYS = (1, 2, 8, 64, 128, 500)
 u32p = C.POINTER(C.c_uint32)
 
@@ -30,7 +24,7 @@ def _up(v, a):
 
 @pytest.mark.parametrize("fmt", [FMT_BYTE, FMT_WORD])
 def test_bound_equals_numpy(fmt):
-    counts = _counts(3)
+    counts = edge_counts(3)
     for ways in WAYS:
         # a stream's worst case: two bytes a symbol and the flushed states, in whole 64-byte lines
         want = int(_up(counts.astype(np.uint64) * 2 + ways * 4, 64).sum())
@@ -98,29 +92,15 @@ def test_argument_errors():
     assert enc(out=b + 8) == R.E_ARG and dec(cont=b + 8) == R.E_ARG  # 16-byte alignment of the container
 
 
-def source_models_batch_kernel_names(csrc=CSRC):
-    """Every string literal of a statement `*models_batch_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
-    names, sites = set(), 0
-    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        for m in re.finditer(r"\*models_batch_kernel\s*=\s*([^;]*);", open(path).read()):
-            sites += 1
-            names.update(_LITERAL.findall(m.group(1)))
-    return names, sites
-
-
 def test_no_models_batch_kernel_without_a_row():
-    from test_gpu_batch_models import MODEL_ROWS
-    names, sites = source_models_batch_kernel_names()
-    assert sites >= 4, sites
+    """(No count of assignment statements and no disjointness from other scans any more: the launchers report a KernelId, and
+    registry() asserts that no name occurs twice.)"""
+    names = registry()[BATCH_MODELS]
     assert names == {"k_decode_batch_models<word>", "k_decode_batch_models<byte>", "k_encode_batch_models<word>",
                      "k_encode_batch_models<byte>"}, names
     rows = {r[k] for r in MODEL_ROWS for k in ("decode", "encode")}
     assert not names - rows, ("kernels no row of MODEL_ROWS expects", sorted(names - rows))
     assert not rows - names, ("MODEL_ROWS names kernels no launcher reports", sorted(rows - names))
-    # disjoint from the two other spellings' names, and invisible to their tests
-    from test_gpu_kernel_matrix import source_kernel_names
-    assert not names & source_kernel_names()[0]
-    assert not names & source_batch_kernel_names()[0]
     # the check has teeth: without its rows a kernel is reported missing
     less = {r[k] for r in MODEL_ROWS if r["fmt"] != FMT_BYTE for k in ("decode", "encode")}
     assert names - less == {"k_decode_batch_models<byte>", "k_encode_batch_models<byte>"}

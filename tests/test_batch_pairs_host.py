@@ -2,57 +2,31 @@
 test of the pair batch kernel, the option's constant, and the proof that the rate inputs of tests/test_gpu_batch_pairs.py
 reach the bounds that file claims.
 
-test_no_pair_batch_kernel_without_a_row: the launcher of the kernel that packs 32 ragged byte streams into a wave reports
-its kernel through an out-parameter spelled `*pair_batch_kernel = ...;` -- a sixth spelling beside `*name = ...;`
-(tests/test_gpu_kernel_matrix.py), `*batch_kernel = ...;` (tests/test_batch_host.py), `*models_batch_kernel = ...;`
-(tests/test_batch_models_host.py), `*group_batch_kernel = ...;` (tests/test_batch_groups_host.py) and
-`*group_batch_enc_kernel = ...;` (tests/test_batch_encode_groups_host.py), invisible to those five tests, which anchor on
-the `*`.  Every literal of such a statement in ryg_rans_amd/csrc/*.hip must be the decode name of a row of PAIR_ROWS in
-tests/test_gpu_batch_pairs.py, and PAIR_ROWS must name no decoder the sources do not contain."""
-import glob
+test_no_pair_batch_kernel_without_a_row: every name of the registry's batch_byte_pairs_decode family (tests/_kernel_rows.py
+reads ryg_rans_amd/csrc/kernel_names.hpp) must be the decode name of a row of PAIR_ROWS, and PAIR_ROWS must name no decoder
+the registry does not hold."""
 import os
 import re
 
 import numpy as np
 
+import _batch as G
+import _kernel_rows as K
 import _stream_rate as S
 import ryg_rans_amd as R
+from _kernel_rows import BATCH_BYTE_PAIRS_DECODE, PAIR_ROWS, ROOT, registry
 from _oracle import FMT_BYTE
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
-_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
-
-
-def source_pair_batch_kernel_names(csrc=CSRC):
-    """Every string literal of a statement `*pair_batch_kernel = ...;` in csrc/*.hip -> (names, number of statements)."""
-    names, sites = set(), 0
-    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        for m in re.finditer(r"\*pair_batch_kernel\s*=\s*([^;]*);", open(path).read()):
-            sites += 1
-            names.update(_LITERAL.findall(m.group(1)))
-    return names, sites
 
 
 def test_no_pair_batch_kernel_without_a_row():
-    from test_gpu_batch_pairs import PAIR_ROWS
-    names, sites = source_pair_batch_kernel_names()
-    assert sites >= 1, sites
+    """(No count of assignment statements and no disjointness from other scans any more: the launchers report a KernelId, and
+    registry() asserts that no name occurs twice.)"""
+    names = registry()[BATCH_BYTE_PAIRS_DECODE]
     assert "k_decode_batch_byte_pairs" in names
     rows = {r["decode"] for r in PAIR_ROWS}
     assert names == rows, ("kernels no row of PAIR_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
     assert all(r["ways"] == 2 and r["fmt"] == FMT_BYTE and r["encode"] == "k_encode_batch<byte>" for r in PAIR_ROWS)
     assert sorted((r["sb"], r["K"]) for r in PAIR_ROWS) == [(8, 256), (10, 64), (12, 256), (14, 256), (16, 256)]
-    # disjoint from what the five other spellings' scans find
-    from test_batch_encode_groups_host import source_group_batch_enc_kernel_names
-    from test_batch_groups_host import source_group_batch_kernel_names
-    from test_batch_host import source_batch_kernel_names
-    from test_batch_models_host import source_models_batch_kernel_names
-    from test_gpu_kernel_matrix import source_kernel_names
-    for scan in (source_kernel_names, source_batch_kernel_names, source_models_batch_kernel_names, source_group_batch_kernel_names,
-                 source_group_batch_enc_kernel_names):
-        assert not names & scan()[0], scan.__name__
     # the check has teeth: without its rows the kernel is reported missing
     less = {r["decode"] for r in PAIR_ROWS if not r["id"].startswith("byte-2-pairs")}
     assert "k_decode_batch_byte_pairs" in names - less
@@ -85,10 +59,9 @@ def test_rate_inputs_reach_the_rings_bound():
         quad-mates at the bound --, and the 65536-symbol one of the single wave-load has 1000 and more consecutive silent
         rounds.  (No stream of fewer than 1000 rounds can show a thousand silent ones: the thousand rounds are the long
         stream's.)
-    The inputs are the GPU file's own generators."""
-    import test_gpu_batch_pairs as G
-    assert G.OPT_BATCH_PAIRS == R.OPT_BATCH_PAIRS and G.OPT_BATCH_GROUPS == R.OPT_BATCH_GROUPS  # (the option these inputs are decoded under)
-    assert 16 in G.RATE_BITS and G.RATE_ROW[16]["sb"] == 16
+    The inputs are the GPU file's own generators (tests/_batch.py)."""
+    assert K.OPT_BATCH_PAIRS == R.OPT_BATCH_PAIRS and K.OPT_BATCH_GROUPS == R.OPT_BATCH_GROUPS  # (the option these inputs are decoded under)
+    assert 16 in G.RATE_BITS and K.RATE_ROW[16]["sb"] == 16
     freqs, counts, contents, phases = G.rate_batch(16)
     b_freqs = np.ones(256, dtype=np.uint32)
     b_freqs[S.COMMON] = (1 << 16) - 255

@@ -1,7 +1,8 @@
 """Ragged batches on the GPU: many independent streams, each with its own symbol count, every stream against the oracle.
 
-BATCH_ROWS: one row per shape, naming the batch kernels the library must report for it (tests/test_batch_host.py holds the
-rows to the names the launchers can report).  Every row runs in the regimes of tests/test_gpu_kernel_matrix.py --
+BATCH_ROWS (tests/_kernel_rows.py): one row per shape, naming the batch kernels the library must report for it
+(tests/test_batch_host.py holds the rows to the names the launchers can report); the harness is tests/_batch.py.  Every row
+runs in the regimes of tests/test_gpu_kernel_matrix.py --
 
   U  one stream per launch (each of the mandatory lengths in turn)
   H  about half as many streams as there are resident waves
@@ -12,54 +13,12 @@ with sym_align = 1 (odd output addresses: element stores) and once with sym_alig
 bench.gen_zipf with seed 1; the checker is the CPU oracle (Oracle.encode per stream, threaded over the host cores), never
 the library itself.  Output buffers are filled with a poison value first: the padding between streams and a guard region
 behind the last one must come back untouched."""
-import os
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 import pytest
 
 from _around_coders import ref_order_keys
-from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
-
-WAVES_PER_BLOCK = 16
-GUARD = 4096  # symbols behind the last stream
-POISON = 0xA5
-MAX_LEN = 65536
-
-
-def _row(rid, fmt, sb, K, ways, decode, encode):
-    return {"id": rid, "fmt": fmt, "sb": sb, "K": K, "ways": ways, "decode": decode, "encode": encode}
-
-
-BATCH_ROWS = [
-    _row("word-64", FMT_WORD, 12, 256, 64, "k_decode_batch_word64", "k_encode_batch<word>"),
-    _row("word-128", FMT_WORD, 12, 256, 128, "k_decode_batch<word>", "k_encode_batch<word>"),
-    _row("word-8", FMT_WORD, 12, 256, 8, "k_decode_batch<word>", "k_encode_batch<word>"),
-    _row("word-u16-64", FMT_WORD, 12, 1024, 64, "k_decode_batch<word, u16 symbols>", "k_encode_batch<word>"),
-    _row("byte-64-14bit", FMT_BYTE, 14, 256, 64, "k_decode_batch<byte>", "k_encode_batch<byte>"),
-    _row("byte-64-12bit", FMT_BYTE, 12, 256, 64, "k_decode_batch<byte, slot records>", "k_encode_batch<byte>"),
-    _row("byte-2", FMT_BYTE, 14, 256, 2, "k_decode_batch<byte>", "k_encode_batch<byte>"),
-    _row("r64-64", FMT_R64, 14, 256, 64, "k_decode_batch<r64>", "k_encode_batch<r64>"),
-    _row("r64-2", FMT_R64, 14, 256, 2, "k_decode_batch<r64>", "k_encode_batch<r64>"),
-    _row("r64-search-64", FMT_R64, 20, 256, 64, "k_decode_batch<r64 search>", "k_encode_batch<r64 full-width>"),
-    _row("alias256-64", FMT_ALIAS, 16, 256, 64, "k_decode_batch<alias>", "k_encode_batch<alias, LDS remap>"),
-]
-ROW = {r["id"]: r for r in BATCH_ROWS}
-UNIT = {FMT_BYTE: 1, FMT_ALIAS: 1, FMT_WORD: 2, FMT_R64: 4}
-
-
-def mandatory_lengths(ways):
-    return [0, 1, ways - 1, ways, ways + 1, 4 * ways + 3, MAX_LEN]
-
-
-def draw_lengths(n_streams, ways, seed):
-    """Log-uniform in [0, 64 Ki]; the mandatory lengths at fixed-seed positions (all of them from seven streams on)."""
-    rng = np.random.default_rng(seed)
-    c = (np.exp(rng.random(n_streams) * np.log(MAX_LEN + 1.0)) - 1.0).astype(np.int64).clip(0, MAX_LEN).astype(np.uint32)
-    must = mandatory_lengths(ways)
-    if n_streams >= len(must):
-        c[rng.choice(n_streams, len(must), replace=False)] = must
-    return c
+from _batch import POISON, Batch, draw_lengths, graph_decode_script, mandatory_lengths, resident_waves, run_graph_script, run_row
+from _kernel_rows import BATCH_ROWS, ROW
 
 
 @pytest.fixture(scope="module")
@@ -70,119 +29,6 @@ def gpu():
     ctx = R.Context(0)
     yield R, ctx, torch
     ctx.close()
-
-
-def resident_waves(torch):
-    return torch.cuda.get_device_properties(0).multi_processor_count * 2 * WAVES_PER_BLOCK
-
-
-class Batch:
-    """The symbols of a batch (dense, bench.gen_zipf seed 1), its models and the oracle's stream of every stream.
-    contents: {stream: its symbols} in place of the generator's (tests/test_gpu_rate_extremes.py); freqs: a normalised model
-    in place of the one counted from the generator's sample."""
-
-    def __init__(self, R, ctx, torch, oracle, row, counts, seed=1, contents=None, freqs=None):
-        import bench
-        self.R, self.ctx, self.torch, self.row = R, ctx, torch, row
-        self.counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        self.n = self.counts.size
-        self.dense_offs = np.concatenate(([0], np.cumsum(self.counts.astype(np.int64))))
-        total = int(self.dense_offs[-1])
-        self.d_dense = bench.gen_zipf(torch, max(total, 1), row["K"], 1.0, seed, "cuda")[:total]
-        if contents:
-            h = self.d_dense.cpu().numpy()
-            for c, content in contents.items():
-                assert content.size == self.counts[c]
-                h[self.dense_offs[c]:self.dense_offs[c + 1]] = np.asarray(content).astype(np.uint16).astype(h.dtype)
-            self.d_dense = torch.from_numpy(h).cuda()
-        if freqs is not None:
-            self.freqs = np.ascontiguousarray(freqs, dtype=np.uint32)
-        else:
-            # (the model comes from a fixed 1 Mi-symbol sample of the same generator: every symbol of the alphabet is in it)
-            sample = bench.gen_zipf(torch, 1 << 20, row["K"], 1.0, seed, "cuda")
-            self.freqs, _ = R.normalize_freqs(ctx.count_freqs_device(sample, row["K"]), 1 << row["sb"])
-        self.gm = ctx.model(row["fmt"], self.freqs, row["sb"])
-        self.om = oracle.model(self.freqs, row["sb"], with_alias=(row["fmt"] == FMT_ALIAS))
-        h = self.d_dense.cpu().numpy()
-        self.h_dense = h.view(np.uint16) if h.dtype == np.int16 else h
-        fmt, ways, om, offs = row["fmt"], row["ways"], self.om, self.dense_offs
-
-        def run(c):
-            return oracle.encode(fmt, om, self.h_dense[offs[c]:offs[c + 1]], ways)
-        with ThreadPoolExecutor(oracle.host_threads()) as ex:
-            self.streams = list(ex.map(run, range(self.n), chunksize=64))
-        self.lens = np.array([s.size for s in self.streams], dtype=np.uint32)
-        self.d_counts = torch.from_numpy(self.counts.view(np.int32)).cuda()
-
-    def poison(self):
-        return POISON if self.d_dense.dtype == self.torch.uint8 else -23131  # 0xA5A5 as int16
-
-    def laid_out(self, align):
-        """-> (d_buf, sym_offs, slot_offs): the symbols at batch_layout's offsets in a poison-filled buffer with a guard."""
-        torch = self.torch
-        sym_offs, slot_offs = self.R.batch_layout(self.counts, self.row["fmt"], self.row["ways"], align)
-        d_buf = torch.full((int(sym_offs[-1]) + GUARD,), self.poison(), dtype=self.d_dense.dtype, device="cuda")
-        if self.d_dense.numel():
-            shift = torch.from_numpy(sym_offs[:-1].astype(np.int64) - self.dense_offs[:-1]).cuda()
-            idx = torch.arange(self.d_dense.numel(), device="cuda") + torch.repeat_interleave(shift, self.d_counts.to(torch.int64))
-            d_buf[idx] = self.d_dense
-        return d_buf, sym_offs, slot_offs
-
-    def dev(self, a, dtype):
-        return self.torch.from_numpy(np.ascontiguousarray(a).astype(dtype)).cuda()
-
-    def oracle_container(self, seed=5):
-        """The oracle's streams concatenated in a shuffled order at unit-aligned offsets with small gaps -> (cont, offs, lens)."""
-        unit = UNIT[self.row["fmt"]]
-        rng = np.random.default_rng(seed)
-        order = rng.permutation(self.n)
-        gaps = rng.integers(0, 4, self.n).astype(np.int64) * unit
-        starts = np.zeros(self.n, dtype=np.int64)
-        at = unit  # (not even the first stream starts on 16 bytes)
-        for k, c in enumerate(order):
-            at += int(gaps[k])
-            starts[c] = at
-            at += int(self.lens[c])
-        cont = np.zeros(at + 16, dtype=np.uint8)
-        for c in range(self.n):
-            cont[starts[c]:starts[c] + self.lens[c]] = self.streams[c]
-        return cont, starts, at
-
-    def check_streams(self, cont, offs, lens, what):
-        """Every stream of a GPU-made container (host arrays) == the oracle's, byte for byte."""
-        assert np.array_equal(lens.astype(np.uint32), self.lens), (what, "lengths differ from the oracle's")
-        for c in range(self.n):
-            a = int(offs[c])
-            assert np.array_equal(cont[a:a + int(lens[c])], self.streams[c]), (what, "stream", c, "count", int(self.counts[c]))
-
-
-def run_row(b, align, with_oracle_container=True):
-    R, ctx, torch, row = b.R, b.ctx, b.torch, b.row
-    ways = row["ways"]
-    d_buf, sym_offs, slot_offs = b.laid_out(align)
-    d_sym = b.dev(sym_offs, np.int64)
-    d_slot = b.dev(slot_offs, np.int64)
-    # 1. encode_batch: every stream == Oracle.encode of its input, ending at its slot's end
-    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, ways, d_slot)
-    assert ctx.last_encode_kernel()[0] == row["encode"] and ctx.last_encode_placement() == 2, ctx.last_encode_kernel()
-    ctx.encode_status()
-    h_offs, h_lens = offs.cpu().numpy().astype(np.uint64)[:b.n], lens.cpu().numpy().view(np.uint32)[:b.n]
-    assert np.array_equal(h_offs + h_lens, slot_offs[1:]), "a stream does not end at its slot's end"
-    b.check_streams(cont.cpu().numpy(), h_offs, h_lens, "encode_batch align %d" % align)
-    # 2. decode_batch of the GPU's own container: the input, padding and guard untouched
-    out = torch.full_like(d_buf, b.poison())
-    ctx.decode_batch(b.gm, cont, int(slot_offs[-1]), offs, lens, d_sym, b.d_counts, ways, out)
-    assert ctx.last_decode_kernel() == row["decode"], ctx.last_decode_kernel()
-    assert torch.equal(out, d_buf), "decode of the GPU's container (align %d)" % align
-    # 3. decode_batch of a batch the oracle made: unordered, unit-aligned offsets
-    if with_oracle_container:
-        o_cont, o_starts, o_bytes = b.oracle_container()
-        out = torch.full_like(d_buf, b.poison())
-        ctx.decode_batch(b.gm, b.dev(o_cont, np.uint8), o_bytes, b.dev(o_starts, np.int64), b.dev(b.lens, np.int32), d_sym, b.d_counts,
-                         ways, out)
-        assert ctx.last_decode_kernel() == row["decode"], ctx.last_decode_kernel()
-        assert torch.equal(out, d_buf), "decode of the oracle's container (align %d)" % align
-    return cont, offs, lens, d_buf, d_sym, d_slot, sym_offs, slot_offs
 
 
 def _cases():
@@ -383,51 +229,8 @@ def test_batch_container_compact_then_decode(gpu, oracle):
     assert torch.equal(out, d_buf)
 
 
-_GRAPH_SCRIPT = r"""
-import os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-import numpy as np, torch
-import bench, ryg_rans_amd as R
-from test_gpu_batch import draw_lengths, POISON
-ctx = R.Context(0)
-counts = draw_lengths(3000, 64, 61)
-sym_offs, slot_offs = R.batch_layout(counts, R.FMT_WORD, 64, 4)
-d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
-freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, 256), 4096)
-gm = ctx.model(R.FMT_WORD, freqs, 12)
-d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
-d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda(); d_slot = torch.from_numpy(slot_offs.astype(np.int64)).cuda()
-cont, offs, lens = ctx.encode_batch(gm, d_syms, d_sym, d_counts, 64, d_slot)
-ctx.encode_status()
-want = torch.full_like(d_syms, POISON)
-ctx.decode_batch(gm, cont, int(slot_offs[-1]), offs, lens, d_sym, d_counts, 64, want)   # (outside the capture first)
-out = torch.full_like(d_syms, POISON)
-s = torch.cuda.Stream()
-g = torch.cuda.CUDAGraph()
-with torch.cuda.stream(s):
-    with torch.cuda.graph(g, stream=s):
-        ctx.decode_batch(gm, cont, int(slot_offs[-1]), offs, lens, d_sym, d_counts, 64, out, sync=False)
-for _ in range(3):
-    out.fill_(POISON)
-    g.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, want), "replay differs"
-assert ctx.decode_errors() == 0 and ctx.last_decode_kernel() == "k_decode_batch_word64"
-print("graph ok")
-"""
-
-
 @pytest.mark.gpu
 def test_batch_decode_in_a_captured_graph(tmp_path):
     """One captured decode_batch, replayed three times, in a child process under a time limit of its own.  Graph replay
     needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set below that the test does not apply."""
-    import subprocess
-    import sys
-    q = os.environ.get("GPU_MAX_HW_QUEUES")
-    if q is not None and int(q) < 4:
-        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
-    script = tmp_path / "graph_batch.py"
-    script.write_text(_GRAPH_SCRIPT)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    run_graph_script(tmp_path, "graph_batch.py", graph_decode_script("k_decode_batch_word64"))

@@ -2,9 +2,9 @@
 kernel rans_amd_encode_batch[_ordered] launches on a context with RANS_AMD_OPT_BATCH_ENCODE_GROUPS = 1, and the hand-out
 order of the batch encoders (d_order).
 
-ENC_GROUP_ROWS names the kernel the library must report (tests/test_batch_encode_groups_host.py holds the rows to the names
-the launchers can report).  The helpers are tests/test_gpu_batch.py's: run_row checks the reported kernel, every stream byte
-for byte against the oracle's, each ending at its slot's end, and decodes the result.
+ENC_GROUP_ROWS (tests/_kernel_rows.py) names the kernel the library must report (tests/test_batch_encode_groups_host.py holds
+the rows to the names the launchers can report).  The helpers are tests/_batch.py's: run_row checks the reported kernel,
+every stream byte for byte against the oracle's, each ending at its slot's end, and decodes the result.
 
 The coder works from a stream's last symbol to its first, so a wave's eight groups start together and finish at different
 times: a group is finalised (states, last blocks, index entry) right behind its last round and is dead from then on, while
@@ -16,24 +16,15 @@ is stored whole, and what it holds below the stream is whatever the group's ring
 Wall time on an MI355X: 12.7 s for the 21 cases of this file -- 6.0 s of it the `several` regime (81 925 calls of the oracle),
 2.7 s the captured graph's child process, 1.7 s the first case's setup and 0.6 s its call (they load the kernels), 0.7 s the
 `half` regime, 0.2 s the order test, 0.04 s and less for each of the others."""
-import os
-
 import numpy as np
 import pytest
 
-import _stream_rate as S
+from _batch import (NO_ZERO_OCTETS, POISON, Batch, draw_lengths, draw_log_uniform, encode_poisoned, finish_octet, graph_encode_script,
+                    mandatory_lengths, no_zero_batch, rate_octet, resident_waves, run_graph_script, run_row, same_result)
+from _kernel_rows import EROW, OPT_BATCH_ENCODE_GROUPS, OPT_BATCH_GROUPS, ROW
 from _oracle import FMT_WORD
-from test_gpu_batch import POISON, ROW, Batch, draw_lengths, mandatory_lengths, resident_waves, run_row
 
-OPT_BATCH_GROUPS = 5
-OPT_BATCH_ENCODE_GROUPS = 6
-ENC_GROUP_ROWS = [
-    {"id": "word-8-enc-groups", "fmt": FMT_WORD, "sb": 12, "K": 256, "ways": 8,
-     "decode": "k_decode_batch<word>", "encode": "k_encode_batch_word_groups"},
-]
-EROW = ENC_GROUP_ROWS[0]
 WAVE = "k_encode_batch<word>"
-
 
 @pytest.fixture(scope="module")
 def gpu():
@@ -46,85 +37,6 @@ def gpu():
     yield R, ctx, torch, off
     off.close()
     ctx.close()
-
-
-def draw_log_uniform(n_streams, max_len, seed):
-    """Log-uniform in [0, max_len]."""
-    rng = np.random.default_rng(seed)
-    return (np.exp(rng.random(n_streams) * np.log(max_len + 1.0)) - 1.0).astype(np.int64).clip(0, max_len).astype(np.uint32)
-
-
-# ---- inputs that the host test proves to sit at their bounds (tests/test_batch_encode_groups_host.py) -----------------
-def finish_octet():
-    """Counts 128 k, k = 1..8, bursts under 3841 + 255 x 1: every stream BEGINS with a run of 64 rare symbols -- the last the
-    coder sees --, so a finished group's state is large, and the common symbol (byte value 0, what a dead group is fed)
-    pushes it over its threshold: the dead group's lanes write into its ring while the others run on."""
-    freqs = S.rate_model()
-    counts = np.array([128 * k for k in range(1, 9)], dtype=np.uint32)
-    return freqs, counts, {g: S.bursts(freqs, int(counts[g]), 40 + g) for g in range(8)}
-
-
-RATE_KINDS = ("quiet", "rare+0", "bursts", "rare+1", "quiet", "bursts", "rare+2", "rare+0")
-RATE_COUNTS = (12288, 128 * 9 + 77, 1500, 128 * 20, 9001, 333, 641, 12288)
-
-
-def rate_octet():
-    """One wave under 4065 + 16 + 15 x 1: rare-only streams (96 bytes in every eight rounds: a block per check), quiet
-    streams (common-only: no block for a thousand rounds and more, then only the states) and bursts, at different lengths
-    -> (freqs, counts, {group: symbols})."""
-    freqs = S.quiet_model()
-    contents = {}
-    for g, (kind, n) in enumerate(zip(RATE_KINDS, RATE_COUNTS)):
-        if kind == "quiet":
-            contents[g] = S.common_only(freqs, n)
-        elif kind == "bursts":
-            contents[g] = S.bursts(freqs, n, 60 + g, lead=8 * g)
-        else:
-            contents[g] = S.rare_only(freqs, n, 60 + g, shift=int(kind[5:]))
-    return freqs, np.array(RATE_COUNTS, dtype=np.uint32), contents
-
-
-def no_zero_model():
-    """Byte value 0 has no record (frequency 0), every other value has: 3842 + 254 x 1.  dense256 is false: TRACK."""
-    f = np.ones(256, dtype=np.uint32)
-    f[0] = 0
-    f[1] = 4096 - 254
-    return f
-
-
-def no_zero_batch():
-    """24 streams (three octets) of uneven lengths, drawn from no_zero_model: groups park at different times, some from the start."""
-    freqs = no_zero_model()
-    counts = np.array([(37 * k * k + 11 * k) % 1500 for k in range(24)], dtype=np.uint32)
-    counts[5] = 0
-    return freqs, counts, {k: S.drawn(freqs, int(counts[k]), 80 + k) for k in range(24)}
-
-
-# ---- helpers --------------------------------------------------------------------------------------------------------
-def stream_mask(torch, n_bytes, offs, lens, n):
-    """True for the bytes of [offs[c], offs[c] + lens[c]), c < n."""
-    d = torch.zeros(n_bytes + 1, dtype=torch.int32, device="cuda")
-    o, ln = offs[:n].to(torch.int64), lens[:n].to(torch.int64)
-    d.index_add_(0, o, torch.ones(n, dtype=torch.int32, device="cuda"))
-    d.index_add_(0, o + ln, torch.full((n,), -1, dtype=torch.int32, device="cuda"))
-    return torch.cumsum(d[:n_bytes], 0) > 0
-
-
-def same_result(torch, a, b, n, what):
-    """Two (container, offsets, lengths) results: equal index entries, equal stream bytes."""
-    assert torch.equal(a[1][:n], b[1][:n]) and torch.equal(a[2][:n], b[2][:n]), (what, "index entries differ")
-    m = stream_mask(torch, a[0].numel(), a[1], a[2], n)
-    assert torch.equal(a[0][m], b[0][m]), (what, "stream bytes differ")
-
-
-def encode_poisoned(b, cx, gm, d_buf, d_sym, d_slot, cap, d_order=None, sentinel=None):
-    """encode_batch into a poison-filled container with 4096 guard bytes behind `cap`; sentinel: pre-filled index entries."""
-    torch = b.torch
-    d_out = torch.full((cap + 4096,), POISON, dtype=torch.uint8, device="cuda")
-    d_offs = torch.full((b.n,), 0 if sentinel is None else sentinel, dtype=torch.int64, device="cuda")
-    d_lens = torch.full((b.n,), 0 if sentinel is None else sentinel, dtype=torch.int32, device="cuda")
-    return cx.encode_batch(gm, d_buf, d_sym, b.d_counts, b.row["ways"], d_slot, d_out=d_out, d_offsets=d_offs, d_lengths=d_lens,
-                           out_cap=cap, d_order=d_order)
 
 
 OCTETS = {
@@ -185,7 +97,7 @@ def test_no_false_e_model_from_parked_groups(gpu, oracle):
     record of byte value 0, which must not reach the flags.  encode_status() is OK (run_row asks) and every stream is the
     oracle's."""
     R, ctx, torch, _ = gpu
-    freqs, counts, contents = no_zero_batch()
+    freqs, counts, contents = no_zero_batch(*NO_ZERO_OCTETS)
     assert freqs[0] == 0 and all(not np.any(c == 0) for c in contents.values())
     b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
     for align in (4, 1):
@@ -197,7 +109,7 @@ def test_true_e_model_is_reported_and_contained(gpu, oracle):
     """The same batch with one symbol of one stream overwritten by 0 on the device: E_MODEL, as the default context reports
     for the same batch; every stream of the other octets is the oracle's; nothing is written outside the container."""
     R, ctx, torch, off = gpu
-    freqs, counts, contents = no_zero_batch()
+    freqs, counts, contents = no_zero_batch(*NO_ZERO_OCTETS)
     b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
     gm_off = off.model(FMT_WORD, freqs, 12)
     d_buf, sym_offs, slot_offs = b.laid_out(4)
@@ -384,62 +296,11 @@ def test_option_takes_zero_or_one(gpu, oracle):
         off.set_option(OPT_BATCH_GROUPS, 0)
 
 
-_GRAPH_SCRIPT = r"""
-import os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-import numpy as np, torch
-import bench, ryg_rans_amd as R
-from test_gpu_batch import draw_lengths, POISON
-from test_gpu_batch_encode_groups import stream_mask
-ctx = R.Context(0)
-ctx.set_option(R.OPT_BATCH_ENCODE_GROUPS, 1)
-counts = draw_lengths(3000, 8, 61)
-n = counts.size
-sym_offs, slot_offs = R.batch_layout(counts, R.FMT_WORD, 8, 4)
-d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
-freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, 256), 4096)
-gm = ctx.model(R.FMT_WORD, freqs, 12)
-d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
-d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda(); d_slot = torch.from_numpy(slot_offs.astype(np.int64)).cuda()
-cap = int(slot_offs[-1])
-want, w_offs, w_lens = ctx.encode_batch(gm, d_syms, d_sym, d_counts, 8, d_slot)   # (outside the capture first)
-ctx.encode_status()
-assert ctx.last_encode_kernel()[0] == "k_encode_batch_word_groups", ctx.last_encode_kernel()
-back = torch.full_like(d_syms, POISON)
-ctx.decode_batch(gm, want, cap, w_offs, w_lens, d_sym, d_counts, 8, back)
-m = stream_mask(torch, cap, w_offs, w_lens, n)
-out = torch.full((cap,), POISON, dtype=torch.uint8, device="cuda")
-offs = torch.zeros(n, dtype=torch.int64, device="cuda"); lens = torch.zeros(n, dtype=torch.int32, device="cuda")
-s = torch.cuda.Stream()
-g = torch.cuda.CUDAGraph()
-with torch.cuda.stream(s):
-    with torch.cuda.graph(g, stream=s):
-        ctx.encode_batch(gm, d_syms, d_sym, d_counts, 8, d_slot, d_out=out, d_offsets=offs, d_lengths=lens, out_cap=cap)
-for _ in range(3):
-    out.fill_(POISON); offs.zero_(); lens.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    ctx.encode_status()
-    assert torch.equal(offs, w_offs[:n]) and torch.equal(lens, w_lens[:n]), "replay: index entries differ"
-    assert torch.equal(out[m], want[:cap][m]), "replay: stream bytes differ"
-assert ctx.last_encode_kernel()[0] == "k_encode_batch_word_groups"
-print("graph ok")
-"""
-
-
 @pytest.mark.gpu
 def test_group_batch_encode_in_a_captured_graph(tmp_path):
     """One captured encode_batch of 3000 8-way streams with the option on: one eager call first, then three replays into a
     poison-refilled container, each equal to the eager result (stream bytes, offsets, lengths), in a child process under a
     time limit of its own.  Graph replay needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set
     below that the test does not apply."""
-    import subprocess
-    import sys
-    q = os.environ.get("GPU_MAX_HW_QUEUES")
-    if q is not None and int(q) < 4:
-        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
-    script = tmp_path / "graph_batch_encode_groups.py"
-    script.write_text(_GRAPH_SCRIPT)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    run_graph_script(tmp_path, "graph_batch_encode_groups.py",
+                     graph_encode_script(EROW["encode"], "FMT_WORD", 8, 12, "OPT_BATCH_ENCODE_GROUPS"))

@@ -1,57 +1,37 @@
 """Ragged batches of the reference's 2-way byte layout CODED with thirty-two streams per wave: k_encode_batch_byte_pairs, the
 kernel rans_amd_encode_batch[_ordered] launches on a context with RANS_AMD_OPT_BATCH_ENCODE_PAIRS = 1.
 
-ENC_PAIR_ROWS names the kernel the library must report (tests/test_batch_encode_pairs_host.py holds the rows to the names the
-launchers can report).  The helpers are tests/test_gpu_batch.py's: run_row checks the reported kernel, every stream byte for
-byte against the oracle's, each ending at its slot's end, and decodes the result.  The decoder a row names is the one the
-context reports for that shape with the option at its default: "k_decode_batch<byte>" for the 14-bit and 16-bit rows, and
-for the other three whatever the default context reports (asked at run time, decoder_of; run_row then asserts it).
+ENC_PAIR_ROWS (tests/_kernel_rows.py) names the kernel the library must report (tests/test_batch_encode_pairs_host.py holds
+the rows to the names the launchers can report).  The helpers are tests/_batch.py's: run_row checks the reported kernel,
+every stream byte for byte against the oracle's, each ending at its slot's end, and decodes the result.  The decoder a row
+names is the one the context reports for that shape with the option at its default: "k_decode_batch<byte>" for the 14-bit and
+16-bit rows, and for the other three whatever the default context reports (asked at run time, decoder_of; run_row then
+asserts it).
 
 The coder works from a stream's last symbol to its first, so a wave's 32 pairs start together and finish at different
 times: a pair is finalised (states, last blocks, index entry) right behind its last round and is dead from then on, while
 the wave's eight-round sequence -- full exec, every lane's byte count its own two compares -- runs on for the others: a dead
 pair's cursor moves, and its lanes keep writing into its ring.  The shapes below are the smallest at which that can go wrong;
-the rate inputs are proved to reach their bounds without a GPU by tests/test_batch_encode_pairs_host.py, which imports the
-generators below.
+the rate inputs are proved to reach their bounds without a GPU by tests/test_batch_encode_pairs_host.py, from the same
+generators (tests/_batch.py).
 
 Containers of two encodes are compared over the bytes of their streams: the 16-byte piece that holds a stream's first byte
 is stored whole, and what it holds below the stream is whatever the pair's ring held (as with the wave kernels' flushes).
 Wall time on an MI355X: 7.3 s for the 40 cases of this file -- 2.7 s of it the captured graph's child process, 1.7 s the first
 case's setup and 0.6 s its call (they load the kernels), 0.4 s the `half` regime, 0.26 s the 65536-symbol rare stream beside
 dead pairs, 0.13 s the `several` regime and the per-stream-models case, 0.06 s and less for each of the others."""
-import os
-
 import numpy as np
 import pytest
 
-import _stream_rate as S
-from _oracle import FMT_BYTE, FMT_WORD
-from test_gpu_batch import POISON, ROW, Batch, draw_lengths, mandatory_lengths, resident_waves, run_row
-from test_gpu_batch_encode_groups import encode_poisoned, same_result
-from test_gpu_batch_pairs import POOL, PoolBatch, draw_log_uniform, rate_batch, rate_wave
-from test_gpu_batch_pairs import PMAIN as DEC_PAIR_ROW
+from _batch import (NO_ZERO_WAVE_LOADS, POISON, POOL, Batch, ModelBatch, PoolBatch, draw_lengths, draw_log_uniform, encode_poisoned,
+                    finish_batch, graph_encode_script, mandatory_lengths, no_zero_batch, rate_batch, rate_wave, resident_waves,
+                    run_graph_script, run_model_row, run_row, same_result)
+from _kernel_rows import E16, EMAIN, ENC_PAIR_ROWS, MODEL_ROW, OPT_BATCH_ENCODE_GROUPS, OPT_BATCH_ENCODE_PAIRS, OPT_BATCH_PAIRS, ROW
+from _kernel_rows import PMAIN as DEC_PAIR_ROW
+from _oracle import FMT_BYTE
 
-OPT_BATCH_ENCODE_GROUPS = 6
-OPT_BATCH_PAIRS = 7
-OPT_BATCH_ENCODE_PAIRS = 8
 KERNEL = "k_encode_batch_byte_pairs"
 WAVE = "k_encode_batch<byte>"
-
-
-def _enc_pair_row(rid, sb, K, decode):
-    return {"id": rid, "fmt": FMT_BYTE, "sb": sb, "K": K, "ways": 2, "decode": decode, "encode": KERNEL}
-
-
-# decode None: the decoder the default context reports for the shape (decoder_of)
-ENC_PAIR_ROWS = [
-    _enc_pair_row("byte-2-enc-pairs", 14, 256, "k_decode_batch<byte>"),       # the reference's scale_bits (main.cpp:139)
-    _enc_pair_row("byte-2-enc-pairs-16bit", 16, 256, "k_decode_batch<byte>"),
-    _enc_pair_row("byte-2-enc-pairs-12bit", 12, 256, None),
-    _enc_pair_row("byte-2-enc-pairs-8bit", 8, 256, None),
-    _enc_pair_row("byte-2-enc-pairs-64sym-10bit", 10, 64, None),                # (the record table is padded to 256)
-]
-EROWS = {r["id"]: r for r in ENC_PAIR_ROWS}
-EMAIN, E16 = EROWS["byte-2-enc-pairs"], EROWS["byte-2-enc-pairs-16bit"]
 
 
 @pytest.fixture(scope="module")
@@ -87,46 +67,6 @@ def decoder_of(gpu, oracle, row):
         assert torch.equal(out, d_buf)
         _DECODERS[row["id"]] = off.last_decode_kernel()
     return dict(row, decode=_DECODERS[row["id"]])
-
-
-# ---- inputs that the host test proves to sit at their bounds (tests/test_batch_encode_pairs_host.py) -----------------
-def mirrored_model():
-    """255 x 1 and one common symbol at 2^16, the common one LAST: byte value 0 -- what a dead pair is fed -- has frequency 1."""
-    f = np.ones(256, dtype=np.uint32)
-    f[255] = (1 << 16) - 255
-    return f
-
-
-def finish_batch():
-    """One wave-load under the mirrored model, counts 128 (g % 8 + 1): whole pieces only, every pair finishes at a piece
-    boundary while others run on.  Every stream BEGINS with 64 frequency-1 symbols other than 0 -- the last the coder sees --
-    and holds no 0; runs of 64 frequency-1 and 64 common symbols in turn.  A dead pair is fed zeros: two bytes per lane and
-    round, 32 bytes per eight rounds, the ring's bound -> (freqs, counts, {stream: symbols})."""
-    freqs = mirrored_model()
-    counts = np.array([128 * (g % 8 + 1) for g in range(32)], dtype=np.uint32)
-    contents = {}
-    for g in range(32):
-        n = int(counts[g])
-        c = np.random.default_rng(40 + g).integers(1, 255, n).astype(np.uint8)
-        c[(np.arange(n) // 64) % 2 == 1] = 255
-        contents[g] = c
-    return freqs, counts, contents
-
-
-def no_zero_model():
-    """Byte value 0 has no record (frequency 0), every other value has: 16130 + 254 x 1 at 14 bits.  dense256 is false: TRACK."""
-    f = np.ones(256, dtype=np.uint32)
-    f[0] = 0
-    f[1] = (1 << 14) - 254
-    return f
-
-
-def no_zero_batch():
-    """96 streams (three wave-loads) of uneven counts, one of them 0, drawn from no_zero_model: pairs die at different times,
-    some from the start."""
-    freqs = no_zero_model()
-    counts = np.array([(37 * k * k + 11 * k) % 1500 for k in range(96)], dtype=np.uint32)
-    return freqs, counts, {k: S.drawn(freqs, int(counts[k]), 80 + k) for k in range(96)}
 
 
 def _padded(lengths, n=32, pad=200):
@@ -187,7 +127,7 @@ def _rate_cases():
 
 @pytest.mark.parametrize("which", list(_rate_cases()))
 def test_rate_extremes_in_one_wave(gpu, oracle, which):
-    """tests/test_gpu_batch_pairs.py's rate inputs on the encoder: a frequency-1-only stream of 65536 symbols (32 bytes per
+    """The byte-pair rate inputs (tests/_batch.py) on the encoder: a frequency-1-only stream of 65536 symbols (32 bytes per
     eight rounds: a block per check) beside 31 common-only ones that are dead for most of it; a common-only stream of 65536
     (no block for a thousand rounds and more) beside rare-only ones that drain one after the other; and the 64-stream batches
     at 16 and 14 bits.  At sym_align 4 and 1, without an order (run_row) and under batch_order's (the same result)."""
@@ -215,7 +155,7 @@ def test_no_false_e_model_from_dead_pairs(gpu, oracle):
     of byte value 0, which must not reach the flags.  encode_status() is OK (run_row asks) and every stream is the oracle's,
     at both alignments."""
     R, ctx, torch, _ = gpu
-    freqs, counts, contents = no_zero_batch()
+    freqs, counts, contents = no_zero_batch(*NO_ZERO_WAVE_LOADS)
     assert freqs[0] == 0 and all(not np.any(c == 0) for c in contents.values())
     b = Batch(R, ctx, torch, oracle, EMAIN, counts, contents=contents, freqs=freqs)
     for align in (4, 1):
@@ -228,7 +168,7 @@ def test_true_e_model_is_reported_and_contained(gpu, oracle):
     the default context reports for the same batch; every stream of the other wave-loads is the oracle's; the poison behind
     out_cap is intact; the next call succeeds."""
     R, ctx, torch, off = gpu
-    freqs, counts, contents = no_zero_batch()
+    freqs, counts, contents = no_zero_batch(*NO_ZERO_WAVE_LOADS)
     b = Batch(R, ctx, torch, oracle, EMAIN, counts, contents=contents, freqs=freqs)
     gm_off = off.model(FMT_BYTE, freqs, 14)
     d_buf, sym_offs, slot_offs = b.laid_out(4)
@@ -365,7 +305,7 @@ def test_half_and_several(gpu, oracle, regime):
     """half: fewer wave-loads than the launch has resident waves, prototype lengths log-uniform up to 64 Ki with the
     mandatory ones.  several: at least 1.25 x as many wave-loads as resident waves, so that waves come back for further
     claims and must reset state, cursor, block count and ring; prototype lengths log-uniform up to 1024.  Every stream is one
-    of at most 4096 prototypes the oracle coded once (tests/test_gpu_batch_pairs.py PoolBatch); every stream of the batch is
+    of at most 4096 prototypes the oracle coded once (tests/_batch.py PoolBatch); every stream of the batch is
     compared on the device with its prototype's.  The last wave-load is partial; with and without d_order at sym_align = 4;
     the result decodes back on the wave kernel and, on a third context with RANS_AMD_OPT_BATCH_PAIRS, on
     k_decode_batch_byte_pairs."""
@@ -423,9 +363,6 @@ def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_
 def test_per_stream_models_keep_their_kernel_with_the_option_on(gpu, oracle):
     """encode_batch_adaptive of 40 2-way byte streams, each with its own model, on the context with the option on: the wave
     kernel with one model per stream, every stream against the oracle."""
-    from test_gpu_batch_models import ROW as MODEL_ROW
-    from test_gpu_batch_models import ModelBatch
-    from test_gpu_batch_models import run_row as run_model_row
     R, ctx, torch, _ = gpu
     row = MODEL_ROW["byte-2-12bit"]
     assert row["encode"] != KERNEL
@@ -473,62 +410,11 @@ def test_option_takes_zero_or_one(gpu, oracle):
     run_row(b, 4)
 
 
-_GRAPH_SCRIPT = r"""
-import os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-import numpy as np, torch
-import bench, ryg_rans_amd as R
-from test_gpu_batch import draw_lengths, POISON
-from test_gpu_batch_encode_groups import stream_mask
-ctx = R.Context(0)
-ctx.set_option(R.OPT_BATCH_ENCODE_PAIRS, 1)
-counts = draw_lengths(3000, 2, 61)
-n = counts.size
-sym_offs, slot_offs = R.batch_layout(counts, R.FMT_BYTE, 2, 4)
-d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
-freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, 256), 1 << 14)
-gm = ctx.model(R.FMT_BYTE, freqs, 14)
-d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
-d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda(); d_slot = torch.from_numpy(slot_offs.astype(np.int64)).cuda()
-cap = int(slot_offs[-1])
-want, w_offs, w_lens = ctx.encode_batch(gm, d_syms, d_sym, d_counts, 2, d_slot)   # (outside the capture first)
-ctx.encode_status()
-assert ctx.last_encode_kernel()[0] == "k_encode_batch_byte_pairs", ctx.last_encode_kernel()
-back = torch.full_like(d_syms, POISON)
-ctx.decode_batch(gm, want, cap, w_offs, w_lens, d_sym, d_counts, 2, back)
-m = stream_mask(torch, cap, w_offs, w_lens, n)
-out = torch.full((cap,), POISON, dtype=torch.uint8, device="cuda")
-offs = torch.zeros(n, dtype=torch.int64, device="cuda"); lens = torch.zeros(n, dtype=torch.int32, device="cuda")
-s = torch.cuda.Stream()
-g = torch.cuda.CUDAGraph()
-with torch.cuda.stream(s):
-    with torch.cuda.graph(g, stream=s):
-        ctx.encode_batch(gm, d_syms, d_sym, d_counts, 2, d_slot, d_out=out, d_offsets=offs, d_lengths=lens, out_cap=cap)
-for _ in range(3):
-    out.fill_(POISON); offs.zero_(); lens.zero_()
-    g.replay()
-    torch.cuda.synchronize()
-    ctx.encode_status()
-    assert torch.equal(offs, w_offs[:n]) and torch.equal(lens, w_lens[:n]), "replay: index entries differ"
-    assert torch.equal(out[m], want[:cap][m]), "replay: stream bytes differ"
-assert ctx.last_encode_kernel()[0] == "k_encode_batch_byte_pairs"
-print("graph ok")
-"""
-
-
 @pytest.mark.gpu
 def test_pair_batch_encode_in_a_captured_graph(tmp_path):
     """One captured encode_batch of 3000 2-way byte streams with the option on: one eager call first, then three replays into a
     poison-refilled container, each equal to the eager result (stream bytes, offsets, lengths), in a child process under a
     time limit of its own.  Graph replay needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set
     below that the test does not apply."""
-    import subprocess
-    import sys
-    q = os.environ.get("GPU_MAX_HW_QUEUES")
-    if q is not None and int(q) < 4:
-        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
-    script = tmp_path / "graph_batch_encode_pairs.py"
-    script.write_text(_GRAPH_SCRIPT)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    run_graph_script(tmp_path, "graph_batch_encode_pairs.py",
+                     graph_encode_script(KERNEL, "FMT_BYTE", 2, 14, "OPT_BATCH_ENCODE_PAIRS"))

@@ -1,29 +1,22 @@
 """Ragged batches of the reference's 8-way word layout with EIGHT streams per wave: k_decode_batch_word_groups, the kernel
 rans_amd_decode_batch launches on a context with RANS_AMD_OPT_BATCH_GROUPS = 1.
 
-GROUP_ROWS names the kernel the library must report (tests/test_batch_groups_host.py holds the rows to the names the
-launchers can report).  The helpers are tests/test_gpu_batch.py's: every decode is checked against the symbols the
-oracle's streams were made from, from the GPU's own container and from one the oracle made (shuffled, unit-aligned
+GROUP_ROWS (tests/_kernel_rows.py) names the kernel the library must report (tests/test_batch_groups_host.py holds the rows
+to the names the launchers can report).  The helpers are tests/_batch.py's: every decode is checked against the symbols
+the oracle's streams were made from, from the GPU's own container and from one the oracle made (shuffled, unit-aligned
 offsets, gaps), into a poison-filled buffer whose padding and guard must come back untouched.
 
 A wave's eight groups hold eight streams with eight different symbol counts: the wave runs the 16-round sequence
 max(count >> 7) times, a group that has run out of 128-byte lines is parked (its bits of the ballot zeroed, its state put
 back behind every block, its line not stored), and what count & 127 leaves goes one round at a time.  The shapes below
 are the smallest at which that can go wrong."""
-import os
-
 import numpy as np
 import pytest
 
+from _batch import (GUARD, POISON, Batch, Coded, draw_lengths, draw_log_uniform, graph_decode_script, mandatory_lengths, resident_waves,
+                    run_graph_script, run_row)
+from _kernel_rows import GROW, OPT_BATCH_GROUPS, ROW
 from _oracle import FMT_WORD
-from test_gpu_batch import GUARD, POISON, ROW, Batch, draw_lengths, mandatory_lengths, resident_waves, run_row
-
-OPT_BATCH_GROUPS = 5
-GROUP_ROWS = [
-    {"id": "word-8-groups", "fmt": FMT_WORD, "sb": 12, "K": 256, "ways": 8,
-     "decode": "k_decode_batch_word_groups", "encode": "k_encode_batch<word>"},
-]
-GROW = GROUP_ROWS[0]
 
 
 @pytest.fixture(scope="module")
@@ -37,38 +30,6 @@ def gpu():
     yield R, ctx, torch, off
     off.close()
     ctx.close()
-
-
-def draw_log_uniform(n_streams, max_len, seed):
-    """Log-uniform in [0, max_len]."""
-    rng = np.random.default_rng(seed)
-    return (np.exp(rng.random(n_streams) * np.log(max_len + 1.0)) - 1.0).astype(np.int64).clip(0, max_len).astype(np.uint32)
-
-
-class Coded:
-    """A batch laid out, coded by the GPU and concatenated by the oracle: what the order and damage tests decode."""
-
-    def __init__(self, b, align):
-        self.b = b
-        self.d_buf, self.sym_offs, self.slot_offs = b.laid_out(align)
-        self.d_sym, d_slot = b.dev(self.sym_offs, np.int64), b.dev(self.slot_offs, np.int64)
-        self.cont, self.offs, self.lens = b.ctx.encode_batch(b.gm, self.d_buf, self.d_sym, b.d_counts, b.row["ways"], d_slot)
-        b.ctx.encode_status()
-        o_cont, o_starts, self.o_bytes = b.oracle_container()
-        self.o_cont, self.o_offs, self.o_lens = b.dev(o_cont, np.uint8), b.dev(o_starts, np.int64), b.dev(b.lens, np.int32)
-
-    def containers(self):
-        yield "gpu", self.cont, int(self.slot_offs[-1]), self.offs, self.lens
-        yield "oracle", self.o_cont, self.o_bytes, self.o_offs, self.o_lens
-
-    def decode_all(self, d_order, what):
-        """Both containers into poison-filled buffers; each must equal the laid-out input, padding and guard included."""
-        b = self.b
-        for name, cont, nbytes, offs, lens in self.containers():
-            out = b.torch.full_like(self.d_buf, b.poison())
-            b.ctx.decode_batch(b.gm, cont, nbytes, offs, lens, self.d_sym, b.d_counts, b.row["ways"], out, d_order=d_order)
-            assert b.ctx.last_decode_kernel() == b.row["decode"], b.ctx.last_decode_kernel()
-            assert b.torch.equal(out, self.d_buf), (what, name)
 
 
 OCTETS = {
@@ -230,59 +191,10 @@ def test_option_takes_zero_or_one(gpu, oracle):
     run_row(b, 4)
 
 
-_GRAPH_SCRIPT = r"""
-import os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-import numpy as np, torch
-import bench, ryg_rans_amd as R
-from test_gpu_batch import draw_lengths, POISON
-ctx = R.Context(0)
-ctx.set_option(R.OPT_BATCH_GROUPS, 1)
-counts = draw_lengths(3000, 8, 61)
-sym_offs, slot_offs = R.batch_layout(counts, R.FMT_WORD, 8, 4)
-d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
-freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, 256), 4096)
-gm = ctx.model(R.FMT_WORD, freqs, 12)
-d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
-d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda(); d_slot = torch.from_numpy(slot_offs.astype(np.int64)).cuda()
-cont, offs, lens = ctx.encode_batch(gm, d_syms, d_sym, d_counts, 8, d_slot)
-ctx.encode_status()
-want = torch.full_like(d_syms, POISON)
-ctx.decode_batch(gm, cont, int(slot_offs[-1]), offs, lens, d_sym, d_counts, 8, want)   # (outside the capture first)
-assert ctx.last_decode_kernel() == "k_decode_batch_word_groups", ctx.last_decode_kernel()
-covered = torch.zeros(d_syms.numel(), dtype=torch.bool, device="cuda")
-idx = torch.repeat_interleave(d_sym[:-1], d_counts.to(torch.int64)) + (torch.arange(int(counts.sum()), device="cuda") -
-      torch.repeat_interleave(torch.cumsum(d_counts.to(torch.int64), 0) - d_counts.to(torch.int64), d_counts.to(torch.int64)))
-covered[idx] = True
-assert torch.equal(want[covered], d_syms[covered]) and bool((want[~covered] == POISON).all()), "eager decode differs from the input"
-out = torch.full_like(d_syms, POISON)
-s = torch.cuda.Stream()
-g = torch.cuda.CUDAGraph()
-with torch.cuda.stream(s):
-    with torch.cuda.graph(g, stream=s):
-        ctx.decode_batch(gm, cont, int(slot_offs[-1]), offs, lens, d_sym, d_counts, 8, out, sync=False)
-for _ in range(3):
-    out.fill_(POISON)
-    g.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, want), "replay differs"
-assert ctx.decode_errors() == 0 and ctx.last_decode_kernel() == "k_decode_batch_word_groups"
-print("graph ok")
-"""
-
-
 @pytest.mark.gpu
 def test_group_batch_decode_in_a_captured_graph(tmp_path):
     """One captured decode_batch of 3000 8-way streams with the option on: one eager call first, then three replays, each
     equal to the eager result, in a child process under a time limit of its own.  Graph replay needs the process's default
     of four hardware queues: with GPU_MAX_HW_QUEUES set below that the test does not apply.  2.5 s."""
-    import subprocess
-    import sys
-    q = os.environ.get("GPU_MAX_HW_QUEUES")
-    if q is not None and int(q) < 4:
-        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
-    script = tmp_path / "graph_batch_groups.py"
-    script.write_text(_GRAPH_SCRIPT)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    run_graph_script(tmp_path, "graph_batch_groups.py",
+                     graph_decode_script(GROW["decode"], ways=8, option="OPT_BATCH_GROUPS"))

@@ -2,38 +2,21 @@
 every stream's frequency row and bytes against the oracle, which builds the model of each stream from that stream alone
 (Oracle.count_freqs + normalize + encode per stream, threaded over the host cores; the library never checks itself).
 
-MODEL_ROWS: one row per shape, naming the kernels the library must report for it (tests/test_batch_models_host.py holds the
-rows to the names the launchers can report).  Regimes U, H and R, the lengths and the poison rules are those of
-tests/test_gpu_batch.py.  Input is bench.gen_zipf with seed 1, stream c's symbols rotated by (37 c) mod 256, so that the
+MODEL_ROWS (tests/_kernel_rows.py): one row per shape, naming the kernels the library must report for it
+(tests/test_batch_models_host.py holds the rows to the names the launchers can report).  Regimes U, H and R, the lengths, the
+poison rules and ModelBatch are tests/_batch.py's.  Input is bench.gen_zipf with seed 1, stream c's symbols rotated by (37 c) mod 256, so that the
 rows differ from stream to stream; four more streams are always in: 4096 and 16384 symbols exactly (the sizes the uniform
 encoder keeps register-resident: here they take the two-pass form), one value repeated 4 N + 3 times (word format: frequency
 4096, a word leaves per symbol) and all 256 values once (at 8 bits every frequency is 1)."""
-import os
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 import pytest
 
+from _batch import POISON, ModelBatch, draw_lengths, graph_decode_script, mandatory_lengths, resident_waves, run_graph_script
+from _batch import run_model_row as run_row
+from _kernel_rows import MODEL_ROW as ROW
+from _kernel_rows import MODEL_ROWS
 from _oracle import FMT_BYTE, FMT_WORD
-from test_gpu_batch import GUARD, POISON, draw_lengths, mandatory_lengths, resident_waves
 
-
-def _row(rid, fmt, sb, ways):
-    f = "word" if fmt == FMT_WORD else "byte"
-    return {"id": rid, "fmt": fmt, "sb": sb, "ways": ways, "decode": "k_decode_batch_models<%s>" % f,
-            "encode": "k_encode_batch_models<%s>" % f}
-
-
-MODEL_ROWS = [
-    _row("word-64", FMT_WORD, 12, 64),
-    _row("word-8", FMT_WORD, 12, 8),
-    _row("word-128", FMT_WORD, 12, 128),
-    _row("byte-64-12bit", FMT_BYTE, 12, 64),
-    _row("byte-2-12bit", FMT_BYTE, 12, 2),
-    _row("byte-64-8bit", FMT_BYTE, 8, 64),
-]
-ROW = {r["id"]: r for r in MODEL_ROWS}
-UNIT = {FMT_BYTE: 1, FMT_WORD: 2}
 ONE_VALUE = 201
 
 
@@ -51,131 +34,6 @@ def gpu():
     ctx = R.Context(0)
     yield R, ctx, torch
     ctx.close()
-
-
-class ModelBatch:
-    """The symbols of a batch, and the oracle's row and stream of every stream under the stream's own model."""
-
-    def __init__(self, R, ctx, torch, oracle, row, counts, contents=None):
-        import bench
-        self.R, self.ctx, self.torch, self.row = R, ctx, torch, row
-        self.counts = np.ascontiguousarray(counts, dtype=np.uint32)
-        self.n = self.counts.size
-        self.dense_offs = np.concatenate(([0], np.cumsum(self.counts.astype(np.int64))))
-        total = int(self.dense_offs[-1])
-        h = bench.gen_zipf(torch, max(total, 1), 256, 1.0, 1, "cuda")[:total].cpu().numpy()
-        h = h + np.repeat(((37 * np.arange(self.n)) % 256).astype(np.uint8), self.counts)  # (u8: wraps modulo 256)
-        for c, content in (contents or {}).items():
-            assert content.size == self.counts[c]
-            h[self.dense_offs[c]:self.dense_offs[c + 1]] = content
-        self.h_dense = h
-        self.d_dense = torch.from_numpy(h).cuda()
-        self.d_counts = torch.from_numpy(self.counts.view(np.int32)).cuda()
-        fmt, sb, ways, offs = row["fmt"], row["sb"], row["ways"], self.dense_offs
-        any_model = oracle.model(np.full(256, (1 << sb) // 256, dtype=np.uint32), sb)  # (an empty stream looks nothing up)
-
-        def run(c):
-            syms = h[offs[c]:offs[c + 1]]
-            if syms.size == 0:
-                return np.zeros(256, dtype=np.uint16), oracle.encode(fmt, any_model, syms, ways)
-            f, _ = oracle.normalize(oracle.count_freqs(syms, 256), 1 << sb)
-            return f.astype(np.uint16), oracle.encode(fmt, oracle.model(f, sb), syms, ways)
-        with ThreadPoolExecutor(oracle.host_threads()) as ex:
-            done = list(ex.map(run, range(self.n), chunksize=64))
-        self.rows = np.stack([d[0] for d in done]) if self.n else np.zeros((0, 256), np.uint16)
-        self.streams = [d[1] for d in done]
-        self.lens = np.array([s.size for s in self.streams], dtype=np.uint32)
-        self.bound = R.encode_batch_adaptive_bound(fmt, self.counts, ways)
-
-    def laid_out(self, align):
-        """-> (d_buf, sym_offs): the symbols at batch_layout's offsets in a poison-filled buffer with a guard behind them."""
-        torch = self.torch
-        sym_offs, _ = self.R.batch_layout(self.counts, self.row["fmt"], self.row["ways"], align)
-        d_buf = torch.full((int(sym_offs[-1]) + GUARD,), POISON, dtype=torch.uint8, device="cuda")
-        if self.d_dense.numel():
-            shift = torch.from_numpy(sym_offs[:-1].astype(np.int64) - self.dense_offs[:-1]).cuda()
-            idx = torch.arange(self.d_dense.numel(), device="cuda") + torch.repeat_interleave(shift, self.d_counts.to(torch.int64))
-            d_buf[idx] = self.d_dense
-        return d_buf, sym_offs
-
-    def dev(self, a, dtype):
-        return self.torch.from_numpy(np.ascontiguousarray(a).astype(dtype)).cuda()
-
-    def d_rows(self, rows=None):
-        return self.torch.from_numpy(np.ascontiguousarray(self.rows if rows is None else rows).view(np.int16).reshape(-1)).cuda()
-
-    def encode(self, d_buf, d_sym, cap=None):
-        """One encode_batch_adaptive into a poison-filled buffer of bound + 4096 bytes -> host (cont, offs[n + 1], lens, rows, total)
-        and the device tensors."""
-        torch, row = self.torch, self.row
-        d_out = torch.full((self.bound + 4096,), POISON, dtype=torch.uint8, device="cuda")
-        t = self.ctx.encode_batch_adaptive(d_buf, d_sym, self.d_counts, row["ways"], row["sb"], fmt=row["fmt"], d_out=d_out,
-                                           cap=self.bound if cap is None else cap)
-        cont, offs, lens, rows, total = t
-        return (cont.cpu().numpy(), offs.cpu().numpy().astype(np.uint64), lens.cpu().numpy().view(np.uint32)[:self.n],
-                rows.cpu().numpy().view(np.uint16).reshape(-1, 256)[:self.n], total), t
-
-    def decode(self, cont, cbytes, offs, lens, d_rows, d_sym, out, **kw):
-        row = self.row
-        return self.ctx.decode_batch_adaptive(cont, cbytes, offs, lens, d_rows, d_sym, self.d_counts, row["ways"], row["sb"], out,
-                                              fmt=row["fmt"], **kw)
-
-    def oracle_container(self, seed=5):
-        """The oracle's streams in a shuffled order at unit-aligned offsets with small gaps -> (cont, starts, bytes)."""
-        unit = UNIT[self.row["fmt"]]
-        rng = np.random.default_rng(seed)
-        order = rng.permutation(self.n)
-        gaps = rng.integers(0, 4, self.n).astype(np.int64) * unit
-        starts = np.zeros(self.n, dtype=np.int64)
-        at = unit  # (not even the first stream starts on 16 bytes)
-        for k, c in enumerate(order):
-            at += int(gaps[k])
-            starts[c] = at
-            at += int(self.lens[c])
-        cont = np.zeros(at + 16, dtype=np.uint8)
-        for c in range(self.n):
-            cont[starts[c]:starts[c] + self.lens[c]] = self.streams[c]
-        return cont, starts, at
-
-    def check_encoded(self, h, what):
-        """Rows, streams and the layout of one encode (host arrays of ModelBatch.encode) against the oracle."""
-        cont, offs, lens, rows, total = h
-        assert np.array_equal(rows, self.rows), (what, "rows differ from the oracle's", np.nonzero((rows != self.rows).any(axis=1))[0][:8])
-        assert np.array_equal(lens, self.lens), (what, "lengths differ from the oracle's", np.nonzero(lens != self.lens)[0][:8])
-        ends = offs[:self.n] + lens
-        assert np.all(ends % 64 == 0), (what, "a stream does not end on a line")
-        starts = np.concatenate(([0], ends[:-1])).astype(np.uint64)  # piece c lies behind piece c - 1
-        assert np.all(offs[:self.n] >= starts) and np.all(np.diff(ends.astype(np.int64)) > 0), (what, "pieces out of order or overlapping")
-        assert int(offs[self.n]) == int(ends[-1]) == total <= self.bound, (what, "bytes in use", int(offs[self.n]), total, self.bound)
-        assert np.all(cont[total:] == POISON), (what, "written behind the bytes in use")
-        for c in range(self.n):
-            a = int(offs[c])
-            assert np.array_equal(cont[a:a + int(lens[c])], self.streams[c]), (what, "stream", c, "count", int(self.counts[c]))
-
-
-def run_row(b, align):
-    ctx, torch, row = b.ctx, b.torch, b.row
-    d_buf, sym_offs = b.laid_out(align)
-    d_sym = b.dev(sym_offs, np.int64)
-    what = "%s align %d" % (row["id"], align)
-    # 1. rows, streams, layout
-    h, (cont, offs, lens, rows, total) = b.encode(d_buf, d_sym)
-    assert ctx.last_encode_kernel()[0] == row["encode"], ctx.last_encode_kernel()
-    b.check_encoded(h, what)
-    # 2. the same layout from run to run
-    h2, _ = b.encode(d_buf, d_sym)
-    assert np.array_equal(h2[1], h[1]) and np.array_equal(h2[2], h[2]) and h2[4] == h[4], (what, "layout differs between two runs")
-    # 3. decode of the GPU's own container
-    out = torch.full_like(d_buf, POISON)
-    b.decode(cont, total, offs, lens, rows, d_sym, out)
-    assert ctx.last_decode_kernel() == row["decode"], ctx.last_decode_kernel()
-    assert torch.equal(out, d_buf), (what, "decode of the GPU's container")
-    # 4. decode of a batch the oracle made: shuffled, unit-aligned offsets with gaps, the oracle's rows
-    o_cont, o_starts, o_bytes = b.oracle_container()
-    out = torch.full_like(d_buf, POISON)
-    b.decode(b.dev(o_cont, np.uint8), o_bytes, b.dev(o_starts, np.int64), b.dev(b.lens, np.int32), b.d_rows(), d_sym, out)
-    assert ctx.last_decode_kernel() == row["decode"], ctx.last_decode_kernel()
-    assert torch.equal(out, d_buf), (what, "decode of the oracle's container")
 
 
 def with_specials(counts, ways):
@@ -350,52 +208,8 @@ def test_models_decode_order(gpu, oracle):
     assert torch.equal(outs[0], d_buf) and torch.equal(outs[1], outs[0])
 
 
-_GRAPH_SCRIPT = r"""
-import os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-import numpy as np, torch
-import bench, ryg_rans_amd as R
-from test_gpu_batch import draw_lengths, POISON
-ctx = R.Context(0)
-counts = draw_lengths(3000, 64, 61)
-sym_offs, _ = R.batch_layout(counts, R.FMT_WORD, 64, 4)
-d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
-d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
-d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda()
-cont, offs, lens, rows, total = ctx.encode_batch_adaptive(d_syms, d_sym, d_counts, 64, 12, fmt=R.FMT_WORD)
-want = torch.full_like(d_syms, POISON)
-ctx.decode_batch_adaptive(cont, total, offs, lens, rows, d_sym, d_counts, 64, 12, want, fmt=R.FMT_WORD)   # (outside the capture first)
-ref = torch.full_like(d_syms, POISON)
-for c in range(counts.size):
-    a = int(sym_offs[c]); ref[a:a + int(counts[c])] = d_syms[a:a + int(counts[c])]
-assert torch.equal(want, ref), "eager decode differs from the input"
-out = torch.full_like(d_syms, POISON)
-s = torch.cuda.Stream()
-g = torch.cuda.CUDAGraph()
-with torch.cuda.stream(s):
-    with torch.cuda.graph(g, stream=s):
-        ctx.decode_batch_adaptive(cont, total, offs, lens, rows, d_sym, d_counts, 64, 12, out, fmt=R.FMT_WORD, sync=False)
-for _ in range(3):
-    out.fill_(POISON)
-    g.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, want), "replay differs"
-assert ctx.decode_errors() == 0 and ctx.last_decode_kernel() == "k_decode_batch_models<word>"
-print("graph ok")
-"""
-
-
 @pytest.mark.gpu
 def test_models_decode_in_a_captured_graph(tmp_path):
     """One captured decode_batch_adaptive, replayed three times, in a child process under a time limit of its own.  Graph
     replay needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set below that the test does not apply."""
-    import subprocess
-    import sys
-    q = os.environ.get("GPU_MAX_HW_QUEUES")
-    if q is not None and int(q) < 4:
-        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
-    script = tmp_path / "graph_batch_models.py"
-    script.write_text(_GRAPH_SCRIPT)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    run_graph_script(tmp_path, "graph_batch_models.py", graph_decode_script("k_decode_batch_models<word>", per_stream_models=True))

@@ -1,8 +1,8 @@
 """Ragged batches of the reference's 2-way byte layout with THIRTY-TWO streams per wave: k_decode_batch_byte_pairs, the kernel
 rans_amd_decode_batch launches on a context with RANS_AMD_OPT_BATCH_PAIRS = 1.
 
-PAIR_ROWS names the kernel the library must report (tests/test_batch_pairs_host.py holds the rows to the names the
-launchers can report).  The helpers are tests/test_gpu_batch.py's: every decode is checked against the symbols the
+PAIR_ROWS (tests/_kernel_rows.py) names the kernel the library must report (tests/test_batch_pairs_host.py holds the rows to
+the names the launchers can report).  The helpers are tests/_batch.py's: every decode is checked against the symbols the
 oracle's streams were made from, from the GPU's own container and from one the oracle made (shuffled, 1-byte-aligned
 offsets, gaps), into a poison-filled buffer whose padding and guard must come back untouched.
 
@@ -11,34 +11,16 @@ times, a pair that has run out of 128-byte lines is parked (its refill check gat
 behind every line, its line not stored) and free-runs on whatever its state becomes, and what count - 128 (count >> 7)
 leaves goes one round at a time.  The shapes below are the smallest at which that can go wrong; the rate inputs (a
 frequency-1-only stream takes the ring's bound of 32 bytes per eight rounds, a common-only stream takes nothing) are
-proved to reach their bounds without a GPU by tests/test_batch_pairs_host.py, which imports the generators below."""
-import os
-from concurrent.futures import ThreadPoolExecutor
-
+tests/_batch.py's generators, proved to reach their bounds without a GPU by tests/test_batch_pairs_host.py."""
 import numpy as np
 import pytest
 
 import _stream_rate as S
+from _batch import (GUARD, POISON, POOL, RATE_BITS, RATE_WAVES, Batch, Coded, ModelBatch, PoolBatch, draw_lengths, draw_log_uniform,
+                    graph_decode_script, mandatory_lengths, rate_batch, rate_wave, resident_waves, run_graph_script, run_model_row, run_row)
+from _kernel_rows import MODEL_ROW, OPT_BATCH_GROUPS, OPT_BATCH_PAIRS, PAIR_ROWS, PMAIN, PROW, RATE_ROW, ROW
 from _oracle import FMT_BYTE
-from test_gpu_batch import GUARD, POISON, ROW, Batch, draw_lengths, mandatory_lengths, resident_waves, run_row
 
-OPT_BATCH_GROUPS = 5
-OPT_BATCH_PAIRS = 7
-
-
-def _pair_row(rid, sb, K):
-    return {"id": rid, "fmt": FMT_BYTE, "sb": sb, "K": K, "ways": 2, "decode": "k_decode_batch_byte_pairs", "encode": "k_encode_batch<byte>"}
-
-
-PAIR_ROWS = [
-    _pair_row("byte-2-pairs", 14, 256),           # the reference's scale_bits (main.cpp:139)
-    _pair_row("byte-2-pairs-16bit", 16, 256),     # 64 KiB of cum2sym: one block per CU
-    _pair_row("byte-2-pairs-12bit", 12, 256),     # (the wave kernel would take the fused slot records here)
-    _pair_row("byte-2-pairs-8bit", 8, 256),
-    _pair_row("byte-2-pairs-64sym-10bit", 10, 64),
-]
-PROW = {r["id"]: r for r in PAIR_ROWS}
-PMAIN = PROW["byte-2-pairs"]
 WAVE_KERNEL = "k_decode_batch<byte>"  # what the 14-bit and 16-bit rows report with the option off
 
 
@@ -53,38 +35,6 @@ def gpu():
     yield R, ctx, torch, off
     off.close()
     ctx.close()
-
-
-def draw_log_uniform(n_streams, max_len, seed):
-    """Log-uniform in [0, max_len]."""
-    rng = np.random.default_rng(seed)
-    return (np.exp(rng.random(n_streams) * np.log(max_len + 1.0)) - 1.0).astype(np.int64).clip(0, max_len).astype(np.uint32)
-
-
-class Coded:
-    """A batch laid out, coded by the GPU and concatenated by the oracle: what the order and damage tests decode."""
-
-    def __init__(self, b, align):
-        self.b = b
-        self.d_buf, self.sym_offs, self.slot_offs = b.laid_out(align)
-        self.d_sym, d_slot = b.dev(self.sym_offs, np.int64), b.dev(self.slot_offs, np.int64)
-        self.cont, self.offs, self.lens = b.ctx.encode_batch(b.gm, self.d_buf, self.d_sym, b.d_counts, b.row["ways"], d_slot)
-        b.ctx.encode_status()
-        o_cont, o_starts, self.o_bytes = b.oracle_container()
-        self.o_cont, self.o_offs, self.o_lens = b.dev(o_cont, np.uint8), b.dev(o_starts, np.int64), b.dev(b.lens, np.int32)
-
-    def containers(self):
-        yield "gpu", self.cont, int(self.slot_offs[-1]), self.offs, self.lens
-        yield "oracle", self.o_cont, self.o_bytes, self.o_offs, self.o_lens
-
-    def decode_all(self, d_order, what):
-        """Both containers into poison-filled buffers; each must equal the laid-out input, padding and guard included."""
-        b = self.b
-        for name, cont, nbytes, offs, lens in self.containers():
-            out = b.torch.full_like(self.d_buf, b.poison())
-            b.ctx.decode_batch(b.gm, cont, nbytes, offs, lens, self.d_sym, b.d_counts, b.row["ways"], out, d_order=d_order)
-            assert b.ctx.last_decode_kernel() == b.row["decode"], b.ctx.last_decode_kernel()
-            assert b.torch.equal(out, self.d_buf), (what, name)
 
 
 def _padded(lengths, n=32, pad=200):
@@ -123,57 +73,6 @@ def test_single_wave_loads(gpu, oracle, name, row):
         run_row(b, align)
     assert ctx.decode_errors() == 0
     assert ctx.launch_spans(1)[0] > 0.0, "the launch recorded no span"
-
-
-# ---- rate x phase x parking: the generators tests/test_batch_pairs_host.py proves things about ---------------------------
-RATE_BITS = (16, 14)
-RATE_STREAMS = 64
-RATE_COUNTS = tuple(128 * b + t for b in (0, 1, 5) for t in (0, 1, 77, 127))
-RATE_ROW = {16: PROW["byte-2-pairs-16bit"], 14: PROW["byte-2-pairs"]}
-
-
-def rate_model(sb):
-    """255 symbols of frequency 1 and one common symbol (tests/test_gpu_rate_extremes.py b_case's byte model)."""
-    freqs = np.ones(256, dtype=np.uint32)
-    freqs[S.COMMON] = (1 << sb) - 255
-    return freqs
-
-
-def rate_kind(k):
-    return "common" if k % 3 == 2 else "rare"
-
-
-def rate_count(k):
-    """Every count meets both kinds, lines in different quad positions: 12 counts against the period 3 of the kinds."""
-    return RATE_COUNTS[(5 * k + k // 12) % len(RATE_COUNTS)]
-
-
-def rate_content(freqs, kind, n, seed):
-    return S.common_only(freqs, n) if kind == "common" else S.rare_only(freqs, n, seed)
-
-
-def rate_batch(sb):
-    """-> (freqs, counts, {stream: symbols}, phases): stream k at offset == k (mod 64), every start phase of the 32-byte blocks
-    and of the 64-byte ring."""
-    freqs = rate_model(sb)
-    counts = np.array([rate_count(k) for k in range(RATE_STREAMS)], dtype=np.uint32)
-    contents = {k: rate_content(freqs, rate_kind(k), int(counts[k]), 800 + k) for k in range(RATE_STREAMS)}
-    return freqs, counts, contents, list(range(RATE_STREAMS))
-
-
-# one wave-load each: a pair at the ring's bound for 512 lines beside parked ones, and a cursor that stands still for a
-# thousand rounds and more beside pairs that drain and park one after the other
-RATE_WAVES = {
-    "fast-beside-parked": ([65536] + [255] * 31, ["rare"] + ["common"] * 31),
-    "stalled-beside-draining": ([65536] + [128 * (g % 8 + 1) for g in range(31)], ["common"] + ["rare"] * 31),
-}
-
-
-def rate_wave(sb, name):
-    freqs = rate_model(sb)
-    counts, kinds = RATE_WAVES[name]
-    contents = {k: rate_content(freqs, kinds[k], counts[k], 900 + k) for k in range(32)}
-    return freqs, np.array(counts, dtype=np.uint32), contents, [(21 * k + 5) % 64 for k in range(32)]
 
 
 def _rate_cases():
@@ -245,58 +144,6 @@ def test_order(gpu, oracle):
             assert ctx.last_decode_kernel() == PMAIN["decode"]
             assert np.array_equal(out.cpu().numpy(), want), (name, "a named stream differs, or the stream without a position was written")
     assert ctx.decode_errors() == 0
-
-
-POOL = 4096  # prototypes of the half and several batches, each coded once by the oracle
-
-
-class PoolBatch:
-    """n streams, each one of at most POOL prototypes: the oracle codes every prototype once, the batch (index, container,
-    expected output) is put together from them on the device.  The container is the oracle's -- the prototypes' streams in a
-    shuffled order at 1-byte-aligned offsets with gaps, every stream of the batch pointing at its prototype's."""
-
-    def __init__(self, R, ctx, torch, oracle, row, proto_counts, n, seed):
-        import bench
-        self.R, self.torch = R, torch
-        pc = np.ascontiguousarray(proto_counts, dtype=np.uint32)
-        p_offs = np.concatenate(([0], np.cumsum(pc.astype(np.int64))))
-        d_proto = bench.gen_zipf(torch, int(p_offs[-1]), row["K"], 1.0, 3, "cuda")
-        sample = bench.gen_zipf(torch, 1 << 20, row["K"], 1.0, 3, "cuda")
-        freqs, _ = R.normalize_freqs(ctx.count_freqs_device(sample, row["K"]), 1 << row["sb"])
-        self.gm = ctx.model(row["fmt"], freqs, row["sb"])
-        om = oracle.model(freqs, row["sb"])
-        h = d_proto.cpu().numpy()
-        with ThreadPoolExecutor(oracle.host_threads()) as ex:
-            streams = list(ex.map(lambda c: oracle.encode(row["fmt"], om, h[p_offs[c]:p_offs[c + 1]], 2), range(pc.size), chunksize=64))
-        p_lens = np.array([s.size for s in streams], dtype=np.int64)
-        rng = np.random.default_rng(seed)
-        gaps = rng.integers(0, 4, pc.size).astype(np.int64)
-        p_starts = np.zeros(pc.size, dtype=np.int64)
-        at = 1
-        for k, c in enumerate(rng.permutation(pc.size)):
-            at += int(gaps[k])
-            p_starts[c] = at
-            at += int(p_lens[c])
-        cont = np.zeros(at + 16, dtype=np.uint8)
-        for c, s in enumerate(streams):
-            cont[p_starts[c]:p_starts[c] + s.size] = s
-        self.cont, self.cont_bytes = torch.from_numpy(cont).cuda(), at
-        # the batch: the first prototypes once each (every prototype length occurs), the rest drawn
-        pick = np.concatenate((np.arange(min(pc.size, n)), rng.integers(0, pc.size, max(0, n - pc.size))))
-        pick = pick[rng.permutation(pick.size)]
-        self.counts = pc[pick]
-        self.sym_offs, self.slot_offs = R.batch_layout(self.counts, row["fmt"], 2, 4)
-
-        def dev(a, t):
-            return torch.from_numpy(np.ascontiguousarray(a).astype(t)).cuda()
-        self.d_counts, self.d_sym = dev(self.counts.view(np.int32), np.int32), dev(self.sym_offs, np.int64)
-        self.d_offs, self.d_lens = dev(p_starts[pick], np.int64), dev(p_lens[pick], np.int32)
-        self.d_slot = dev(self.slot_offs, np.int64)
-        self.d_buf = torch.full((int(self.sym_offs[-1]) + GUARD,), POISON, dtype=torch.uint8, device="cuda")
-        reps = self.d_counts.to(torch.int64)
-        total = int(reps.sum())
-        within = torch.arange(total, device="cuda") - torch.repeat_interleave(torch.cumsum(reps, 0) - reps, reps)
-        self.d_buf[torch.repeat_interleave(self.d_sym[:-1], reps) + within] = d_proto[torch.repeat_interleave(dev(p_offs[pick], np.int64), reps) + within]
 
 
 @pytest.mark.gpu
@@ -398,9 +245,6 @@ def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_
 def test_per_stream_models_keep_their_kernel_with_the_option_on(gpu, oracle):
     """decode_batch_adaptive of 40 2-way byte streams, each with its own model, on the context with the option on: the wave
     kernel with one model per stream, every stream against the oracle.  Wall time on an MI355X: 0.03 s."""
-    from test_gpu_batch_models import ROW as MODEL_ROW
-    from test_gpu_batch_models import ModelBatch
-    from test_gpu_batch_models import run_row as run_model_row
     R, ctx, torch, _ = gpu
     row = MODEL_ROW["byte-2-12bit"]
     assert row["decode"] != PMAIN["decode"]
@@ -442,60 +286,11 @@ def test_option_takes_zero_or_one(gpu, oracle):
     run_row(b, 4)
 
 
-_GRAPH_SCRIPT = r"""
-import os, sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
-import numpy as np, torch
-import bench, ryg_rans_amd as R
-from test_gpu_batch import draw_lengths, POISON
-ctx = R.Context(0)
-ctx.set_option(R.OPT_BATCH_PAIRS, 1)
-counts = draw_lengths(3000, 2, 61)
-sym_offs, slot_offs = R.batch_layout(counts, R.FMT_BYTE, 2, 4)
-d_syms = bench.gen_zipf(torch, int(sym_offs[-1]), 256, 1.0, 1, "cuda")
-freqs, _ = R.normalize_freqs(ctx.count_freqs_device(d_syms, 256), 1 << 14)
-gm = ctx.model(R.FMT_BYTE, freqs, 14)
-d_counts = torch.from_numpy(counts.view(np.int32)).cuda()
-d_sym = torch.from_numpy(sym_offs.astype(np.int64)).cuda(); d_slot = torch.from_numpy(slot_offs.astype(np.int64)).cuda()
-cont, offs, lens = ctx.encode_batch(gm, d_syms, d_sym, d_counts, 2, d_slot)
-ctx.encode_status()
-want = torch.full_like(d_syms, POISON)
-ctx.decode_batch(gm, cont, int(slot_offs[-1]), offs, lens, d_sym, d_counts, 2, want)   # (outside the capture first)
-assert ctx.last_decode_kernel() == "k_decode_batch_byte_pairs", ctx.last_decode_kernel()
-covered = torch.zeros(d_syms.numel(), dtype=torch.bool, device="cuda")
-idx = torch.repeat_interleave(d_sym[:-1], d_counts.to(torch.int64)) + (torch.arange(int(counts.sum()), device="cuda") -
-      torch.repeat_interleave(torch.cumsum(d_counts.to(torch.int64), 0) - d_counts.to(torch.int64), d_counts.to(torch.int64)))
-covered[idx] = True
-assert torch.equal(want[covered], d_syms[covered]) and bool((want[~covered] == POISON).all()), "eager decode differs from the input"
-out = torch.full_like(d_syms, POISON)
-s = torch.cuda.Stream()
-g = torch.cuda.CUDAGraph()
-with torch.cuda.stream(s):
-    with torch.cuda.graph(g, stream=s):
-        ctx.decode_batch(gm, cont, int(slot_offs[-1]), offs, lens, d_sym, d_counts, 2, out, sync=False)
-for _ in range(3):
-    out.fill_(POISON)
-    g.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, want), "replay differs"
-assert ctx.decode_errors() == 0 and ctx.last_decode_kernel() == "k_decode_batch_byte_pairs"
-print("graph ok")
-"""
-
-
 @pytest.mark.gpu
 def test_pair_batch_decode_in_a_captured_graph(tmp_path):
     """One captured decode_batch of 3000 2-way byte streams with the option on: one eager call first, then three replays, each
     equal to the eager result, in a child process under a time limit of its own.  Graph replay needs the process's default
     of four hardware queues: with GPU_MAX_HW_QUEUES set below that the test does not apply.  Wall time on an MI355X:
     2.4 s."""
-    import subprocess
-    import sys
-    q = os.environ.get("GPU_MAX_HW_QUEUES")
-    if q is not None and int(q) < 4:
-        pytest.skip("fewer than 4 hardware queues: captured graphs are not replayed here")
-    script = tmp_path / "graph_batch_pairs.py"
-    script.write_text(_GRAPH_SCRIPT)
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "graph ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    run_graph_script(tmp_path, "graph_batch_pairs.py",
+                     graph_decode_script(PMAIN["decode"], fmt="FMT_BYTE", ways=2, sb=14, option="OPT_BATCH_PAIRS"))

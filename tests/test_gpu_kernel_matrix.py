@@ -15,165 +15,21 @@ tests/_every_chunk.py: every chunk of every layout is compared with the CPU orac
 oracle made, and after every call the kernel the library reports must be the one the row names -- a change of dispatch
 that moves a shape to another kernel fails here instead of leaving a kernel without a test.
 
-test_no_kernel_without_a_row runs without a GPU: every kernel-name literal of the launchers in ryg_rans_amd/csrc/*.hip
-must appear in KERNEL_ROWS, and KERNEL_ROWS must name no kernel the sources do not contain.
+test_no_kernel_without_a_row runs without a GPU: every name of the registry's uniform family (tests/_kernel_rows.py reads
+ryg_rans_amd/csrc/kernel_names.hpp) must appear in KERNEL_ROWS, and KERNEL_ROWS must name no kernel the registry does not hold.
 """
-import glob
-import os
-import re
-
 import pytest
 
-from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(os.path.dirname(HERE), "ryg_rans_amd", "csrc")
-
-# context options (ryg_rans_amd.OPT_*; the numbers are the ABI's, tests/test_abi.py)
-LANE_FUSED, FUSED, DUAL = 1, 2, 3
-
-WAVES_PER_BLOCK = 16  # kDecBlockThreads / 64: no launcher uses a larger block
-DEFAULT_ROUNDS_SYMBOLS = 1 << 28
-REGIMES = ("U", "H", "R")
-
-
-def _row(rid, fmt, sb, K, ways, chunk, unit, decode, encode, slots, sized, opts=(), regimes=REGIMES, n=None, kind="static"):
-    return {"id": rid, "fmt": fmt, "sb": sb, "K": K, "ways": ways, "chunk": chunk, "unit": unit, "decode": decode, "encode": encode,
-            "slots": slots, "sized": sized, "opts": tuple(opts), "regimes": tuple(regimes), "n": n, "kind": kind}
-
-
-def _by(U, H, R=None):
-    """An expectation that depends on the regime (the lane encoders take their staged form from six batches per CU on)."""
-    return {"U": U, "H": H, "R": H if R is None else R}
-
-
-W, B = "k_encode<word>", "k_encode<byte>"
-WG, ST, L16, RX = "k_encode_word_groups", "k_encode_lanes_staged", "k_encode_lanes16", "k_encode_lanes_r64x2"
-
-# One table: the shape (format, scale_bits, alphabet -- u16 symbols above 256 --, interleave, chunk size, work unit in
-# chunks, context options) and the kernels the library must report for it: the decoder, and the coding kernel + placement
-# flag of the compact layout, the slot layout and sized slots.
-KERNEL_ROWS = [
-    # ---- wave per chunk (decode_wave.hip / encode_wave.hip): one chunk per unit
-    _row("word-64", FMT_WORD, 12, 256, 64, 4096, 1, "k_decode_word64", (W, 1), (W, 2), (W, 2)),
-    _row("word-128", FMT_WORD, 12, 256, 128, 8192, 1, "k_decode<word>", (W, 1), (W, 2), (W, 2)),
-    _row("word-32", FMT_WORD, 12, 256, 32, 4096, 1, "k_decode<word>", (W, 1), (W, 2), (W, 2)),
-    _row("word-64-unfused", FMT_WORD, 12, 256, 64, 4096, 1, "k_decode_word64", (W, 0), (W, 2), (W, 2), opts=((FUSED, 0),)),
-    _row("word-u16-64", FMT_WORD, 12, 1024, 64, 4096, 1, "k_decode<word, u16 symbols>", (W, 1), (W, 2), (W, 2)),
-    _row("byte-64-14bit", FMT_BYTE, 14, 256, 64, 4096, 1, "k_decode<byte>", (B, 1), (B, 2), (B, 2)),
-    _row("byte-64-12bit", FMT_BYTE, 12, 256, 64, 4096, 1, "k_decode<byte, slot records>", (B, 1), (B, 2), (B, 2)),
-    _row("r64-64", FMT_R64, 14, 256, 64, 4096, 1, "k_decode<r64>", ("k_encode<r64>", 1), ("k_encode<r64>", 2), ("k_encode<r64>", 2)),
-    _row("r64-search-64", FMT_R64, 20, 256, 64, 4096, 1, "k_decode<r64 search>", ("k_encode<r64 full-width>", 1),
-         ("k_encode<r64 full-width>", 2), ("k_encode<r64 full-width>", 2)),
-    _row("alias256-64", FMT_ALIAS, 16, 256, 64, 4096, 1, "k_decode<alias>", ("k_encode<alias, LDS remap>", 1),
-         ("k_encode<alias, LDS remap>", 2), ("k_encode<alias, LDS remap>", 2)),
-    # ---- two chunks per wave (decode_dual.hip): u16 symbols (config 4's model), and u8 symbols where the option asks for it
-    _row("alias4096-64", FMT_ALIAS, 16, 4096, 64, 4096, 1, "k_decode_dual<alias>", ("k_encode<alias, LDS remap>", 1),
-         ("k_encode<alias, LDS remap>", 2), ("k_encode<alias, LDS remap>", 2)),
-    _row("alias256-64-dual", FMT_ALIAS, 16, 256, 64, 4096, 1, "k_decode_dual<alias>", ("k_encode<alias, LDS remap>", 1),
-         ("k_encode<alias, LDS remap>", 2), ("k_encode<alias, LDS remap>", 2), opts=((DUAL, 2),)),
-    # ---- eight chunks per wave (decode_groups.hip / encode_groups.hip).  The compact layout of fewer than 64 chunks goes to the
-    #      wave encoder and its fused placement; without it (OPT_FUSED_PLACEMENT = 0) 8..63 chunks run the group encoder
-    #      WITHOUT claim counters (ADVICE r06, second finding): regime U of the second row is that shape (12 chunks)
-    _row("word-8", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode_word_groups", _by((W, 1), (WG, 0)), (WG, 2), (WG, 2)),
-    _row("word-8-unfused", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode_word_groups", (WG, 0), (WG, 2), (WG, 2), opts=((FUSED, 0),)),
-    # ---- 32 chunks per wave (k_decode_byte_pairs); its encoders are the lane encoders, staged from six batches per CU on
-    _row("byte-2", FMT_BYTE, 14, 256, 2, 256, 32, "k_decode_byte_pairs", _by((B, 1), (ST, 0)), _by((B, 2), (ST, 2)), _by((B, 2), (ST, 2))),
-    _row("byte-2-lane-fused", FMT_BYTE, 14, 256, 2, 256, 32, "k_decode_byte_pairs", _by((B, 1), (ST, 1)), _by((B, 2), (ST, 2)),
-         _by((B, 2), (ST, 2)), opts=((LANE_FUSED, 1),)),
-    # ---- one chunk per lane (decode_lanes.hip, encode_lanes.hip): 64 chunks per unit
-    _row("r64-2-packed", FMT_R64, 14, 256, 2, 128, 64, "k_decode_lanes_r64x2<packed slots>", _by((L16, 0), (RX, 0)),
-         _by((L16, 2), (RX, 2)), _by(("k_encode<r64>", 2), (RX, 2))),
-    _row("r64-2-16bit", FMT_R64, 16, 256, 2, 128, 64, "k_decode_lanes_r64x2", _by((L16, 0), (RX, 0)), _by((L16, 2), (RX, 2)),
-         _by(("k_encode<r64>", 2), (RX, 2))),
-    _row("r64-2-lane-fused", FMT_R64, 14, 256, 2, 128, 64, "k_decode_lanes_r64x2<packed slots>", _by((L16, 0), (RX, 1)),
-         _by((L16, 2), (RX, 2)), _by(("k_encode<r64>", 2), (RX, 2)), opts=((LANE_FUSED, 1),)),
-    _row("word-4", FMT_WORD, 12, 256, 4, 128, 64, "k_decode_lanes_staged", _by((L16, 0), (ST, 0)), _by((L16, 2), (ST, 2)),
-         _by((W, 2), (ST, 2))),
-    _row("byte-1", FMT_BYTE, 14, 256, 1, 128, 64, "k_decode_lanes_staged", _by((L16, 0), (ST, 0)), _by((L16, 2), (ST, 2)),
-         _by((B, 2), (ST, 2))),
-    _row("alias256-8", FMT_ALIAS, 16, 256, 8, 128, 64, "k_decode_lanes_staged", _by((L16, 0), (ST, 0)), _by((L16, 2), (ST, 2)),
-         _by(("k_encode<alias, LDS remap>", 2), (ST, 2))),
-    # (chunks that are no multiple of 4 symbols: not the group kernels'; no multiple of 16: the per-lane encoder at every size,
-    #  and sized slots, which it cannot take, go to the wave encoder)
-    _row("word-8-chunk-130", FMT_WORD, 12, 256, 8, 130, 64, "k_decode_lanes_staged", (L16, 0), (L16, 2), (W, 2)),
-    # (the per-lane decoder is the fallback for chunks of 512 Ki symbols and more: a wave holds 64 of them, 32 Mi symbols --
-    #  "half the resident waves" would be 2^36 symbols, so this row has regime U alone)
-    _row("byte-2-huge-chunks", FMT_BYTE, 14, 256, 2, (1 << 19) + 2, 64, "k_decode_lanes", (L16, 0), (L16, 2), (B, 2), regimes=("U",)),
-    # ---- one model per chunk (decode_wave.hip, encode_wave.hip, encode_adaptive.hip): Oracle.compare_container_adaptive
-    _row("byte-64-per-chunk-models", FMT_BYTE, 12, 256, 64, 4096, 1, "k_decode<byte, per-chunk models>", "k_encode<byte, per-chunk models>",
-         None, "k_encode_adaptive<byte>", kind="adaptive"),
-    _row("word-64-per-chunk-models", FMT_WORD, 12, 256, 64, 4096, 1, "k_decode<word, per-chunk models>", "k_encode<word, per-chunk models>",
-         None, "k_encode_adaptive<word>", kind="adaptive"),
-    # ---- either side of every applicability threshold of the group kernels (fixed sizes; chunks this small have no sized
-    #      slot below the worst case, so the sized steps are left out).  Word groups: chunks of 32 symbols and more ...
-    _row("word-8-chunk-28", FMT_WORD, 12, 256, 8, 28, 8, "k_decode_lanes_staged", (L16, 0), (L16, 2), None, regimes=("F",), n=28 * 1000 + 9),
-    _row("word-8-chunk-32", FMT_WORD, 12, 256, 8, 32, 8, "k_decode_word_groups", (WG, 0), (WG, 2), None, regimes=("F",), n=32 * 1000 + 9),
-    _row("word-8-chunk-36", FMT_WORD, 12, 256, 8, 36, 8, "k_decode_word_groups", (WG, 0), (WG, 2), None, regimes=("F",), n=36 * 1000 + 9),
-    # ... and eight full chunks and more (with and without the fused placement of the wave encoder that takes fewer than 64)
-    _row("word-8-7-chunks", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode<word>", (W, 1), (W, 2), None, regimes=("F",), n=7 * 1024),
-    _row("word-8-8-chunks", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode_word_groups", (W, 1), (WG, 2), None, regimes=("F",), n=8 * 1024),
-    _row("word-8-9-chunks", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode_word_groups", (W, 1), (WG, 2), None, regimes=("F",), n=9 * 1024),
-    _row("word-8-7-chunks-unfused", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode<word>", (W, 0), (W, 2), None, opts=((FUSED, 0),),
-         regimes=("F",), n=7 * 1024),
-    _row("word-8-8-chunks-unfused", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode_word_groups", (WG, 0), (WG, 2), None, opts=((FUSED, 0),),
-         regimes=("F",), n=8 * 1024),
-    _row("word-8-63-chunks-unfused", FMT_WORD, 12, 256, 8, 1024, 8, "k_decode_word_groups", (WG, 0), (WG, 2), None, opts=((FUSED, 0),),
-         regimes=("F",), n=63 * 1024),
-    # byte pairs: chunks of 64 symbols and more ...
-    _row("byte-2-chunk-60", FMT_BYTE, 14, 256, 2, 60, 32, "k_decode_lanes_staged", (L16, 0), (L16, 2), None, regimes=("F",), n=60 * 1000 + 9),
-    _row("byte-2-chunk-64", FMT_BYTE, 14, 256, 2, 64, 32, "k_decode_byte_pairs", (L16, 0), (L16, 2), None, regimes=("F",), n=64 * 1000 + 9),
-    _row("byte-2-chunk-68", FMT_BYTE, 14, 256, 2, 68, 32, "k_decode_byte_pairs", (L16, 0), (L16, 2), None, regimes=("F",), n=68 * 1000 + 9),
-    # ... and 32 full chunks and more
-    _row("byte-2-31-chunks", FMT_BYTE, 14, 256, 2, 256, 32, "k_decode<byte>", (B, 1), (B, 2), None, regimes=("F",), n=31 * 256),
-    _row("byte-2-32-chunks", FMT_BYTE, 14, 256, 2, 256, 32, "k_decode_byte_pairs", (B, 1), (B, 2), None, regimes=("F",), n=32 * 256),
-    _row("byte-2-33-chunks", FMT_BYTE, 14, 256, 2, 256, 32, "k_decode_byte_pairs", (B, 1), (B, 2), None, regimes=("F",), n=33 * 256),
-]
-
-
-def pick(value, regime):
-    return value.get(regime) if isinstance(value, dict) else value
-
-
-def row_kernel_names(rows=None):
-    """Every kernel name KERNEL_ROWS expects, in any regime."""
-    names = set()
-    for r in KERNEL_ROWS if rows is None else rows:
-        for key in ("decode", "encode", "slots", "sized"):
-            v = r[key]
-            for w in (v.values() if isinstance(v, dict) else (v,)):
-                if w is not None:
-                    names.add(w if isinstance(w, str) else w[0])
-    return names
-
-
-_LITERAL = re.compile(r'"((?:[^"\\]|\\.)*)"')
-
-
-def source_kernel_names(csrc=CSRC):
-    """The kernel-name literals of the launchers: every string literal of a statement `*name = ...;` (a ternary chain has one
-    per arm), and the literal passed as `kname` at every call of launch_dual_t (decode_dual.hip assigns `*name = kname`).
-    Returns (names, number of assignment statements)."""
-    names, sites = set(), 0
-    for path in sorted(glob.glob(os.path.join(csrc, "*.hip"))):
-        text = open(path).read()
-        for m in re.finditer(r"\*name\s*=\s*([^;]*);", text):
-            sites += 1
-            names.update(_LITERAL.findall(m.group(1)))
-        for m in re.finditer(r"\blaunch_dual_t<[^;(]*>\(([^;]*)\);", text):
-            lits = _LITERAL.findall(m.group(1))
-            assert lits, (path, m.group(0))  # (a caller that passes no literal: this extraction must learn its form)
-            names.update(lits)
-    return names, sites
+from _batch import resident_waves
+from _kernel_rows import KERNEL_ROWS, UNIFORM, pick, regime_symbols, registry, row_kernel_names
 
 
 def test_no_kernel_without_a_row():
-    """Runs without a GPU.  All 13 statements that assign `*name` in ryg_rans_amd/csrc/*.hip are found -- the seven arms of
-    encode_wave.hip's chain, the ten of decode_wave.hip's (k_decode_word64 is its first), every caller of launch_dual_t -- and the
-    set of names they can report equals the set KERNEL_ROWS expects: a new kernel needs a row, and a row cannot name a kernel
-    that is gone."""
-    names, sites = source_kernel_names()
-    assert sites >= 13, sites
+    """Runs without a GPU.  The set of names the uniform launchers can report -- the registry's uniform family -- equals the set
+    KERNEL_ROWS expects: a new kernel needs a row, and a row cannot name a kernel that is gone.  (A count of the assignment
+    statements and a special case for launch_dual_t's argument once guarded the completeness of a scan of the sources; the
+    launchers now report a KernelId, and a name outside the registry does not compile.)"""
+    names = registry()[UNIFORM]
     for must in ("k_encode<word>", "k_encode<byte>", "k_encode<byte, per-chunk models>", "k_encode<word, per-chunk models>", "k_encode<r64>",
                  "k_encode<r64 full-width>", "k_encode<alias, LDS remap>", "k_decode_dual<alias>", "k_decode<word, u16 symbols>",
                  "k_decode_lanes_r64x2<packed slots>", "k_decode_lanes_r64x2", "k_encode_adaptive<word>", "k_encode_adaptive<byte>"):
@@ -198,26 +54,6 @@ def gpu():
     ctx = R.Context(0)
     yield R, ctx, torch
     ctx.close()
-
-
-def resident_waves(torch):
-    return torch.cuda.get_device_properties(0).multi_processor_count * 2 * WAVES_PER_BLOCK
-
-
-def regime_symbols(row, regime, resident):
-    """-> (n, whole units before the partial one)"""
-    chunk, unit = row["chunk"], row["unit"]
-    ragged = chunk // 3 + 1
-    if regime == "F":
-        return row["n"], row["n"] // (chunk * unit)
-    if regime == "U":
-        units = 1
-    elif regime == "H":
-        units = resident // 2
-    else:
-        per_unit = chunk * unit
-        units = max(4 * resident, (DEFAULT_ROUNDS_SYMBOLS + per_unit - 1) // per_unit)
-    return (units * unit + unit // 2) * chunk + ragged, units
 
 
 def _cases():
@@ -266,7 +102,7 @@ def test_counter_ring_two_wraps_on_a_fresh_context(oracle):
     decode rows of the matrix at their "part of one round" size in a FIXED order (launch i runs item i % items: a failure
     names its position in the ring).  The three decode entry points share the one ring, so the cycle holds all of them:
     the static rows through ctx.decode, the two per-chunk-model rows through ctx.decode_adaptive, and one ragged batch
-    (tests/test_gpu_batch.py's Batch) through ctx.decode_batch.  Launch i claims from counter slot i % 64 and re-zeroes slot
+    (tests/_batch.py's Batch) through ctx.decode_batch.  Launch i claims from counter slot i % 64 and re-zeroes slot
     (i + 32) % 64 for the launch 32 calls later (api.cpp take_counter_slot): a kernel family or an entry point that forgot
     would leave a used counter to a launch of ANOTHER one.  Every launch has its own pre-poisoned output; afterwards every
     output == its input and decode_errors() == 0.
@@ -277,7 +113,8 @@ def test_counter_ring_two_wraps_on_a_fresh_context(oracle):
     assert torch.cuda.is_available(), "these tests need the GPU box"
     import bench
     import ryg_rans_amd as R
-    from test_gpu_batch import ROW as BATCH_ROW, Batch, draw_lengths
+    from _batch import Batch, draw_lengths
+    from _kernel_rows import ROW as BATCH_ROW
     resident = resident_waves(torch)
     rows = [r for r in KERNEL_ROWS if "H" in r["regimes"] and not r["opts"]]
     assert len({pick(r["decode"], "H") for r in rows if r["kind"] == "static"}) >= 10

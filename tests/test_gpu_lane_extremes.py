@@ -49,8 +49,8 @@ import numpy as np
 import pytest
 
 import _stream_rate as S
+from _batch import GUARD, POISON
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
-from test_gpu_batch import GUARD, POISON
 
 OPT_LANE_FUSED_PLACEMENT = 1  # (ryg_rans_amd.OPT_LANE_FUSED_PLACEMENT; the number is the ABI's, tests/test_abi.py)
 

@@ -19,7 +19,7 @@ lengths are the oracle's, the window of a piece is need_model's from the oracle'
              registers) and 128 ways (the same sizes in trips of 4096)
   section c  the piece a chunk gets: need[c] = end of piece c - end of piece c - 1, a multiple of 64 inside need_model's
              window, the stream at its top, pieces in index order, the same container on a second call
-  section d  ragged batches (tests/test_gpu_batch_models.py ModelBatch / run_row): the classes at the sizes of section b,
+  section d  ragged batches (tests/_batch.py ModelBatch / run_model_row): the classes at the sizes of section b,
              neighbours at different alignments (sym_align 1 and 16), an empty stream between two dom_* streams; rows, streams,
              kernel names, exact decode into poison; the window of section c with the ragged cap
   section e  adapt_build_dec alone: the oracle's containers and rows, decode_adaptive at 64 and 2 ways and
@@ -56,8 +56,8 @@ import numpy as np
 import pytest
 
 import _model_extremes as X
+from _batch import GUARD, POISON
 from _oracle import FMT_BYTE, FMT_WORD
-from test_gpu_batch import GUARD, POISON
 
 FORMATS = {"word-12": (FMT_WORD, 12), "byte-12": (FMT_BYTE, 12), "byte-8": (FMT_BYTE, 8)}
 CHUNKS, OTHER_WAYS = X.CHUNKS, X.OTHER_WAYS
@@ -243,7 +243,7 @@ def test_piece_sizes_inside_the_window(gpu, oracle, fid, chunk):
 
 # ---- section d ----------------------------------------------------------------------------------------------------------
 def _batch_cases():
-    from test_gpu_batch_models import MODEL_ROWS
+    from _kernel_rows import MODEL_ROWS
     for row in MODEL_ROWS:
         yield pytest.param(row, id=row["id"], marks=pytest.mark.gpu)
 
@@ -251,7 +251,8 @@ def _batch_cases():
 @pytest.mark.parametrize("row", list(_batch_cases()))
 def test_ragged_batches_of_the_classes(gpu, oracle, row):
     """Section d."""
-    from test_gpu_batch_models import ModelBatch, run_row
+    from _batch import ModelBatch
+    from _batch import run_model_row as run_row
     R, ctx, torch = gpu
     fmt, sb, ways = row["fmt"], row["sb"], row["ways"]
     plan = X.batch_plan()

@@ -22,9 +22,9 @@ import numpy as np
 import pytest
 
 import _stream_rate as S
+from _batch import GUARD, POISON, Batch, mandatory_lengths, run_row
+from _kernel_rows import BATCH_ROWS, GROUP_ROWS, GROW, OPT_BATCH_GROUPS
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
-from test_gpu_batch import BATCH_ROWS, GUARD, POISON, Batch, mandatory_lengths, run_row
-from test_gpu_batch_groups import GROUP_ROWS, GROW, OPT_BATCH_GROUPS
 
 # ---- section a: k_decode_batch_word_groups, rate x phase x parking --------------------------------------------------
 A_MODELS = {"3826-16-254x1": S.rate_model_16, "4065-16-15x1": S.quiet_model}

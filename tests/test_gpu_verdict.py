@@ -52,8 +52,8 @@ import numpy as np
 import pytest
 
 import _verdict as V
+from _batch import resident_waves
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
-from test_gpu_kernel_matrix import resident_waves
 
 pytestmark = pytest.mark.gpu
 

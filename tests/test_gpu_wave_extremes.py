@@ -64,8 +64,8 @@ import numpy as np
 import pytest
 
 import _stream_rate as S
+from _batch import GUARD, POISON
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
-from test_gpu_batch import GUARD, POISON
 
 OPT_FUSED_PLACEMENT, OPT_DUAL_DECODE = 2, 3  # (ryg_rans_amd.OPT_*; the numbers are the ABI's, tests/test_abi.py)
 
@@ -539,7 +539,7 @@ def test_steered_cursor_at_the_mark(gpu, oracle, rid):
 
 # ---- section c ----------------------------------------------------------------------------------------------------------
 def resident_waves(torch):
-    from test_gpu_kernel_matrix import resident_waves as rw
+    from _batch import resident_waves as rw
     return rw(torch)
 
 
@@ -584,10 +584,11 @@ def test_word64_hand_over_ladder(gpu, oracle, g):
 @pytest.mark.gpu
 def test_word64_hand_over_ladder_in_one_batch(gpu, oracle):
     """Section c, the batch form (k_decode_batch_word64): the streams' lengths walk an Euler circuit over the ladder's path
-    lengths, so one launch hands over between every ordered pair of them; kinds in turn by stream.  tests/test_gpu_batch.py's
+    lengths, so one launch hands over between every ordered pair of them; kinds in turn by stream.  tests/_batch.py's
     run_row (encode_batch against the oracle, decode_batch of the GPU's and of the oracle's shuffled container, laid-out
     input with poison between the streams and a guard) at sym_align 4 and 1, then the phase-packed container."""
-    from test_gpu_batch import ROW as BATCH_ROW, Batch, run_row
+    from _batch import Batch, run_row
+    from _kernel_rows import ROW as BATCH_ROW
     R, ctx, torch, _ = gpu
     row = ROW["word-64-rate"]
     brow = BATCH_ROW["word-64"]

@@ -159,7 +159,8 @@ def test_ragged_batch_unchanged(shared, oracle):
     """k_decode_batch_word64 (the same source, its ragged instantiation: untouched by anything done to the uniform one) on 2000
     streams with log-uniform lengths in [0, 64 Ki], from a container the oracle made, at odd and at dword-aligned output
     offsets."""
-    from test_gpu_batch import ROW, Batch, draw_lengths
+    from _batch import Batch, draw_lengths
+    from _kernel_rows import ROW
     R, ctx, torch = shared.R, shared.ctx, shared.torch
     b = Batch(R, ctx, torch, oracle, ROW["word-64"], draw_lengths(2000, 64, 31))
     o_cont, o_starts, o_bytes = b.oracle_container()

@@ -15,8 +15,6 @@
   * bursts: a silent group and a group at the maximum in one chunk, wherever `lead` puts the runs;
   * coverage: LANE_CASES names every kernel the lane launchers can report under a rare-only, a common-only and a mixed
     wave, the patterns put every kind at every lane position of a quad, and the phases cover every offset."""
-import os
-
 import numpy as np
 import pytest
 
@@ -198,12 +196,11 @@ def test_wrap_chunk_is_the_smallest_that_wraps_the_ring(oracle):
 
 
 # ---- what the GPU file covers -------------------------------------------------------------------------------------------
-def lane_source_kernel_names():
-    """The kernel-name literals of decode_lanes.hip and encode_lanes.hip: tests/test_gpu_kernel_matrix.py's extraction,
-    restricted to the names those two files hold."""
-    from test_gpu_kernel_matrix import CSRC, source_kernel_names
-    text = "".join(open(os.path.join(CSRC, f)).read() for f in ("decode_lanes.hip", "encode_lanes.hip"))
-    return {n for n in source_kernel_names()[0] if '"%s"' % n in text}
+def lane_kernel_names():
+    """The names of decode_lanes.hip's and encode_lanes.hip's kernels: those of the registry's uniform family
+    (tests/_kernel_rows.py) that say `_lanes`."""
+    from _kernel_rows import UNIFORM, registry
+    return {n for n in registry()[UNIFORM] if "_lanes" in n}
 
 
 def test_no_lane_kernel_without_an_extreme_case():
@@ -211,7 +208,7 @@ def test_no_lane_kernel_without_an_extreme_case():
     mixed wave: a later lane kernel needs a case.  (k_encode_lanes_r64x2 is two instantiations under one name: the models of
     255 x 1 and one common symbol have a record for every byte value and run the one without TRACK, every class of section c
     that has symbols without a record runs the other.)"""
-    need = lane_source_kernel_names()
+    need = lane_kernel_names()
     assert need == {G.D_ST, G.D_RX, G.D_RXP, G.D_L, G.E_ST, G.E_RX, G.E_L16}, sorted(need)
     for inp in G.ALL_INPUTS:
         have = G.kernels_under(inp)

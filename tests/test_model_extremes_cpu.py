@@ -175,7 +175,7 @@ def test_the_factor_is_visible_in_the_plans(capsys):
     """need_floor on the very pieces the GPU tests look at (class_plan: uniform calls; batch_plan: ragged batches): never above
     hi, below lo nowhere, and above lo -- a whole line -- on at least one piece of every ragged batch (FACTOR_SIZES): there a
     kernel without the 1 + 2^-12 factor, which returns lo, is caught."""
-    from test_gpu_batch_models import MODEL_ROWS
+    from _kernel_rows import MODEL_ROWS
     calls = [("uniform %d" % chunk, fmt, sb, ways, False, chunk, X.class_plan(chunk)) for fmt, sb in FORMATS for chunk in X.CHUNKS
              for ways in (64, X.OTHER_WAYS[chunk])]
     calls += [("ragged " + r["id"], r["fmt"], r["sb"], r["ways"], True, None, X.batch_plan()) for r in MODEL_ROWS]

@@ -196,14 +196,11 @@ def test_section_a_meets_every_combination():
 
 
 def test_no_batch_kernel_without_a_rate_case():
-    """Every kernel name a batch launcher can report (the `*batch_kernel = ...;` and `*group_batch_kernel = ...;` literals of
-    csrc/*.hip), every name of BATCH_ROWS and GROUP_ROWS, and the two uniform ring decoders are asserted by a case of
+    """Every kernel name a batch launcher can report (the registry's batch and batch_word_groups_decode families,
+    tests/_kernel_rows.py), every name of BATCH_ROWS and GROUP_ROWS, and the two uniform ring decoders are asserted by a case of
     RATE_CASES under a rare-only and under a common-only stream: a later batch kernel needs a rate-extreme case."""
-    from test_batch_groups_host import source_group_batch_kernel_names
-    from test_batch_host import row_batch_kernel_names, source_batch_kernel_names
-    from test_gpu_batch import BATCH_ROWS
-    from test_gpu_batch_groups import GROUP_ROWS
-    need = source_batch_kernel_names()[0] | source_group_batch_kernel_names()[0]
+    from _kernel_rows import BATCH, BATCH_ROWS, BATCH_WORD_GROUPS_DECODE, GROUP_ROWS, registry, row_batch_kernel_names
+    need = registry()[BATCH] | registry()[BATCH_WORD_GROUPS_DECODE]
     need |= row_batch_kernel_names(BATCH_ROWS) | row_batch_kernel_names(GROUP_ROWS)
     need |= {"k_decode_word_groups", "k_decode_byte_pairs"}
     assert len(need) >= 16, sorted(need)

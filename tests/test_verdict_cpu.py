@@ -16,7 +16,7 @@ import pytest
 
 import _verdict as V
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_NAMES, FMT_R64, FMT_WORD
-from test_gpu_kernel_matrix import KERNEL_ROWS, pick, source_kernel_names
+from _kernel_rows import KERNEL_ROWS, UNIFORM, pick, registry
 
 ROWS = V.VERDICT_ROWS
 ROW_IDS = [r["id"] for r in ROWS]
@@ -165,11 +165,10 @@ def test_start_phases_of_the_slot_layout(oracle):
 
 
 def test_no_chunked_decoder_without_a_verdict_row():
-    """Every kernel name rans_amd_decode / rans_amd_decode_adaptive[_fmt] can report (the `*name = ...` literals of the
-    launchers that start with k_decode; the ragged-batch launchers report theirs through another pointer and have damage tests
-    of their own) has a row in VERDICT_ROWS, the rows name no kernel that is gone, and every decoder of KERNEL_ROWS is there."""
-    names, sites = source_kernel_names()
-    decoders = {n for n in names if n.startswith("k_decode")}
+    """Every kernel name rans_amd_decode / rans_amd_decode_adaptive[_fmt] can report (the names of the registry's uniform
+    family, tests/_kernel_rows.py, that start with k_decode; the ragged-batch kernels are families of their own and have damage
+    tests of their own) has a row in VERDICT_ROWS, the rows name no kernel that is gone, and every decoder of KERNEL_ROWS is there."""
+    decoders = {n for n in registry()[UNIFORM] if n.startswith("k_decode")}
     assert len(decoders) >= 17 and not any("batch" in n for n in decoders), sorted(decoders)
     have = {r["kernel"] for r in ROWS}
     assert not decoders - have, ("decoder kernels without a verdict row", sorted(decoders - have))

@@ -285,7 +285,7 @@ def test_no_wave_kernel_without_an_extreme_case():
     per-chunk-model kernels -- is asserted by a case of WAVE_CASES under a rare-only, a common-only and a mixed input: a new
     wave kernel needs a row in the matrix (tests/test_gpu_kernel_matrix.py test_no_kernel_without_a_row) and then fails here
     until it has an extreme case."""
-    from test_gpu_kernel_matrix import KERNEL_ROWS, row_kernel_names
+    from _kernel_rows import KERNEL_ROWS, row_kernel_names
     need = row_kernel_names([r for r in KERNEL_ROWS if r["unit"] == 1])
     assert {G.D_W64, G.D_W, G.D_W16, G.D_B, G.D_BF, G.D_R, G.D_RS, G.D_A, G.D_DUAL, G.D_WA, G.D_BA, G.E_W, G.E_B, G.E_R, G.E_RF, G.E_A, G.E_WA,
             G.E_BA, G.E_WAD, G.E_BAD} == need, sorted(need)
