@@ -25,6 +25,7 @@ OPT_LANE_KERNELS, OPT_LANE_FUSED_PLACEMENT, OPT_FUSED_PLACEMENT, OPT_DUAL_DECODE
 OPT_BATCH_ENCODE_GROUPS = 6
 OPT_BATCH_PAIRS = 7
 OPT_BATCH_ENCODE_PAIRS = 8
+OPT_BATCH_LANES = 9
 
 OK, E_ARG, E_MODEL, E_SPACE, E_CORRUPT, E_UNSUPPORTED, E_HIP, E_NOMEM = range(8)
 

@@ -678,6 +678,11 @@ int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value)
             return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_ENCODE_PAIRS takes 0 (one stream per wave) or 1 (thirty-two 2-way byte streams per wave)");
         ctx->variant = value ? (ctx->variant | kVarBatchEncPairs) : (ctx->variant & ~kVarBatchEncPairs);
         return RANS_AMD_OK;
+    case RANS_AMD_OPT_BATCH_LANES:
+        if (value != 0 && value != 1)
+            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_LANES takes 0 (one stream per wave) or 1 (sixty-four 2-way rans64 streams per wave)");
+        ctx->variant = value ? (ctx->variant | kVarBatchLanes) : (ctx->variant & ~kVarBatchLanes);
+        return RANS_AMD_OK;
     default:
         return fail(RANS_AMD_E_ARG, "set_option: unknown option");
     }
@@ -1490,6 +1495,9 @@ int rans_amd_decode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
         const bool pairs = (ctx->variant & kVarBatchPairs) && dec_format == RANS_AMD_FMT_BYTE && decode_batch_byte_pairs_applicable(dp);
         if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12 && !pairs)
             dec_format = use_byte_fused_tables(dp, model);
+        // (rans64, RANS_AMD_OPT_BATCH_LANES: the 64-streams-per-wave kernel reads the cum2sym tables filled in above; whether they
+        // and a wave's rings fit the CU's LDS is decode_batch_r64_lanes_applicable's question, asked by launch_decode_batch, and
+        // the block is sized from what they leave by its launcher)
         RC_TRY(launch_decoder(ctx, capture, s, launch_decode_batch, dec_format, dp));
     }
     if (h_bad_streams)

@@ -1,6 +1,7 @@
 // decode_lanes.hip -- lane-per-stream decoders for narrow interleaves (N = 1, 2, 4, 8), all generations.
 
 #include "lanes_common.hpp"
+#include "groups_common.hpp" // the ragged kernel's prologue, work hand-out and span record
 
 namespace rans_amd {
 
@@ -873,6 +874,272 @@ template <bool PACKED> __global__ void __launch_bounds__(1024) k_decode_lanes_r6
 }
 #undef R64_BOUNDARY
 
+// ---------------------------------------------------------------------------
+// k_decode_batch_r64_lanes -- the ragged form of k_decode_lanes_r64x2 (rans_amd_decode_batch under
+// RANS_AMD_OPT_BATCH_LANES): a wave's sixty-four lanes hold sixty-four STREAMS of the reference's 2-way rans64 layout
+// (main64.cpp:224-287), each with its own symbol count, output address, stream offset and length.  The unit of work is
+// one wave-load of the hand-out order, claimed through the work counter: lane l of claim k holds stream
+// order[64 k + l] -- 64 k + l without an order; a position at or past nchunks has no stream.  The rings (128 bytes +
+// mirror per lane, rows 136 bytes apart), the quad fetches through the wave's buffer window, the commit of the parked
+// pieces, the pair of symbols and the group of sixteen are k_decode_lanes_r64x2's, macro for macro; the ring's invariant
+// is its invariant (>= 48 bytes ahead at a group boundary, the side path for a lane below that).  What is new:
+//   * ONE TRIP (64 symbols) is one asm statement, not the whole loop: the wave runs it max_l(count_l >> 6) times, and
+//     between two trips nothing is in flight (the trip ends with the commit of the pieces its last group asked for), so
+//     the compiler's code between them sees plain registers.  That costs the uniform kernel's overlap of a trip's stores
+//     and last fetch with the next trip's first group; other waves of the SIMD cover it.
+//   * a lane whose stream has run out of whole trips -- or that has no stream -- is PARKED: the statement runs under full
+//     exec (its DPP moves read the quad's other lanes), so the lane free-runs on whatever its state becomes.  That reads
+//     LDS only: cum2sym at x & mask, inside table 0; a record at table 1 + 8 s with s a byte of cum2sym, a symbol of
+//     the model; its own ring row at (cursor & 127) and the mirror dword behind it.  It requests no line: for the trip
+//     its "next line" is put 2^29 bytes ahead of its cursor, so neither the fetch's test (<= 64 ahead) nor the side
+//     path's (< 48 ahead) sees it, and a quad fetches for a member only what that member asked for.  Behind the trip its
+//     states, window, cursor and next line are put back from copies: its ring holds what it held, its tail reads the
+//     right bytes.  Its 64 bytes are not stored.
+//   * stores: a lane whose output is 64-byte aligned has its line written by its quad (transpose, then instruction t
+//     writes the line of the quad's lane t under "this trip < the trips of lane t": the uniform kernel's vq masks, per
+//     trip); a lane on the 4-byte grid writes its own four 16-byte pieces, any other lane 64 bytes one by one -- before
+//     the transpose, from its own registers.  rans_amd_batch_layout with sym_align = 64 is the fast layout.
+//   * the tail: count & 63 symbols in groups of sixteen, compiler-scheduled, a pair at a time and the odd last symbol on
+//     state 0 (main64.cpp's loops: i < (n & ~1) in pairs, then rans0); every group follows a fetch + commit of its own
+//     (synchronous, the side path's), so it never relies on a line a parked lane did not request.  Byte stores.
+//   * the window: a buffer resource at the line of the wave-load's lowest stream, lanes 2^30 bytes and more beyond it wait
+//     for another pass over the same claim (`again`), as in the uniform kernel; reads behind the container's last 16-byte
+//     granule return 0.  Ring positions are 32-bit: a stream longer than 2^30 bytes is counted as failed here.
+// Index entries are the caller's data: the order entry names a stream, the offset is on the 4-byte grid, the stream holds
+// its two states and lies inside the container, the symbol range lies inside [0, out_syms) -- a stream that fails any of
+// these is counted once, nothing of it is fetched, nothing stored.  Behind the last symbol both states are 2^31 and the
+// cursor stands at the stream's end, else the stream is counted.
+// ---------------------------------------------------------------------------
+#define R64B_BOUNDARY(N)                                                                                                \
+    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
+    "v_cmp_gt_i32 vcc, 48, v46\n\t"                                                                                     \
+    "s_cbranch_vccz .Lr64bok" N "_%=\n\t"                                                                               \
+    R64_FETCH R64_COMMIT                                                                                                \
+    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
+    ".Lr64bok" N "_%=:\n\t" R64_FETCH
+// (R64_CLOBBERS without the sixteen output registers, which are operands here, and without s50)
+#define R64B_CLOBBERS                                                                                                   \
+    "vcc", "scc", "memory", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", \
+        "v38", "v39", "v46", "v47", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", \
+        "v61", "v62", "v63", "v64", "v65", "v66", "v67", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", \
+        "s46", "s47"
+typedef uint32_t lanes_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes on the 4-byte grid
+
+__global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const unsigned long long t_start = p.span ? wall_clock64() : 0ull;
+    const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // cum2sym u8[M]
+    const uint32_t t1_bytes = (p.table1_bytes + 15u) & ~15u; // {freq, start}[nsyms]
+    stage_table(smem, p.table0, t0_bytes);
+    stage_table(smem + t0_bytes, p.table1, t1_bytes);
+    __syncthreads();
+    if (!lds_starts_at_zero(smem)) { // the asm addresses LDS by raw offsets
+        if (threadIdx.x == 0)
+            atomicAdd(p.err_count, 1ull << 32);
+        return;
+    }
+    reset_for_next_launch(p);
+    DecTables<FMT_R64> T; // the tail's compiler-scheduled steps
+    T.init(smem, smem + t0_bytes, p.scale_bits, p.log2nsyms);
+
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t row = t0_bytes + t1_bytes + wave * kR64WaveLds + lane * kR64RingStride; // LDS byte offset
+    const uint32_t m = lane & 3u;
+    const uint32_t rq0 = row - m * kR64RingStride + m * 16u; // piece m in the row of the quad's lane 0
+    const uint32_t l16 = m * 16u;
+    const uint8_t *rowp = smem + row;
+    uint32_t maskv = (1u << p.scale_bits) - 1u, sbv = p.scale_bits, t1v = t0_bytes;
+    asm volatile("v_mov_b32 %0, %0" : "+v"(maskv)); // VGPR copies: a VALU op with an SGPR operand issues slower
+    asm volatile("v_mov_b32 %0, %0" : "+v"(sbv));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(t1v));
+    const uint64_t kL = 1ull << 31;
+    const uint64_t m0 = 0x1111111111111111ull; // lane 0 of every quad
+    constexpr uint32_t kParkAhead = 1u << 29;  // a lane that must not ask: its next line this far ahead of its cursor
+
+    const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
+    const uint64_t cbytes16 = (p.container_bytes + 15u) & ~uint64_t(15);
+    const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 63u) >> 6); // wave-loads, one per claim; stream indices are 32-bit
+    uint32_t nbad = 0;
+    WorkClaims work;
+    work.init(p.work_counter, wave, waves_per_block);
+    uint64_t again = 0; // lanes of the wave-load in hand whose streams lay beyond the last pass's window (wave_min_offset)
+    uint64_t load = 0;
+    for (;;) {
+        if (again == 0) {
+            load = work.take(lane);
+            if ((load >> 32) != 0 || (uint32_t)load >= loads) // (scalar compares)
+                break;
+        }
+        // ---- this lane's stream: its index entries, all of them the caller's data
+        const uint64_t pos = load * 64u + lane;
+        const bool mine = pos < p.nchunks && (again == 0 || ((again >> lane) & 1u)); // a position this pass looks at
+        uint64_t s = pos;
+        if (mine && p.order)
+            s = p.order[pos];
+        bool valid = mine && s < p.nchunks;
+        uint64_t off = 0, first = 0;
+        uint32_t len = 0, count = 0;
+        if (valid) {
+            off = p.offsets[s];
+            len = p.lengths[s];
+            first = p.sym_offsets[s];
+            count = p.sym_counts[s];
+        }
+        valid = valid && (off & 3u) == 0 && len >= 16u && len <= (1u << 30) && off <= p.container_bytes && len <= p.container_bytes - off &&
+                first <= p.out_syms && count <= p.out_syms - first;
+        if (mine && !valid)
+            nbad++; // (a rejected entry is seen in one pass only: it never joins `again`)
+        const uint64_t rb = wave_min_offset(off, valid) & ~uint64_t(kLaneLine - 1);
+        const bool far = valid && off - rb >= (1u << 30);
+        again = __builtin_amdgcn_ballot_w64(far);
+        valid = valid && !far;
+        // the wave-load's window onto the container: offsets from rb, reads past the last 16-byte granule return 0
+        const uint64_t span = cbytes16 - (rb < cbytes16 ? rb : cbytes16);
+        const uint32_t nrec = uniform((uint32_t)(span < 0x7ffffff0ull ? span : 0x7ffffff0ull));
+        const uint64_t wbase = uniform64(cbase + rb);
+        const u32x4 rsrc4 = {uniform((uint32_t)wbase), uniform((uint32_t)(wbase >> 32)) & 0xffffu, nrec, 0x00020000u};
+
+        // ---- the lane's own counts and where its symbols go ([dst, dst + count) lies inside the output)
+        const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + first;
+        const uint32_t trips = valid ? count >> 6 : 0u;
+        const uint32_t tail = valid ? count & 63u : 0u;
+        const bool by_quad = (dst & 63u) == 0, by_dwords = (dst & 3u) == 0;
+        // store instruction t writes the line of the quad's lane t, this lane its piece m -- while that lane has trips left
+        const uint32_t qtrips = by_quad ? trips : 0u;
+        uint64_t at[4];
+        uint32_t tq[4];
+        {
+            const uint32_t dlo = (uint32_t)dst, dhi = (uint32_t)(dst >> 32);
+            at[0] = (((uint64_t)quad_perm<0x00>(dhi) << 32) | quad_perm<0x00>(dlo)) + l16;
+            at[1] = (((uint64_t)quad_perm<0x55>(dhi) << 32) | quad_perm<0x55>(dlo)) + l16;
+            at[2] = (((uint64_t)quad_perm<0xAA>(dhi) << 32) | quad_perm<0xAA>(dlo)) + l16;
+            at[3] = (((uint64_t)quad_perm<0xFF>(dhi) << 32) | quad_perm<0xFF>(dlo)) + l16;
+            tq[0] = quad_perm<0x00>(qtrips);
+            tq[1] = quad_perm<0x55>(qtrips);
+            tq[2] = quad_perm<0xAA>(qtrips);
+            tq[3] = quad_perm<0xFF>(qtrips);
+        }
+
+        uint32_t cur = valid ? (uint32_t)(off - rb) : 0u; // position in the wave-load's window (ring index = cur & 127)
+        const uint32_t cur0 = cur;
+        uint32_t ld = valid ? (cur & ~(kLaneLine - 1u)) : kParkAhead; // next line not yet requested (never, without a stream)
+        // opening: the first two lines (the states are the first 16 bytes of the stream, rans64.h:251-262)
+        asm volatile("v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT "v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT
+                     "s_waitcnt lgkmcnt(0)"
+                     : [ld] "+v"(ld)
+                     : [cur] "v"(cur), [l16] "v"(l16), [rq0] "v"(rq0), [m0] "s"(m0), [rsrc] "s"(rsrc4)
+                     : R64_CLOBBERS);
+        uint64_t xA = kL, xB = kL, win = 0;
+        if (valid) {
+            const u32x2 a = *reinterpret_cast<const u32x2 *>(rowp + (cur & 127u));
+            const u32x2 b = *reinterpret_cast<const u32x2 *>(rowp + ((cur + 8u) & 127u));
+            xA = (uint64_t)a.x | ((uint64_t)a.y << 32);
+            xB = (uint64_t)b.x | ((uint64_t)b.y << 32);
+            cur += 16u;
+            const uint32_t w0 = *reinterpret_cast<const uint32_t *>(rowp + (cur & 127u));
+            const uint32_t w1 = *reinterpret_cast<const uint32_t *>(rowp + ((cur + 4u) & 127u));
+            win = (uint64_t)w0 | ((uint64_t)w1 << 32);
+        }
+
+        // ---- whole trips: 64 symbols per lane and statement
+        for (uint32_t trip = 0; __builtin_amdgcn_ballot_w64(trip < trips) != 0; ++trip) {
+            const bool run = trip < trips;
+            const uint64_t xA_keep = xA, xB_keep = xB, win_keep = win;
+            const uint32_t cur_keep = cur, ld_keep = ld;
+            ld = run ? ld : cur + kParkAhead;
+            u32x4 q0, q1, q2, q3;
+            asm volatile("s_mov_b64 s[40:41], 0\n\t"
+                         "s_mov_b64 s[42:43], 0\n\t"
+                         "s_mov_b64 s[44:45], 0\n\t"
+                         "s_mov_b64 s[46:47], 0\n\t"
+                         R64B_BOUNDARY("0") R64_GROUP("v8", "v9", "v10", "v11")
+                         R64_COMMIT R64B_BOUNDARY("1") R64_GROUP("v12", "v13", "v14", "v15")
+                         R64_COMMIT R64B_BOUNDARY("2") R64_GROUP("v16", "v17", "v18", "v19")
+                         R64_COMMIT R64B_BOUNDARY("3") R64_GROUP("v20", "v21", "v22", "v23")
+                         R64_COMMIT
+                         "s_waitcnt lgkmcnt(0)"
+                         : "+{v[40:41]}"(xA), "+{v[42:43]}"(xB), "+{v[44:45]}"(win), [cur] "+v"(cur), [ld] "+v"(ld), "=&{v[8:11]}"(q0),
+                           "=&{v[12:15]}"(q1), "=&{v[16:19]}"(q2), "=&{v[20:23]}"(q3)
+                         : [maskv] "v"(maskv), [sbv] "v"(sbv), [t1v] "v"(t1v), [row] "v"(row), [l16] "v"(l16), [rq0] "v"(rq0),
+                           [kL] "s"(kL), [m0] "s"(m0), [rsrc] "s"(rsrc4)
+                         : R64B_CLOBBERS);
+            xA = run ? xA : xA_keep;
+            xB = run ? xB : xB_keep;
+            win = run ? win : win_keep;
+            cur = run ? cur : cur_keep;
+            ld = run ? ld : ld_keep;
+            const uint64_t o = (uint64_t)trip << 6;
+            if (run && !by_quad) { // the lane's own 64 bytes, from its own registers
+                if (by_dwords) {
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o) = q0;
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o + 16u) = q1;
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o + 32u) = q2;
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o + 48u) = q3;
+                } else {
+                    uint8_t RANS_GLOBAL *d = reinterpret_cast<uint8_t RANS_GLOBAL *>(dst + o);
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        d[j] = (uint8_t)(q0[j >> 2] >> (8 * (j & 3)));
+                        d[16 + j] = (uint8_t)(q1[j >> 2] >> (8 * (j & 3)));
+                        d[32 + j] = (uint8_t)(q2[j >> 2] >> (8 * (j & 3)));
+                        d[48 + j] = (uint8_t)(q3[j >> 2] >> (8 * (j & 3)));
+                    }
+                }
+            }
+            quad_transpose(q0, q1, q2, q3, lane); // (full exec: the moves read all four lanes)
+            if (trip < tq[0])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[0] + o) = q0;
+            if (trip < tq[1])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[1] + o) = q1;
+            if (trip < tq[2])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[2] + o) = q2;
+            if (trip < tq[3])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[3] + o) = q3;
+        }
+
+        // ---- count & 63 symbols: sixteen at a time behind a fetch + commit of their own, straight from the ring
+        uint8_t RANS_GLOBAL *tdst = reinterpret_cast<uint8_t RANS_GLOBAL *>(dst + ((uint64_t)trips << 6));
+        for (uint32_t j0 = 0; __builtin_amdgcn_ballot_w64(j0 < tail) != 0; j0 += 16u) {
+            const bool live = j0 < tail;
+            const uint32_t ld_keep = ld;
+            ld = live ? ld : cur + kParkAhead;
+            asm volatile("v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT "s_waitcnt lgkmcnt(0)"
+                         : [ld] "+v"(ld)
+                         : [cur] "v"(cur), [l16] "v"(l16), [rq0] "v"(rq0), [m0] "s"(m0), [rsrc] "s"(rsrc4)
+                         : R64_CLOBBERS);
+            ld = live ? ld : ld_keep;
+            if (live) {
+                const uint32_t cnt = tail - j0 < 16u ? tail - j0 : 16u;
+                for (uint32_t i = 0; i < cnt; i += 2u) {
+                    const bool two = i + 1u < cnt;
+                    tdst[j0 + i] = (uint8_t)dec_step<FMT_R64>(T, xA);
+                    if (two)
+                        tdst[j0 + i + 1u] = (uint8_t)dec_step<FMT_R64>(T, xB);
+                    if (xA < kL) { // rans64.h:305-316, state 0 first
+                        xA = (xA << 32) | *reinterpret_cast<const uint32_t *>(rowp + (cur & 127u));
+                        cur += 4u;
+                    }
+                    if (two && xB < kL) {
+                        xB = (xB << 32) | *reinterpret_cast<const uint32_t *>(rowp + (cur & 127u));
+                        cur += 4u;
+                    }
+                }
+            }
+        }
+        // RansDec end state: both states back at L, every byte of the stream consumed (main64.cpp has no check; ours)
+        if (valid && (xA != kL || xB != kL || cur - cur0 != len))
+            nbad++;
+    }
+    if (nbad)
+        atomicAdd(p.err_count, (unsigned long long)nbad);
+    record_span(p, t_start, smem, threadIdx.x);
+}
+#undef R64B_BOUNDARY
+#undef R64B_CLOBBERS
+
 template <int FMT, int NW>
 __global__ void __launch_bounds__(256) k_decode_lanes(const DecParams p)
 {
@@ -1093,6 +1360,32 @@ hipError_t launch_decode_lanes(int format, const DecParams &p, int num_cus, hipS
     case FMT_ALIAS: return launch_decode_lanes_f<FMT_ALIAS>(p, num_cus, stream, name);
     default: return hipErrorInvalidValue;
     }
+}
+
+// The ragged form of the 2-way rans64 lane decoder: rans64 over u8 symbols with the cum2sym tables (the caller has checked
+// the format: the search variant is another kernel format), from 64 streams on; any symbol count, any output address.  Both
+// tables and at least one wave's rings inside the CU's 160 KiB of LDS.
+static size_t batch_lanes_tables(const DecParams &p) { return (size_t)((p.table0_bytes + 15u) & ~15u) + ((p.table1_bytes + 15u) & ~15u); }
+bool decode_batch_r64_lanes_applicable(const DecParams &p)
+{
+    return p.n_ways == 2 && p.sym_bytes == 1 && p.scale_bits >= 7 && p.scale_bits <= 16 && p.nchunks >= 64 && p.sym_offsets &&
+           p.sym_counts && !p.trace && batch_lanes_tables(p) + kR64WaveLds <= 160 * 1024;
+}
+
+hipError_t launch_decode_batch_r64_lanes(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
+{
+    // one block per CU, as many waves as the tables leave rings for (14 bits: 16; 16 bits, 64 KiB of cum2sym: 11); a batch
+    // that does not fill them spreads its wave-loads evenly (lanes_even_waves)
+    const size_t table_lds = batch_lanes_tables(p);
+    const uint32_t room = (uint32_t)((160 * 1024 - table_lds) / kR64WaveLds);
+    const uint32_t max_waves = room > 16 ? 16 : room;
+    const uint64_t loads = (p.nchunks + 63) / 64;
+    const uint32_t sw = loads >= (uint64_t)num_cus * max_waves ? max_waves : lanes_even_waves(loads, num_cus, max_waves);
+    static std::atomic<uint64_t> lds_ok{0};
+    if (name)
+        *name = KernelId::decode_batch_r64_lanes;
+    return launch_lanes(k_decode_batch_r64_lanes, lds_ok, 160 * 1024, lanes_grid(loads, sw, num_cus), 64 * sw,
+                        table_lds + (size_t)sw * kR64WaveLds, stream, p);
 }
 
 #undef R64_LOOKUP

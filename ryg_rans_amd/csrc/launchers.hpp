@@ -109,6 +109,11 @@ inline bool lanes_applicable(uint64_t nchunks, uint32_t n_ways)
 }
 hipError_t launch_decode_lanes(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
+// the ragged form of the 2-way rans64 lane decoder (rans_amd_decode_batch under kVarBatchLanes; decode_lanes.hip): 64 STREAMS
+// per wave, one per lane, each with its own symbol count and output address, from 64 streams on, scale_bits 7..16, the tables
+// and at least one wave's rings inside the CU's 160 KiB of LDS (the launcher sizes the block from what the tables leave)
+bool decode_batch_r64_lanes_applicable(const DecParams &p);
+hipError_t launch_decode_batch_r64_lanes(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // true when launch_encode_lanes would take the staged kernel for this request -- the one that can place its chunks
 // itself (EncParams::status); everything but status / offsets / out / out_cap must be filled in
 bool encode_lanes_fused(const EncParams &p, int num_cus);
