@@ -658,32 +658,15 @@ int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value)
         ctx->variant &= ~(kVarNoDual | kVarDualAlways);
         ctx->variant |= value == 0 ? kVarNoDual : value == 2 ? kVarDualAlways : 0u;
         return RANS_AMD_OK;
-    case RANS_AMD_OPT_BATCH_GROUPS:
-        if (value != 0 && value != 1)
-            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_GROUPS takes 0 (one stream per wave) or 1 (eight 8-way word streams per wave)");
-        ctx->variant = value ? (ctx->variant | kVarBatchGroups) : (ctx->variant & ~kVarBatchGroups);
-        return RANS_AMD_OK;
-    case RANS_AMD_OPT_BATCH_ENCODE_GROUPS:
-        if (value != 0 && value != 1)
-            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_ENCODE_GROUPS takes 0 (one stream per wave) or 1 (eight 8-way word streams per wave)");
-        ctx->variant = value ? (ctx->variant | kVarBatchEncGroups) : (ctx->variant & ~kVarBatchEncGroups);
-        return RANS_AMD_OK;
-    case RANS_AMD_OPT_BATCH_PAIRS:
-        if (value != 0 && value != 1)
-            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_PAIRS takes 0 (one stream per wave) or 1 (thirty-two 2-way byte streams per wave)");
-        ctx->variant = value ? (ctx->variant | kVarBatchPairs) : (ctx->variant & ~kVarBatchPairs);
-        return RANS_AMD_OK;
-    case RANS_AMD_OPT_BATCH_ENCODE_PAIRS:
-        if (value != 0 && value != 1)
-            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_ENCODE_PAIRS takes 0 (one stream per wave) or 1 (thirty-two 2-way byte streams per wave)");
-        ctx->variant = value ? (ctx->variant | kVarBatchEncPairs) : (ctx->variant & ~kVarBatchEncPairs);
-        return RANS_AMD_OK;
-    case RANS_AMD_OPT_BATCH_LANES:
-        if (value != 0 && value != 1)
-            return fail(RANS_AMD_E_ARG, "set_option: RANS_AMD_OPT_BATCH_LANES takes 0 (one stream per wave) or 1 (sixty-four 2-way rans64 streams per wave)");
-        ctx->variant = value ? (ctx->variant | kVarBatchLanes) : (ctx->variant & ~kVarBatchLanes);
-        return RANS_AMD_OK;
     default:
+        for (const BatchFamily &f : kBatchFamilies) { // the streams-per-wave families of the ragged batches: one bit each
+            if (option != f.option)
+                continue;
+            if (value != 0 && value != 1)
+                return fail(RANS_AMD_E_ARG, (std::string("set_option: ") + f.option_name + " takes 0 (one stream per wave) or 1 (" + f.streams + ")").c_str());
+            ctx->variant = value ? (ctx->variant | f.bit) : (ctx->variant & ~f.bit);
+            return RANS_AMD_OK;
+        }
         return fail(RANS_AMD_E_ARG, "set_option: unknown option");
     }
 }
@@ -1491,9 +1474,9 @@ int rans_amd_decode_batch(rans_amd_ctx *ctx, const rans_amd_model *model, const 
         RC_TRY(take_counter_slot(ctx, capture, s, dp)); // (n_streams fits the 32-bit counters: checked above)
         int dec_format = decoder_kernel_format(model);
         // byte format: the fused slot records where the model has them and they leave room for two blocks per CU (rans_amd_decode;
-        // the wave-per-stream kernels' tables -- the 32-streams-per-wave kernel of RANS_AMD_OPT_BATCH_PAIRS keeps cum2sym + records)
-        const bool pairs = (ctx->variant & kVarBatchPairs) && dec_format == RANS_AMD_FMT_BYTE && decode_batch_byte_pairs_applicable(dp);
-        if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12 && !pairs)
+        // the wave-per-stream kernels' tables: no family took it -- the 32-streams-per-wave kernel of RANS_AMD_OPT_BATCH_PAIRS keeps
+        // cum2sym + records)
+        if (dec_format == RANS_AMD_FMT_BYTE && model->d_fused && model->host.scale_bits <= 12 && !decode_batch_family(dp.variant, dec_format, dp))
             dec_format = use_byte_fused_tables(dp, model);
         // (rans64, RANS_AMD_OPT_BATCH_LANES: the 64-streams-per-wave kernel reads the cum2sym tables filled in above; whether they
         // and a wave's rings fit the CU's LDS is decode_batch_r64_lanes_applicable's question, asked by launch_decode_batch, and

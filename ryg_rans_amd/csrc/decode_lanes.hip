@@ -564,6 +564,23 @@ constexpr uint32_t kR64WaveLds = 64 * kR64RingStride;
     "v_add_u32 v67, %[rq0], v67\n\t" \
     "s_mov_b64 exec, -1\n\t" \
     "s_nop 4\n\t"
+// a group boundary: the ring's invariant is >= 48 bytes ahead here (N: the boundary's number within its statement, for the label)
+#define R64_BOUNDARY(N)                                                                                                 \
+    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
+    "v_cmp_gt_i32 vcc, 48, v46\n\t"                                                                                     \
+    "s_cbranch_vccz .Lr64ok" N "_%=\n\t"                                                                                \
+    /* side path (some lane is about to starve): everybody with room asks now, and we wait */                          \
+    R64_FETCH R64_COMMIT                                                                                                \
+    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
+    ".Lr64ok" N "_%=:\n\t" R64_FETCH
+// LINES lines fetched and committed at once, a statement of its own (the opening's two, the one ahead of a tail group); the
+// names are the kernels' own: ld, cur, l16, rq0, m0, rsrc4
+#define R64_ASK "v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT
+#define R64_FETCH_NOW(LINES)                                                                                            \
+    asm volatile(LINES "s_waitcnt lgkmcnt(0)"                                                                           \
+                 : [ld] "+v"(ld)                                                                                        \
+                 : [cur] "v"(cur), [l16] "v"(l16), [rq0] "v"(rq0), [m0] "s"(m0), [rsrc] "s"(rsrc4)                      \
+                 : R64_CLOBBERS)
 // 4 x 4 transpose of 16-byte pieces inside every quad: lane 4k+m, set t  <->  lane 4k+t, set m
 #define R64_TRANSPOSE                                                                                                   \
     "v_mov_b32 v46, v8\n\t" \
@@ -697,11 +714,29 @@ constexpr uint32_t kR64WaveLds = 64 * kR64RingStride;
         "v62", "v63", "v64", "v65", "v66", "v67", "s36", "s37", "s38", "s39", "s40", "s41", "s42", "s43", "s44", "s45", "s46", \
         "s47", "s50"
 
+// The window of a wave's sixty-four streams onto the container, a buffer resource at the line of the lowest one: offsets from
+// rb, reads past the last 16-byte granule return 0.  Lanes 2^30 bytes and more beyond rb wait for another pass (`again`) and
+// are not valid in this one.  Declares rb and rsrc4; the other names are the kernels' own.  (A macro: as a forceinline helper
+// taking references it costs both kernels their code -- 1 and 3 instructions less, 2 VGPRs less in the ragged one, not equal:
+// profiles/batch_families_isa.md.)
+#define R64_WINDOW                                                                                                      \
+    const uint64_t rb = wave_min_offset(off, valid) & ~uint64_t(kLaneLine - 1);                                         \
+    const bool far = valid && off - rb >= (1u << 30);                                                                   \
+    again = __builtin_amdgcn_ballot_w64(far);                                                                           \
+    valid = valid && !far;                                                                                              \
+    const uint64_t span = cbytes16 - (rb < cbytes16 ? rb : cbytes16);                                                   \
+    const uint32_t nrec = uniform((uint32_t)(span < 0x7ffffff0ull ? span : 0x7ffffff0ull));                             \
+    const uint64_t wbase = uniform64(cbase + rb);                                                                       \
+    const u32x4 rsrc4 = {uniform((uint32_t)wbase), uniform((uint32_t)(wbase >> 32)) & 0xffffu, nrec, 0x00020000u}
+
 template <bool PACKED> __global__ void __launch_bounds__(1024) k_decode_lanes_r64x2(const DecParams p)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u;
     const uint32_t t1_bytes = (p.table1_bytes + 15u) & ~15u;
+    // (groups_common.hpp's stage_table and reset_for_next_launch, written out: with either helper the claim loop's set-up is laid
+    // out differently, 7 instructions more in both instantiations -- profiles/batch_families_isa.md.  The ragged kernel below
+    // calls them.)
     {
         const uint4 *g0 = reinterpret_cast<const uint4 *>(p.table0);
         uint4 *l0 = reinterpret_cast<uint4 *>(smem);
@@ -757,15 +792,7 @@ template <bool PACKED> __global__ void __launch_bounds__(1024) k_decode_lanes_r6
             nbad++;
             valid = false;
         }
-        const uint64_t rb = wave_min_offset(off, valid) & ~uint64_t(kLaneLine - 1);
-        const bool far = valid && off - rb >= (1u << 30);
-        again = __builtin_amdgcn_ballot_w64(far);
-        valid = valid && !far;
-        // the batch's window onto the container: offsets from rb, reads past the last 16-byte granule return 0
-        const uint64_t span = cbytes16 - (rb < cbytes16 ? rb : cbytes16);
-        const uint32_t nrec = uniform((uint32_t)(span < 0x7ffffff0ull ? span : 0x7ffffff0ull));
-        const uint64_t wbase = uniform64(cbase + rb);
-        const u32x4 rsrc4 = {uniform((uint32_t)wbase), uniform((uint32_t)(wbase >> 32)) & 0xffffu, nrec, 0x00020000u};
+        R64_WINDOW;
         // store addresses: instruction t writes the line of the quad's lane t, this lane its piece m
         const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + chunk * p.chunk_syms;
         uint64_t at[4], vq[4];
@@ -781,11 +808,7 @@ template <bool PACKED> __global__ void __launch_bounds__(1024) k_decode_lanes_r6
         const uint32_t cur0 = cur;
         uint32_t ld = valid ? (cur & ~(kLaneLine - 1u)) : 0x40000000u; // next line not yet requested (never, without a chunk)
         // opening: the first two lines (the states are the first 16 bytes of the stream, rans64.h:251-262)
-        asm volatile("v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT "v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT
-                     "s_waitcnt lgkmcnt(0)"
-                     : [ld] "+v"(ld)
-                     : [cur] "v"(cur), [l16] "v"(l16), [rq0] "v"(rq0), [m0] "s"(m0), [rsrc] "s"(rsrc4)
-                     : R64_CLOBBERS);
+        R64_FETCH_NOW(R64_ASK R64_ASK);
         uint64_t xA, xB, win;
         {
             const u32x2 a = *reinterpret_cast<const u32x2 *>(rowp + (cur & 127u));
@@ -798,73 +821,37 @@ template <bool PACKED> __global__ void __launch_bounds__(1024) k_decode_lanes_r6
             win = (uint64_t)w0 | ((uint64_t)w1 << 32);
         }
         uint32_t trips = uniform(p.chunk_syms >> 6);
-        if constexpr (PACKED) {
-        asm volatile("s_mov_b64 s[40:41], 0\n\t"
-                     "s_mov_b64 s[42:43], 0\n\t"
-                     "s_mov_b64 s[44:45], 0\n\t"
-                     "s_mov_b64 s[46:47], 0\n\t"
-                     "s_mov_b32 s50, 0\n\t"
-                     ".Lr64trip_%=:\n\t"
-                     R64_COMMIT
-                     R64_TRIP_TOP
-#define R64_BOUNDARY(N)                                                                                                 \
-    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
-    "v_cmp_gt_i32 vcc, 48, v46\n\t"                                                                                     \
-    "s_cbranch_vccz .Lr64ok" N "_%=\n\t"                                                                                \
-    /* side path (some lane is about to starve): everybody with room asks now, and we wait */                          \
-    R64_FETCH R64_COMMIT                                                             \
-    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
-    ".Lr64ok" N "_%=:\n\t" R64_FETCH
-                     R64_BOUNDARY("0") R64P_GROUP("v8", "v9", "v10", "v11")
-                     R64_COMMIT R64_BOUNDARY("1") R64P_GROUP("v12", "v13", "v14", "v15")
-                     R64_COMMIT R64_BOUNDARY("2") R64P_GROUP("v16", "v17", "v18", "v19")
-                     R64_COMMIT R64_BOUNDARY("3") R64P_GROUP("v20", "v21", "v22", "v23")
-                     R64_TRIP_END
-                     "s_sub_u32 %[trips], %[trips], 1\n\t"
-                     "s_cmp_lg_u32 %[trips], 0\n\t"
-                     "s_cbranch_scc1 .Lr64trip_%=\n\t"
-                     R64_LAST
-                     "s_waitcnt vmcnt(0) lgkmcnt(0)"
-                     : "+{v[40:41]}"(xA), "+{v[42:43]}"(xB), "+{v[44:45]}"(win), [cur] "+v"(cur), [ld] "+v"(ld), [at0] "+v"(at[0]),
-                       [at1] "+v"(at[1]), [at2] "+v"(at[2]), [at3] "+v"(at[3]), [trips] "+s"(trips)
-                     : [maskv] "v"(maskv), [sbv] "v"(sbv), [m12v] "v"(m12v), [selA] "s"(0x0c0c0703u), [selB] "s"(0x07030c0cu), [row] "v"(row), [l16] "v"(l16), [rq0] "v"(rq0),
-                       [kL] "s"(kL), [m0] "s"(m0), [vq0] "s"(vq[0]), [vq1] "s"(vq[1]), [vq2] "s"(vq[2]), [vq3] "s"(vq[3]),
-                       [rsrc] "s"(rsrc4)
-                     : R64_CLOBBERS R64_HOLD_CLOBBERS);
-        } else {
-        asm volatile("s_mov_b64 s[40:41], 0\n\t"
-                     "s_mov_b64 s[42:43], 0\n\t"
-                     "s_mov_b64 s[44:45], 0\n\t"
-                     "s_mov_b64 s[46:47], 0\n\t"
-                     "s_mov_b32 s50, 0\n\t"
-                     ".Lr64trip_%=:\n\t"
-                     R64_COMMIT
-                     R64_TRIP_TOP
-#define R64_BOUNDARY(N)                                                                                                 \
-    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
-    "v_cmp_gt_i32 vcc, 48, v46\n\t"                                                                                     \
-    "s_cbranch_vccz .Lr64ok" N "_%=\n\t"                                                                                \
-    /* side path (some lane is about to starve): everybody with room asks now, and we wait */                          \
-    R64_FETCH R64_COMMIT                                                             \
-    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
-    ".Lr64ok" N "_%=:\n\t" R64_FETCH
-                     R64_BOUNDARY("0") R64_GROUP("v8", "v9", "v10", "v11")
-                     R64_COMMIT R64_BOUNDARY("1") R64_GROUP("v12", "v13", "v14", "v15")
-                     R64_COMMIT R64_BOUNDARY("2") R64_GROUP("v16", "v17", "v18", "v19")
-                     R64_COMMIT R64_BOUNDARY("3") R64_GROUP("v20", "v21", "v22", "v23")
-                     R64_TRIP_END
-                     "s_sub_u32 %[trips], %[trips], 1\n\t"
-                     "s_cmp_lg_u32 %[trips], 0\n\t"
-                     "s_cbranch_scc1 .Lr64trip_%=\n\t"
-                     R64_LAST
-                     "s_waitcnt vmcnt(0) lgkmcnt(0)"
-                     : "+{v[40:41]}"(xA), "+{v[42:43]}"(xB), "+{v[44:45]}"(win), [cur] "+v"(cur), [ld] "+v"(ld), [at0] "+v"(at[0]),
-                       [at1] "+v"(at[1]), [at2] "+v"(at[2]), [at3] "+v"(at[3]), [trips] "+s"(trips)
-                     : [maskv] "v"(maskv), [sbv] "v"(sbv), [t1v] "v"(t1v), [row] "v"(row), [l16] "v"(l16), [rq0] "v"(rq0),
-                       [kL] "s"(kL), [m0] "s"(m0), [vq0] "s"(vq[0]), [vq1] "s"(vq[1]), [vq2] "s"(vq[2]), [vq3] "s"(vq[3]),
-                       [rsrc] "s"(rsrc4)
-                     : R64_CLOBBERS R64_HOLD_CLOBBERS);
-        }
+        // every trip of the chunk in one statement; GROUP and its own operands (...) are what the two slot layouts differ in
+#define R64_ALL_TRIPS(GROUP, ...)                                                                                       \
+    asm volatile("s_mov_b64 s[40:41], 0\n\t"                                                                            \
+                 "s_mov_b64 s[42:43], 0\n\t"                                                                            \
+                 "s_mov_b64 s[44:45], 0\n\t"                                                                            \
+                 "s_mov_b64 s[46:47], 0\n\t"                                                                            \
+                 "s_mov_b32 s50, 0\n\t"                                                                                 \
+                 ".Lr64trip_%=:\n\t"                                                                                    \
+                 R64_COMMIT                                                                                             \
+                 R64_TRIP_TOP                                                                                           \
+                 R64_BOUNDARY("0") GROUP("v8", "v9", "v10", "v11")                                                      \
+                 R64_COMMIT R64_BOUNDARY("1") GROUP("v12", "v13", "v14", "v15")                                         \
+                 R64_COMMIT R64_BOUNDARY("2") GROUP("v16", "v17", "v18", "v19")                                         \
+                 R64_COMMIT R64_BOUNDARY("3") GROUP("v20", "v21", "v22", "v23")                                         \
+                 R64_TRIP_END                                                                                           \
+                 "s_sub_u32 %[trips], %[trips], 1\n\t"                                                                  \
+                 "s_cmp_lg_u32 %[trips], 0\n\t"                                                                         \
+                 "s_cbranch_scc1 .Lr64trip_%=\n\t"                                                                      \
+                 R64_LAST                                                                                               \
+                 "s_waitcnt vmcnt(0) lgkmcnt(0)"                                                                        \
+                 : "+{v[40:41]}"(xA), "+{v[42:43]}"(xB), "+{v[44:45]}"(win), [cur] "+v"(cur), [ld] "+v"(ld), [at0] "+v"(at[0]),       \
+                   [at1] "+v"(at[1]), [at2] "+v"(at[2]), [at3] "+v"(at[3]), [trips] "+s"(trips)                         \
+                 : [maskv] "v"(maskv), [sbv] "v"(sbv), __VA_ARGS__, [row] "v"(row), [l16] "v"(l16), [rq0] "v"(rq0),     \
+                   [kL] "s"(kL), [m0] "s"(m0), [vq0] "s"(vq[0]), [vq1] "s"(vq[1]), [vq2] "s"(vq[2]), [vq3] "s"(vq[3]),  \
+                   [rsrc] "s"(rsrc4)                                                                                    \
+                 : R64_CLOBBERS R64_HOLD_CLOBBERS)
+        if constexpr (PACKED)
+            R64_ALL_TRIPS(R64P_GROUP, [m12v] "v"(m12v), [selA] "s"(0x0c0c0703u), [selB] "s"(0x07030c0cu));
+        else
+            R64_ALL_TRIPS(R64_GROUP, [t1v] "v"(t1v));
+#undef R64_ALL_TRIPS
         // RansDec end state: both states back at L, every byte of the chunk consumed (main64.cpp has no check; ours)
         if (valid && (xA != kL || xB != kL || cur - cur0 != len))
             nbad++;
@@ -872,7 +859,6 @@ template <bool PACKED> __global__ void __launch_bounds__(1024) k_decode_lanes_r6
     if (nbad)
         atomicAdd(p.err_count, (unsigned long long)nbad);
 }
-#undef R64_BOUNDARY
 
 // ---------------------------------------------------------------------------
 // k_decode_batch_r64_lanes -- the ragged form of k_decode_lanes_r64x2 (rans_amd_decode_batch under
@@ -910,13 +896,6 @@ template <bool PACKED> __global__ void __launch_bounds__(1024) k_decode_lanes_r6
 // these is counted once, nothing of it is fetched, nothing stored.  Behind the last symbol both states are 2^31 and the
 // cursor stands at the stream's end, else the stream is counted.
 // ---------------------------------------------------------------------------
-#define R64B_BOUNDARY(N)                                                                                                \
-    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
-    "v_cmp_gt_i32 vcc, 48, v46\n\t"                                                                                     \
-    "s_cbranch_vccz .Lr64bok" N "_%=\n\t"                                                                               \
-    R64_FETCH R64_COMMIT                                                                                                \
-    "v_sub_u32 v46, %[ld], %[cur]\n\t"                                                                                  \
-    ".Lr64bok" N "_%=:\n\t" R64_FETCH
 // (R64_CLOBBERS without the sixteen output registers, which are operands here, and without s50)
 #define R64B_CLOBBERS                                                                                                   \
     "vcc", "scc", "memory", "v24", "v25", "v26", "v27", "v28", "v29", "v30", "v31", "v32", "v33", "v34", "v35", "v36", "v37", \
@@ -975,6 +954,9 @@ __global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams
         }
         // ---- this lane's stream: its index entries, all of them the caller's data
         const uint64_t pos = load * 64u + lane;
+        // (groups_common.hpp's fetch_stream_entry<16, false> with the 4-byte grid and the 2^30 limit behind it, written out: the
+        // helper knows no `again`, so a later pass reads the entries of lanes it skips, and the kernel compiles to another
+        // register allocation, 113 VGPRs for 115 -- profiles/batch_families_isa.md.  A fix there has to be made here as well.)
         const bool mine = pos < p.nchunks && (again == 0 || ((again >> lane) & 1u)); // a position this pass looks at
         uint64_t s = pos;
         if (mine && p.order)
@@ -992,15 +974,7 @@ __global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams
                 first <= p.out_syms && count <= p.out_syms - first;
         if (mine && !valid)
             nbad++; // (a rejected entry is seen in one pass only: it never joins `again`)
-        const uint64_t rb = wave_min_offset(off, valid) & ~uint64_t(kLaneLine - 1);
-        const bool far = valid && off - rb >= (1u << 30);
-        again = __builtin_amdgcn_ballot_w64(far);
-        valid = valid && !far;
-        // the wave-load's window onto the container: offsets from rb, reads past the last 16-byte granule return 0
-        const uint64_t span = cbytes16 - (rb < cbytes16 ? rb : cbytes16);
-        const uint32_t nrec = uniform((uint32_t)(span < 0x7ffffff0ull ? span : 0x7ffffff0ull));
-        const uint64_t wbase = uniform64(cbase + rb);
-        const u32x4 rsrc4 = {uniform((uint32_t)wbase), uniform((uint32_t)(wbase >> 32)) & 0xffffu, nrec, 0x00020000u};
+        R64_WINDOW;
 
         // ---- the lane's own counts and where its symbols go ([dst, dst + count) lies inside the output)
         const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + first;
@@ -1027,11 +1001,7 @@ __global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams
         const uint32_t cur0 = cur;
         uint32_t ld = valid ? (cur & ~(kLaneLine - 1u)) : kParkAhead; // next line not yet requested (never, without a stream)
         // opening: the first two lines (the states are the first 16 bytes of the stream, rans64.h:251-262)
-        asm volatile("v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT "v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT
-                     "s_waitcnt lgkmcnt(0)"
-                     : [ld] "+v"(ld)
-                     : [cur] "v"(cur), [l16] "v"(l16), [rq0] "v"(rq0), [m0] "s"(m0), [rsrc] "s"(rsrc4)
-                     : R64_CLOBBERS);
+        R64_FETCH_NOW(R64_ASK R64_ASK);
         uint64_t xA = kL, xB = kL, win = 0;
         if (valid) {
             const u32x2 a = *reinterpret_cast<const u32x2 *>(rowp + (cur & 127u));
@@ -1055,10 +1025,10 @@ __global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams
                          "s_mov_b64 s[42:43], 0\n\t"
                          "s_mov_b64 s[44:45], 0\n\t"
                          "s_mov_b64 s[46:47], 0\n\t"
-                         R64B_BOUNDARY("0") R64_GROUP("v8", "v9", "v10", "v11")
-                         R64_COMMIT R64B_BOUNDARY("1") R64_GROUP("v12", "v13", "v14", "v15")
-                         R64_COMMIT R64B_BOUNDARY("2") R64_GROUP("v16", "v17", "v18", "v19")
-                         R64_COMMIT R64B_BOUNDARY("3") R64_GROUP("v20", "v21", "v22", "v23")
+                         R64_BOUNDARY("0") R64_GROUP("v8", "v9", "v10", "v11")
+                         R64_COMMIT R64_BOUNDARY("1") R64_GROUP("v12", "v13", "v14", "v15")
+                         R64_COMMIT R64_BOUNDARY("2") R64_GROUP("v16", "v17", "v18", "v19")
+                         R64_COMMIT R64_BOUNDARY("3") R64_GROUP("v20", "v21", "v22", "v23")
                          R64_COMMIT
                          "s_waitcnt lgkmcnt(0)"
                          : "+{v[40:41]}"(xA), "+{v[42:43]}"(xB), "+{v[44:45]}"(win), [cur] "+v"(cur), [ld] "+v"(ld), "=&{v[8:11]}"(q0),
@@ -1106,10 +1076,7 @@ __global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams
             const bool live = j0 < tail;
             const uint32_t ld_keep = ld;
             ld = live ? ld : cur + kParkAhead;
-            asm volatile("v_sub_u32 v46, %[ld], %[cur]\n\t" R64_FETCH R64_COMMIT "s_waitcnt lgkmcnt(0)"
-                         : [ld] "+v"(ld)
-                         : [cur] "v"(cur), [l16] "v"(l16), [rq0] "v"(rq0), [m0] "s"(m0), [rsrc] "s"(rsrc4)
-                         : R64_CLOBBERS);
+            R64_FETCH_NOW(R64_ASK);
             ld = live ? ld : ld_keep;
             if (live) {
                 const uint32_t cnt = tail - j0 < 16u ? tail - j0 : 16u;
@@ -1137,7 +1104,6 @@ __global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams
         atomicAdd(p.err_count, (unsigned long long)nbad);
     record_span(p, t_start, smem, threadIdx.x);
 }
-#undef R64B_BOUNDARY
 #undef R64B_CLOBBERS
 
 template <int FMT, int NW>

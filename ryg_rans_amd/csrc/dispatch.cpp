@@ -1,8 +1,6 @@
 // dispatch.cpp -- chooses the kernel family for a (format, n_ways, chunk count) request.
 #include "launchers.hpp"
 
-#include "../../include/ryg_rans_amd.h"
-
 namespace rans_amd {
 
 bool ways_supported(int format, uint32_t n_ways)
@@ -30,23 +28,12 @@ hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_
     return launch_decode_wave(format, p, num_cus, stream, name);
 }
 
-// ragged batches: the wave-per-stream kernels, whatever the interleave -- unless the context asked for eight streams per wave
-// (RANS_AMD_OPT_BATCH_GROUPS for the decoder, RANS_AMD_OPT_BATCH_ENCODE_GROUPS for the encoder) and the batch is the
-// reference's 8-way word layout over u8 symbols, from eight streams on, or for thirty-two streams per wave
-// (RANS_AMD_OPT_BATCH_PAIRS for the decoder, RANS_AMD_OPT_BATCH_ENCODE_PAIRS for the encoder) and the batch is the reference's
-// 2-way byte layout over u8 symbols at scale_bits 8..16, from 32 streams on: the ragged kernels of decode_groups.hip and
-// encode_groups.hip -- or for sixty-four streams per wave (RANS_AMD_OPT_BATCH_LANES, the decoder's alone) and the batch is the
-// reference's 2-way rans64 layout over u8 symbols at scale_bits 7..16, from 64 streams on: decode_lanes.hip's ragged kernel.
-// Every other shape takes the wave kernels under those options as well (the ragged forms of the other lane kernels and of the
-// 2-way rans64 ENCODER are later work).
+// ragged batches: the first streams-per-wave family that takes the batch (kBatchFamilies, launchers.hpp), else the
+// wave-per-stream kernels, whatever the interleave
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
-    if ((p.variant & kVarBatchGroups) && format == (int)RANS_AMD_FMT_WORD && decode_batch_word_groups_applicable(p))
-        return launch_decode_batch_word_groups(p, num_cus, stream, name);
-    if ((p.variant & kVarBatchPairs) && format == (int)RANS_AMD_FMT_BYTE && decode_batch_byte_pairs_applicable(p))
-        return launch_decode_batch_byte_pairs(p, num_cus, stream, name);
-    if ((p.variant & kVarBatchLanes) && format == (int)RANS_AMD_FMT_R64 && decode_batch_r64_lanes_applicable(p))
-        return launch_decode_batch_r64_lanes(p, num_cus, stream, name);
+    if (const BatchFamily *f = decode_batch_family(p.variant, format, p))
+        return f->launch_decode(p, num_cus, stream, name);
     return launch_decode_batch_wave(format, p, num_cus, stream, name);
 }
 
@@ -57,10 +44,8 @@ hipError_t launch_decode_batch_models(int format, const DecParams &p, int num_cu
 
 hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
-    if ((p.variant & kVarBatchEncGroups) && format == (int)RANS_AMD_FMT_WORD && encode_batch_word_groups_applicable(p))
-        return launch_encode_batch_word_groups(p, num_cus, stream, name);
-    if ((p.variant & kVarBatchEncPairs) && format == (int)RANS_AMD_FMT_BYTE && encode_batch_byte_pairs_applicable(p))
-        return launch_encode_batch_byte_pairs(p, num_cus, stream, name);
+    if (const BatchFamily *f = encode_batch_family(p.variant, format, p))
+        return f->launch_encode(p, num_cus, stream, name);
     return launch_encode_batch_wave(format == kKernelFormatWord16 ? (int)RANS_AMD_FMT_WORD : format, p, num_cus, stream, name);
 }
 

@@ -11,12 +11,7 @@
 //   batch_word_groups_encode  ... encoder (RANS_AMD_OPT_BATCH_ENCODE_GROUPS)
 //   batch_byte_pairs_decode   ragged 2-way byte streams, 32 per wave, decoder (RANS_AMD_OPT_BATCH_PAIRS)
 //   batch_byte_pairs_encode   ... encoder (RANS_AMD_OPT_BATCH_ENCODE_PAIRS)
-// A second list follows the first one: RANS_AMD_KERNEL_NAMES_LANES, the family
 //   batch_r64_lanes_decode    ragged 2-way rans64 streams, 64 per wave, decoder (RANS_AMD_OPT_BATCH_LANES)
-// Its ids follow the first list's in KernelId, its rows are kLaneKernelEntries; kKernelEntries (what
-// tests/kernel_names_driver.cpp prints and tests/_kernel_rows.py reads) is the first list alone, and
-// tests/kernel_names_batch_lanes_driver.cpp with tests/_batch_lanes.py hold the second list to its rows.  kernel_name() and
-// kernel_family() resolve ids from both.  (Folding the two into one list needs the row module to know the family.)
 #pragma once
 
 namespace rans_amd {
@@ -72,9 +67,7 @@ namespace rans_amd {
     X(decode_batch_word_groups, "k_decode_batch_word_groups", batch_word_groups_decode)           \
     X(encode_batch_word_groups, "k_encode_batch_word_groups", batch_word_groups_encode)           \
     X(decode_batch_byte_pairs, "k_decode_batch_byte_pairs", batch_byte_pairs_decode)              \
-    X(encode_batch_byte_pairs, "k_encode_batch_byte_pairs", batch_byte_pairs_encode)
-
-#define RANS_AMD_KERNEL_NAMES_LANES(X)                                                            \
+    X(encode_batch_byte_pairs, "k_encode_batch_byte_pairs", batch_byte_pairs_encode)              \
     X(decode_batch_r64_lanes, "k_decode_batch_r64_lanes", batch_r64_lanes_decode)
 
 enum class KernelFamily {
@@ -92,7 +85,6 @@ enum class KernelId {
     none, // no launch yet: the name is ""
 #define X(id, name, family) id,
     RANS_AMD_KERNEL_NAMES(X)
-    RANS_AMD_KERNEL_NAMES_LANES(X) // (behind the first list: an id of this one is kKernelEntryCount + 1 + its row)
 #undef X
 };
 
@@ -111,22 +103,9 @@ constexpr KernelEntry kKernelEntries[] = {
 };
 constexpr int kKernelEntryCount = (int)(sizeof(kKernelEntries) / sizeof(kKernelEntries[0]));
 
-// the second list's entries, in its order
-constexpr KernelEntry kLaneKernelEntries[] = {
-#define X(id, name, family) {KernelId::id, name, KernelFamily::family, #family},
-    RANS_AMD_KERNEL_NAMES_LANES(X)
-#undef X
-};
-constexpr int kLaneKernelEntryCount = (int)(sizeof(kLaneKernelEntries) / sizeof(kLaneKernelEntries[0]));
-
-constexpr const KernelEntry &kernel_entry(KernelId id) // (not for KernelId::none)
-{
-    return (int)id <= kKernelEntryCount ? kKernelEntries[(int)id - 1] : kLaneKernelEntries[(int)id - 1 - kKernelEntryCount];
-}
+constexpr const KernelEntry &kernel_entry(KernelId id) { return kKernelEntries[(int)id - 1]; } // (not for KernelId::none)
 constexpr const char *kernel_name(KernelId id) { return id == KernelId::none ? "" : kernel_entry(id).name; }
 constexpr KernelFamily kernel_family(KernelId id) { return kernel_entry(id).family; } // (not for KernelId::none)
-static_assert(kernel_entry(KernelId::decode_batch_r64_lanes).id == KernelId::decode_batch_r64_lanes &&
-                  kernel_entry(KernelId::encode_batch_byte_pairs).id == KernelId::encode_batch_byte_pairs,
-              "ids of both lists resolve to their own rows");
+static_assert(kernel_entry(KernelId::decode_batch_r64_lanes).id == KernelId::decode_batch_r64_lanes, "an id resolves to its own row");
 
 } // namespace rans_amd

@@ -5,6 +5,8 @@
 
 #include "kernels.h"
 
+#include "../../include/ryg_rans_amd.h" // the option ids and public formats of kBatchFamilies
+
 // Launch and report THIS launch's status: hipGetLastError() is per thread and sticky, so an error left
 // behind by other code in the process (PyTorch probing a device, say) would otherwise be blamed on us.
 #define RANS_LAUNCH(kern, grid, block, lds, stream, ...)                         \
@@ -76,14 +78,14 @@ hipError_t launch_decode_dual(int format, const DecParams &p, int num_cus, hipSt
 // symbols on a 4-byte aligned output, a partial last octet and a ragged last chunk included
 bool decode_word_groups_applicable(const DecParams &p);
 hipError_t launch_decode_word_groups(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
-// ... its ragged form (rans_amd_decode_batch under kVarBatchGroups): eight STREAMS per wave, each with its own symbol count
+// ... its ragged form (rans_amd_decode_batch, kBatchFamilies): eight STREAMS per wave, each with its own symbol count
 // and output address, from eight streams on
 bool decode_batch_word_groups_applicable(const DecParams &p);
 hipError_t launch_decode_batch_word_groups(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // 32 chunks per wave, the byte format's 2-way layout over u8 symbols (cum2sym tables), same file
 bool decode_byte_pairs_applicable(const DecParams &p);
 hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
-// ... its ragged form (rans_amd_decode_batch under kVarBatchPairs): 32 STREAMS per wave, each with its own symbol count and
+// ... its ragged form (rans_amd_decode_batch, kBatchFamilies): 32 STREAMS per wave, each with its own symbol count and
 // output address, from 32 streams on, the tables and the wave rings inside the CU's 160 KiB of LDS
 bool decode_batch_byte_pairs_applicable(const DecParams &p);
 hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
@@ -92,11 +94,11 @@ hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipSt
 // three-kernel placement, the slot layout or sized slots (no fused placement)
 bool encode_word_groups_applicable(const EncParams &p);
 hipError_t launch_encode_word_groups(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
-// ... its ragged form (rans_amd_encode_batch[_ordered] under kVarBatchEncGroups): eight STREAMS per wave, each with its own
+// ... its ragged form (rans_amd_encode_batch[_ordered], kBatchFamilies): eight STREAMS per wave, each with its own
 // symbol count, symbol address and slot, from eight streams on
 bool encode_batch_word_groups_applicable(const EncParams &p);
 hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
-// the byte format's 2-way layout, ragged (rans_amd_encode_batch[_ordered] under kVarBatchEncPairs): 32 STREAMS per wave, each
+// the byte format's 2-way layout, ragged (rans_amd_encode_batch[_ordered], kBatchFamilies): 32 STREAMS per wave, each
 // with its own symbol count, symbol address and slot, from 32 streams on, scale_bits 8..16
 bool encode_batch_byte_pairs_applicable(const EncParams &p);
 hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
@@ -109,7 +111,7 @@ inline bool lanes_applicable(uint64_t nchunks, uint32_t n_ways)
 }
 hipError_t launch_decode_lanes(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
-// the ragged form of the 2-way rans64 lane decoder (rans_amd_decode_batch under kVarBatchLanes; decode_lanes.hip): 64 STREAMS
+// the ragged form of the 2-way rans64 lane decoder (rans_amd_decode_batch, kBatchFamilies; decode_lanes.hip): 64 STREAMS
 // per wave, one per lane, each with its own symbol count and output address, from 64 streams on, scale_bits 7..16, the tables
 // and at least one wave's rings inside the CU's 160 KiB of LDS (the launcher sizes the block from what the tables leave)
 bool decode_batch_r64_lanes_applicable(const DecParams &p);
@@ -119,5 +121,49 @@ hipError_t launch_decode_batch_r64_lanes(const DecParams &p, int num_cus, hipStr
 bool encode_lanes_fused(const EncParams &p, int num_cus);
 // true when launch_encode_lanes would take a staged kernel for this SIZED-slot request (EncParams::ovf_ctl): encode_lanes.hip
 bool encode_lanes_sized_ok(int format, const EncParams &p, int num_cus);
+
+// The streams-per-wave families of the ragged batches, in the order the launchers ask them: a context option sets the bit, and
+// a batch of the row's public format that the row's *_applicable accepts goes to the row's kernel; every other batch takes the
+// wave-per-stream kernels, under the options as well.  A decoder's row leaves the encoder's pair null and the other way round.
+// `streams` completes the option's E_ARG text.  (The ragged forms of the other lane kernels and of the 2-way rans64 ENCODER are
+// later work: one more row each.)
+struct BatchFamily {
+    int option; // RANS_AMD_OPT_*
+    const char *option_name;
+    uint32_t bit; // kVarBatch* in DecParams::variant / EncParams::variant
+    int format;
+    bool (*decode_applicable)(const DecParams &);
+    hipError_t (*launch_decode)(const DecParams &, int, hipStream_t, KernelId *);
+    bool (*encode_applicable)(const EncParams &);
+    hipError_t (*launch_encode)(const EncParams &, int, hipStream_t, KernelId *);
+    const char *streams;
+};
+#define RANS_BATCH_DECODER(opt, bit, fmt, kern, streams) {opt, #opt, bit, fmt, kern##_applicable, launch_##kern, nullptr, nullptr, streams}
+#define RANS_BATCH_ENCODER(opt, bit, fmt, kern, streams) {opt, #opt, bit, fmt, nullptr, nullptr, kern##_applicable, launch_##kern, streams}
+constexpr BatchFamily kBatchFamilies[] = {
+    RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_GROUPS, kVarBatchGroups, RANS_AMD_FMT_WORD, decode_batch_word_groups, "eight 8-way word streams per wave"),
+    RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_PAIRS, kVarBatchPairs, RANS_AMD_FMT_BYTE, decode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
+    RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_LANES, kVarBatchLanes, RANS_AMD_FMT_R64, decode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
+    RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_GROUPS, kVarBatchEncGroups, RANS_AMD_FMT_WORD, encode_batch_word_groups, "eight 8-way word streams per wave"),
+    RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_PAIRS, kVarBatchEncPairs, RANS_AMD_FMT_BYTE, encode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
+};
+#undef RANS_BATCH_DECODER
+#undef RANS_BATCH_ENCODER
+
+// the first family whose option is on and that takes this batch, or null: the wave-per-stream kernels
+inline const BatchFamily *decode_batch_family(uint32_t variant, int format, const DecParams &p)
+{
+    for (const BatchFamily &f : kBatchFamilies)
+        if (f.launch_decode && (variant & f.bit) && format == f.format && f.decode_applicable(p))
+            return &f;
+    return nullptr;
+}
+inline const BatchFamily *encode_batch_family(uint32_t variant, int format, const EncParams &p)
+{
+    for (const BatchFamily &f : kBatchFamilies)
+        if (f.launch_encode && (variant & f.bit) && format == f.format && f.encode_applicable(p))
+            return &f;
+    return nullptr;
+}
 
 } // namespace rans_amd

@@ -12,6 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 import _stream_rate as S
+from _kernel_rows import ROW
 from _oracle import FMT_ALIAS, FMT_BYTE, FMT_R64, FMT_WORD
 
 WAVES_PER_BLOCK = 16  # kDecBlockThreads / 64: no launcher uses a larger block
@@ -499,6 +500,308 @@ def finish_batch():
         c[(np.arange(n) // 64) % 2 == 1] = 255
         contents[g] = c
     return freqs, counts, contents
+
+
+# ---- what the five streams-per-wave families' GPU files share: d is the family's descriptor (tests/_kernel_rows.py), gpu the
+# ---- (R, ctx, torch, off) of option_contexts ------------------------------------------------------------------------------
+def option_contexts(option):
+    """The `gpu` fixture's body: a context with `option` on (only that option) and one with everything at its default, the
+    wave-per-stream kernels."""
+    import torch
+    assert torch.cuda.is_available(), "these tests need the GPU box"
+    import ryg_rans_amd as R
+    ctx = R.Context(0)
+    ctx.set_option(option, 1)
+    off = R.Context(0)
+    yield R, ctx, torch, off
+    off.close()
+    ctx.close()
+
+
+def padded(n, lengths, pad=200):
+    return list(lengths) + [pad] * (n - len(lengths))
+
+
+def wave_load_cases(loads, rows, few):
+    """Every row at the first wave-load, the rows `few` at the others."""
+    import pytest
+    for k, name in enumerate(loads):
+        for row in (few if k else rows):
+            yield pytest.param(name, row, id="%s-%s" % (name, row["id"]), marks=pytest.mark.gpu)
+
+
+def _wave_row(d):
+    """The main row's shape with the option off."""
+    return dict(d.main, **{d.side: d.wave_kernel})
+
+
+def check_option_takes_zero_or_one(gpu, oracle, d, align=4):
+    """Any other value is E_ARG and changes nothing; 0 restores the wave-per-stream kernel, 1 the family's -> the batch."""
+    import pytest
+    R, ctx, torch, _ = gpu
+    b = Batch(R, ctx, torch, oracle, d.main, np.array([300] * (d.streams + 1), dtype=np.uint32))
+    for bad in (2, -1):
+        with pytest.raises(R.RansAmdError) as e:
+            ctx.set_option(d.option, bad)
+        assert e.value.status == R.E_ARG
+    run_row(b, align)
+    ctx.set_option(d.option, 0)
+    try:
+        run_row(Batch(R, ctx, torch, oracle, _wave_row(d), b.counts), align)
+    finally:
+        ctx.set_option(d.option, 1)
+    run_row(b, align)
+    return b
+
+
+def check_other_shape_keeps_its_kernels(gpu, oracle, d, rid, n_streams):
+    R, ctx, torch, _ = gpu
+    row = ROW[rid]
+    assert row[d.side] != d.main[d.side]
+    b = Batch(R, ctx, torch, oracle, row, draw_lengths(n_streams, row["ways"], 29))
+    run_row(b, 4)  # (asserts the row's kernel names)
+    assert ctx.decode_errors() == 0
+
+
+def run_family_graph(tmp_path, d, name):
+    fmt, sb, option = d.graph
+    script = graph_decode_script(d.main["decode"], fmt=fmt, ways=d.ways, sb=sb, option=option) if d.side == "decode" else \
+        graph_encode_script(d.main["encode"], fmt, d.ways, sb, option)
+    run_graph_script(tmp_path, name, script)
+
+
+def check_decode_order(gpu, oracle, d, n, aligns):
+    import pytest
+    R, ctx, torch, _ = gpu
+    b = Batch(R, ctx, torch, oracle, d.main, draw_lengths(n, d.ways, 23))
+    for align in aligns:
+        c = Coded(b, align)
+        c.decode_all(None, "no order")
+        c.decode_all(b.dev(np.arange(n)[::-1], np.int32), "reversed identity")
+        d_order = ctx.batch_order(b.d_counts)
+        assert sorted(d_order.cpu().tolist()) == list(range(n))
+        c.decode_all(d_order, "batch_order")
+        lost = int(np.argmax(b.counts))  # (a stream with symbols: its range would show a write)
+        order = np.arange(n)
+        order[lost] = n
+        want = c.d_buf.cpu().numpy().copy()
+        lo = int(c.sym_offs[lost])
+        want[lo:lo + int(b.counts[lost])] = POISON
+        for name, cont, nbytes, offs, lens in c.containers():
+            out = torch.full_like(c.d_buf, b.poison())
+            with pytest.raises(R.RansAmdError) as e:
+                ctx.decode_batch(b.gm, cont, nbytes, offs, lens, c.d_sym, b.d_counts, d.ways, out, d_order=b.dev(order, np.int32))
+            assert e.value.status == R.E_CORRUPT and e.value.bad_streams == 1, (name, e.value.bad_streams)
+            assert ctx.last_decode_kernel() == d.main["decode"]
+            assert np.array_equal(out.cpu().numpy(), want), (name, "a named stream differs, or the stream without a position was written")
+    assert ctx.decode_errors() == 0
+
+
+def check_rate_phase_parking(gpu, oracle, d, row, rate, aligns, start_phases=None):
+    """rate: (freqs, counts, contents, phases) of a rate generator.  Each from three containers -- the GPU's, the oracle's and one
+    packed by hand at the phases (start_phases: the offsets mod 64 it must show) --, with and without batch_order, with the
+    option and without; all must equal the input."""
+    R, ctx, torch, off = gpu
+    freqs, counts, contents, phases = rate
+    b = Batch(R, ctx, torch, oracle, row, counts, contents=contents, freqs=freqs)
+    gm_off = off.model(d.fmt, b.freqs, row["sb"])
+    p_cont, p_starts, p_bytes = S.pack_at_phases(b.streams, phases, 64, order=np.random.default_rng(11).permutation(b.n))
+    assert start_phases is None or sorted(set(int(s) % 64 for s in p_starts)) == start_phases
+    d_lens = b.dev(b.lens, np.int32)
+    d_order = ctx.batch_order(b.d_counts)
+    for align in aligns:
+        cont, offs, lens, d_buf, d_sym, d_slot, sym_offs, slot_offs = run_row(b, align)  # (the GPU's and the oracle's container)
+        containers = (("gpu", cont, int(slot_offs[-1]), offs, lens),
+                      ("phases", b.dev(p_cont, np.uint8), p_bytes, b.dev(p_starts, np.int64), d_lens))
+        for cx, gm, kernel in ((ctx, b.gm, row["decode"]), (off, gm_off, d.wave_kernel)):
+            for name, c, nbytes, o, ln in containers:
+                for order in (None, d_order):
+                    out = torch.full_like(d_buf, b.poison())
+                    cx.decode_batch(gm, c, nbytes, o, ln, d_sym, b.d_counts, d.ways, out, d_order=order)
+                    assert cx.last_decode_kernel() == kernel, (cx.last_decode_kernel(), name)
+                    assert torch.equal(out, d_buf), (kernel, name, "align", align, "order" if order is not None else "no order")
+                    assert cx.decode_errors() == 0, (kernel, name)
+
+
+def check_damage_inside_one_wave_load(gpu, oracle, d, n, damaged, shorter_by, moved_to, accepted):
+    """n streams of 300..5000 symbols; four streams of the FIRST wave-load `damaged` = (flipped, short, moved, far): a byte
+    flipped in the flushed states, a length shortened by `shorter_by`, an offset replaced by moved_to(offset, length,
+    container_bytes), a sym_offset one symbol past out_syms.  bad_streams is what the wave-per-stream kernel reports for the same
+    damaged batch, one of `accepted`; the other streams, the padding and the guard are exact; the streams rejected on their
+    index entry (moved, far) are not written."""
+    import pytest
+    R, ctx, torch, off = gpu
+    counts = np.random.default_rng(17).integers(300, 5001, n).astype(np.uint32)
+    b = Batch(R, ctx, torch, oracle, d.main, counts)
+    gm_off = off.model(d.fmt, b.freqs, d.main["sb"])
+    flipped, short, moved, far = damaged
+    for align in (1, 4):
+        c = Coded(b, align)
+        for name, cont, nbytes, offs, lens in c.containers():
+            h_offs, h_lens = offs.cpu().numpy(), lens.cpu().numpy()
+            bad_cont = cont.clone()
+            bad_cont[int(h_offs[flipped]) + 1] ^= 0x40  # inside the flushed states
+            bad_lens = lens.clone()
+            bad_lens[short] -= shorter_by
+            bad_offs = offs.clone()
+            bad_offs[moved] = moved_to(int(h_offs[moved]), int(h_lens[moved]), nbytes)
+            bad_sym = c.d_sym.clone()
+            bad_sym[far] = c.d_buf.numel() - int(counts[far]) + 1  # one symbol past the end
+            reported = []
+            for cx, gm, kernel in ((ctx, b.gm, d.main["decode"]), (off, gm_off, d.wave_kernel)):
+                out = torch.full_like(c.d_buf, b.poison())
+                with pytest.raises(R.RansAmdError) as e:
+                    cx.decode_batch(gm, bad_cont, nbytes, bad_offs, bad_lens, bad_sym, b.d_counts, d.ways, out)
+                assert e.value.status == R.E_CORRUPT and cx.last_decode_kernel() == kernel, (name, cx.last_decode_kernel())
+                assert cx.decode_errors() == 0  # (reported and reset by that call)
+                reported.append(e.value.bad_streams)
+                got, want = out.cpu().numpy(), c.d_buf.cpu().numpy()
+                keep = np.ones(want.size, dtype=bool)
+                for s in damaged:
+                    keep[int(c.sym_offs[s]):int(c.sym_offs[s]) + int(counts[s])] = False
+                assert np.array_equal(got[keep], want[keep]), (name, kernel, "an undamaged stream, the padding or the guard differs")
+                for s in (far, moved):
+                    assert np.all(got[int(c.sym_offs[s]):int(c.sym_offs[s]) + int(counts[s])] == POISON), (name, kernel, "stream", s, "was written")
+                assert np.all(got[int(c.sym_offs[-1]):] == POISON) and got.size == int(c.sym_offs[-1]) + GUARD
+            print("bad_streams (the family's kernel, wave kernel):", name, "align", align, reported)
+            assert reported[0] == reported[1] and reported[0] in accepted, (name, align, reported)
+
+
+# ---- ... and the two encoder files
+def check_encode_order(gpu, oracle, cx, row, counts):
+    """No order, the reversed identity and batch_order's result give the same streams, offsets and lengths; an order with one
+    entry replaced by n_streams reports E_ARG, every stream still named is exact, and the stream that lost its position keeps
+    its slot's poison and its pre-filled index entries.  On context cx, which must report the row's encoder."""
+    import pytest
+    R, _, torch, _ = gpu
+    n = counts.size
+    b = Batch(R, cx, torch, oracle, row, counts)
+    d_buf, sym_offs, slot_offs = b.laid_out(4)
+    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
+    cap = int(slot_offs[-1])
+    d_order = cx.batch_order(b.d_counts)
+    assert sorted(d_order.cpu().tolist()) == list(range(n))
+    results = []
+    for name, order in (("no order", None), ("reversed identity", b.dev(np.arange(n)[::-1], np.int32)), ("batch_order", d_order)):
+        res = encode_poisoned(b, cx, b.gm, d_buf, d_sym, d_slot, cap, d_order=order)
+        assert cx.last_encode_kernel()[0] == row["encode"] and cx.last_encode_placement() == 2, (name, cx.last_encode_kernel())
+        cx.encode_status()
+        b.check_streams(res[0].cpu().numpy(), res[1].cpu().numpy().astype(np.uint64), res[2].cpu().numpy().view(np.uint32),
+                        "%s, %s" % (row["id"], name))
+        assert np.all(res[0].cpu().numpy()[cap:] == POISON)
+        results.append(res)
+    same_result(torch, results[0], results[1], n, "reversed identity")
+    same_result(torch, results[0], results[2], n, "batch_order")
+    lost = int(np.argmax(counts))
+    order = np.arange(n)
+    order[lost] = n
+    cont, offs, lens = encode_poisoned(b, cx, b.gm, d_buf, d_sym, d_slot, cap, d_order=b.dev(order, np.int32), sentinel=-77)
+    assert cx.last_encode_kernel()[0] == row["encode"], cx.last_encode_kernel()
+    with pytest.raises(R.RansAmdError) as e:
+        cx.encode_status()
+    assert e.value.status == R.E_ARG, row["id"]
+    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
+    for c in range(n):
+        lo, hi = int(slot_offs[c]), int(slot_offs[c + 1])
+        if c == lost:
+            assert h_offs[c] == -77 and h_lens[c] == -77, "the index entry of the stream without a position was written"
+            assert np.all(h[lo:hi] == POISON), "the slot of the stream without a position was written"
+        else:
+            ln = int(h_lens[c])
+            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, (row["id"], c)
+            assert np.array_equal(h[hi - ln:hi], b.streams[c]), (row["id"], "stream", c)
+    assert np.all(h[cap:] == POISON)
+
+
+def check_bad_slots(gpu, oracle, d):
+    """test_batch_encode_rejects_bad_slots' construction on 400 streams of the family's shape with the option on: every slot 32
+    bytes larger than its bound; a slot off 16 bytes on both sides (two streams), one a granule too small, one beyond out_cap --
+    each in a wave-load with valid streams.  E_SPACE, the rejected slots keep their poison and get lengths 0, every other stream
+    is exact, the first 16 bytes of every accepted slot are still poison, nothing is written behind the container."""
+    import pytest
+    R, ctx, torch, _ = gpu
+    counts = draw_lengths(400, d.ways, 71)
+    b = Batch(R, ctx, torch, oracle, d.main, counts)
+    d_buf, sym_offs, _ = b.laid_out(4)
+    bound = np.array([R.chunk_bound(d.fmt, int(c), d.ways) for c in counts], dtype=np.int64)
+    sizes = bound + 32
+    idx = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+    cap = int(idx[-1])
+    big = np.nonzero(counts >= 1000)[0]
+    off16, past = int(big[0]), 399
+    small = int(big[(big > off16 + 2) & (big < past - 1)][0])
+    bad_idx = idx.copy()
+    bad_idx[off16 + 1] += 8
+    bad_idx[small] = bad_idx[small + 1] - (bound[small] - 16)
+    rejected = {off16, off16 + 1, small, past}
+    assert len(rejected) == 4
+    for c in rejected:  # (its wave-load holds valid streams as well)
+        assert any(k not in rejected for k in range(d.streams * (c // d.streams), min(d.streams * (c // d.streams) + d.streams, 400)))
+    d_out = torch.full((cap + 4096,), POISON, dtype=torch.uint8, device="cuda")
+    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, b.dev(sym_offs, np.int64), b.d_counts, d.ways, b.dev(bad_idx, np.int64), d_out=d_out,
+                                        out_cap=cap - 16)
+    assert ctx.last_encode_kernel()[0] == d.main["encode"], ctx.last_encode_kernel()
+    with pytest.raises(R.RansAmdError) as e:
+        ctx.encode_status()
+    assert e.value.status == R.E_SPACE
+    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
+    for c in range(b.n):
+        lo, hi = int(bad_idx[c]), int(bad_idx[c + 1])
+        if c in rejected:
+            assert h_lens[c] == 0 and int(h_offs[c]) == hi, c
+            if hi > lo:
+                assert np.all(h[lo:hi] == POISON), ("a rejected slot was written", c)
+        else:
+            ln = int(h_lens[c])
+            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, c
+            assert np.array_equal(h[hi - ln:hi], b.streams[c]), ("stream", c)
+            assert np.all(h[lo:lo + 16] == POISON), ("the head of a slot was written", c)
+    assert np.all(h[cap:] == POISON), "written behind the container"
+
+
+def check_no_false_e_model(gpu, oracle, d, no_zero):
+    """no_zero: no_zero_batch's arguments.  encode_status() is OK (run_row asks) and every stream is the oracle's, at both
+    alignments."""
+    R, ctx, torch, _ = gpu
+    freqs, counts, contents = no_zero_batch(*no_zero)
+    assert freqs[0] == 0 and all(not np.any(c == 0) for c in contents.values())
+    b = Batch(R, ctx, torch, oracle, d.main, counts, contents=contents, freqs=freqs)
+    for align in (4, 1):
+        run_row(b, align)
+
+
+def check_true_e_model(gpu, oracle, d, no_zero):
+    """The same batch with one symbol of the longest stream of the second wave-load overwritten by 0 on the device: E_MODEL, as
+    the default context reports for the same batch; every stream of the other wave-loads is the oracle's; the poison behind
+    out_cap is intact; the next call succeeds, on the family's kernel."""
+    import pytest
+    R, ctx, torch, off = gpu
+    freqs, counts, contents = no_zero_batch(*no_zero)
+    b = Batch(R, ctx, torch, oracle, d.main, counts, contents=contents, freqs=freqs)
+    gm_off = off.model(d.fmt, freqs, d.main["sb"])
+    d_buf, sym_offs, slot_offs = b.laid_out(4)
+    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
+    victim = d.streams + int(np.argmax(counts[d.streams:2 * d.streams]))
+    assert counts[victim] >= 256
+    bad = d_buf.clone()
+    bad[int(sym_offs[victim]) + int(counts[victim]) // 2] = 0
+    cap = int(slot_offs[-1])
+    for cx, gm, kernel in ((ctx, b.gm, d.main["encode"]), (off, gm_off, d.wave_kernel)):
+        cont, offs, lens = encode_poisoned(b, cx, gm, bad, d_sym, d_slot, cap)
+        assert cx.last_encode_kernel()[0] == kernel, cx.last_encode_kernel()
+        with pytest.raises(R.RansAmdError) as e:
+            cx.encode_status()
+        assert e.value.status == R.E_MODEL, kernel
+        h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
+        for c in range(b.n):
+            if c // d.streams != victim // d.streams:
+                a = int(h_offs[c])
+                assert h_lens[c] == b.lens[c] and a + int(h_lens[c]) == int(slot_offs[c + 1]), (kernel, c)
+                assert np.array_equal(h[a:a + int(h_lens[c])], b.streams[c]), (kernel, "stream", c)
+        assert np.all(h[cap:] == POISON), (kernel, "written behind the container")
+    ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, d.ways, d_slot)  # the next call succeeds
+    assert ctx.last_encode_kernel()[0] == d.main["encode"]
+    ctx.encode_status()
 
 
 # ---- the captured-graph tests' child programs ---------------------------------------------------------------------------

@@ -1,85 +1,26 @@
-"""What tests/test_batch_lanes_host.py and tests/test_gpu_batch_lanes.py share: the rows of the ragged 2-way rans64 lane decoder
-(k_decode_batch_r64_lanes, RANS_AMD_OPT_BATCH_LANES), the reader of the registry's second list, the rate inputs whose bounds
-the host file proves, and the damage catalogue with every verdict worked out on the CPU.
+"""What tests/test_batch_lanes_host.py and tests/test_gpu_batch_lanes.py share: the single wave-loads of the ragged 2-way rans64
+lane decoder (k_decode_batch_r64_lanes, RANS_AMD_OPT_BATCH_LANES; its rows are tests/_kernel_rows.py's LANE_ROWS), the rate inputs
+whose bounds the host file proves, and the damage catalogue with every verdict worked out on the CPU.
 
-The registry's second list (RANS_AMD_KERNEL_NAMES_LANES of ryg_rans_amd/csrc/kernel_names.hpp, family batch_r64_lanes_decode)
-is printed by tests/kernel_names_batch_lanes_driver.cpp; lane_registry() reads it the way _kernel_rows.registry() reads the
-first list.  Nothing here needs a GPU: symbols are Oracle.gen_zipf's (bit-identical to bench.gen_zipf), streams the oracle's,
-verdicts tests/_verdict.py's plain reference decoder's."""
-import functools
-import os
-import subprocess
-
+Nothing here needs a GPU: symbols are Oracle.gen_zipf's (bit-identical to bench.gen_zipf), streams the oracle's, verdicts
+tests/_verdict.py's plain reference decoder's."""
 import numpy as np
 
 import _stream_rate as S
 import _verdict as V
-from _batch import mandatory_lengths
+from _batch import mandatory_lengths, padded
 from _oracle import FMT_R64
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
-
-BATCH_R64_LANES_DECODE = "batch_r64_lanes_decode"
-LANE_FAMILIES = (BATCH_R64_LANES_DECODE,)
-LANE_KERNEL = "k_decode_batch_r64_lanes"
-WAVE_KERNEL = "k_decode_batch<r64>"  # what every row reports with the option off
-
-
-@functools.lru_cache(maxsize=None)
-def lane_registry():
-    """{family: set of names}: every entry of the registry's second list, as its driver prints them."""
-    build = os.path.join(ROOT, "build", "kernel_names")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "kernel_names_batch_lanes_driver")
-    subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Werror", "-I", CSRC, "-o", exe,
-                    os.path.join(HERE, "kernel_names_batch_lanes_driver.cpp")], check=True)
-    lines = [ln.split("\t") for ln in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()]
-    names = [name for _, name in lines]
-    assert len(set(names)) == len(names), ("a name occurs twice in the second list", names)
-    out = {f: set() for f in LANE_FAMILIES}
-    for family, name in lines:
-        out[family].add(name)  # (a family this module does not know: KeyError)
-    return out
-
-
-def lane_registry_lines():
-    lane_registry()
-    exe = os.path.join(ROOT, "build", "kernel_names", "kernel_names_batch_lanes_driver")
-    return subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
-
-
-def _lane_row(rid, sb, K):
-    return {"id": rid, "fmt": FMT_R64, "sb": sb, "K": K, "ways": 2, "decode": LANE_KERNEL, "encode": "k_encode_batch<r64>"}
-
-
-LANE_ROWS = [
-    _lane_row("r64-2-lanes", 14, 256),            # the reference's scale_bits (main64.cpp)
-    _lane_row("r64-2-lanes-16bit", 16, 256),      # 64 KiB of cum2sym: eleven waves per block
-    _lane_row("r64-2-lanes-12bit", 12, 256),
-    _lane_row("r64-2-lanes-64sym-7bit", 7, 64),   # the smallest cum2sym table (2^7 slots hold no 256 symbols)
-    _lane_row("r64-2-lanes-64sym-10bit", 10, 64),
-]
-LROW = {r["id"]: r for r in LANE_ROWS}
-LMAIN, L16 = LROW["r64-2-lanes"], LROW["r64-2-lanes-16bit"]
-RATE_ROW = {14: LMAIN, 16: L16}
-
-
 # ---- single wave-loads: the smallest shapes at which the parking can go wrong ---------------------------------------------
-def _padded(lengths, n=64, pad=200):
-    return list(lengths) + [pad] * (n - len(lengths))
-
-
 WAVE_LOADS = {
     "one-trip-each": [64] * 64,
-    "boundaries": _padded([0, 1, 2, 3, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193]),
+    "boundaries": padded(64, [0, 1, 2, 3, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 192, 193]),
     "63-parked-1023-trips": [65536] + [127] * 63,
     "every-lane-parks-elsewhere": [64 * (l % 16 + 1) + l for l in range(64)],
     "quad-mates-differ": [640, 0, 64, 385] * 16,
     "all-empty": [0] * 64,
     "second-load-of-one": [300] * 65,
-    "mandatory-and-200s": _padded(mandatory_lengths(2)),
+    "mandatory-and-200s": padded(64, mandatory_lengths(2)),
 }
 ALIGNS = (1, 4, 64)
 

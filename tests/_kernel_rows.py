@@ -5,8 +5,10 @@ name, family.  registry() compiles tests/kernel_names_driver.cpp (g++, no HIP) a
 `test_no_*_without_a_row` holds its names to its table below, in both directions.  The tables name, per shape, the kernels
 the library must report for it; the GPU files run the rows.  Option numbers are ryg_rans_amd.OPT_*.
 """
+import collections
 import functools
 import os
+import re
 import subprocess
 
 import ryg_rans_amd as R
@@ -20,8 +22,9 @@ CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
 UNIFORM, BATCH, BATCH_MODELS = "uniform", "batch", "batch_models"
 BATCH_WORD_GROUPS_DECODE, BATCH_WORD_GROUPS_ENCODE = "batch_word_groups_decode", "batch_word_groups_encode"
 BATCH_BYTE_PAIRS_DECODE, BATCH_BYTE_PAIRS_ENCODE = "batch_byte_pairs_decode", "batch_byte_pairs_encode"
+BATCH_R64_LANES_DECODE = "batch_r64_lanes_decode"
 FAMILIES = (UNIFORM, BATCH, BATCH_MODELS, BATCH_WORD_GROUPS_DECODE, BATCH_WORD_GROUPS_ENCODE, BATCH_BYTE_PAIRS_DECODE,
-            BATCH_BYTE_PAIRS_ENCODE)
+            BATCH_BYTE_PAIRS_ENCODE, BATCH_R64_LANES_DECODE)
 
 
 @functools.lru_cache(maxsize=None)
@@ -45,7 +48,25 @@ def registry():
 # context options (the numbers are the ABI's, tests/test_abi.py)
 LANE_FUSED, FUSED, DUAL = R.OPT_LANE_FUSED_PLACEMENT, R.OPT_FUSED_PLACEMENT, R.OPT_DUAL_DECODE
 OPT_BATCH_GROUPS, OPT_BATCH_ENCODE_GROUPS = R.OPT_BATCH_GROUPS, R.OPT_BATCH_ENCODE_GROUPS
-OPT_BATCH_PAIRS, OPT_BATCH_ENCODE_PAIRS = R.OPT_BATCH_PAIRS, R.OPT_BATCH_ENCODE_PAIRS
+OPT_BATCH_PAIRS, OPT_BATCH_ENCODE_PAIRS, OPT_BATCH_LANES = R.OPT_BATCH_PAIRS, R.OPT_BATCH_ENCODE_PAIRS, R.OPT_BATCH_LANES
+OPTIONS = ("LANE_KERNELS", "LANE_FUSED_PLACEMENT", "FUSED_PLACEMENT", "DUAL_DECODE", "ENC_SCRATCH_RING", "BATCH_GROUPS",
+           "BATCH_ENCODE_GROUPS", "BATCH_PAIRS", "BATCH_ENCODE_PAIRS", "BATCH_LANES")  # RANS_AMD_OPT_*, by value
+
+
+def check_option_constant(name, value):
+    """RANS_AMD_OPT_<name> is `value` in the header and in the package, every option 0..9 is where it was, the version has not
+    moved (additions only), and a NULL context is refused before the option is looked at (the values need a context: the
+    family's GPU file)."""
+    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
+    assert OPTIONS[value] == name
+    for v, n in enumerate(OPTIONS):
+        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % n, header)
+        assert m and int(m.group(1)) == v, n
+        assert getattr(R, "OPT_" + n) == v, n
+    assert re.search(r"#define\s+RANS_AMD_VERSION\s+600\b", header)
+    assert R.lib().rans_amd_ctx_set_option(None, value, 1) == R.E_ARG
+    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+
 
 # ---- uniform chunks (tests/test_gpu_kernel_matrix.py runs the rows) ---------------------------------------------------------
 DEFAULT_ROUNDS_SYMBOLS = 1 << 28
@@ -247,7 +268,7 @@ PAIR_ROWS = [
 ]
 PROW = {r["id"]: r for r in PAIR_ROWS}
 PMAIN = PROW["byte-2-pairs"]
-RATE_ROW = {16: PROW["byte-2-pairs-16bit"], 14: PMAIN}  # the rows of _batch.rate_batch / rate_wave, by scale_bits
+PAIR_RATE_ROW = {16: PROW["byte-2-pairs-16bit"], 14: PMAIN}  # the rows of _batch.rate_batch / rate_wave, by scale_bits
 
 
 # ... and encoder (tests/test_gpu_batch_encode_pairs.py)
@@ -265,3 +286,53 @@ ENC_PAIR_ROWS = [
 ]
 EROWS = {r["id"]: r for r in ENC_PAIR_ROWS}
 EMAIN, E16 = EROWS["byte-2-enc-pairs"], EROWS["byte-2-enc-pairs-16bit"]
+
+
+# ---- sixty-four 2-way rans64 streams per wave: decoder (tests/test_gpu_batch_lanes.py)
+def _lane_row(rid, sb, K):
+    return {"id": rid, "fmt": FMT_R64, "sb": sb, "K": K, "ways": 2, "decode": "k_decode_batch_r64_lanes", "encode": "k_encode_batch<r64>"}
+
+
+LANE_ROWS = [
+    _lane_row("r64-2-lanes", 14, 256),            # the reference's scale_bits (main64.cpp)
+    _lane_row("r64-2-lanes-16bit", 16, 256),      # 64 KiB of cum2sym: eleven waves per block
+    _lane_row("r64-2-lanes-12bit", 12, 256),
+    _lane_row("r64-2-lanes-64sym-7bit", 7, 64),   # the smallest cum2sym table (2^7 slots hold no 256 symbols)
+    _lane_row("r64-2-lanes-64sym-10bit", 10, 64),
+]
+LROW = {r["id"]: r for r in LANE_ROWS}
+LMAIN, LANE16 = LROW["r64-2-lanes"], LROW["r64-2-lanes-16bit"]  # (L16 is the lane ENCODER's name above)
+LANE_RATE_ROW = {14: LMAIN, 16: LANE16}  # the rows of _batch_lanes.rate_batch, by scale_bits
+
+# ---- the five streams-per-wave families, one descriptor each: what their GPU and host files differ in -----------------------
+# side: the row key of the family's own kernel; streams: per wave; wave_kernel: what the main row's shape reports with the option
+# off; shapes: the (sb, K) of the rows; graph: the captured-graph child's format, scale_bits and option, by name
+Family = collections.namedtuple("Family", "option side fmt ways streams rows main wave_kernel family shapes graph")
+PAIR_SHAPES, LANE_SHAPES = [(8, 256), (10, 64), (12, 256), (14, 256), (16, 256)], [(7, 64), (10, 64), (12, 256), (14, 256), (16, 256)]
+GROUPS = Family(OPT_BATCH_GROUPS, "decode", FMT_WORD, 8, 8, GROUP_ROWS, GROW, "k_decode_batch<word>", BATCH_WORD_GROUPS_DECODE,
+                [(12, 256)], ("FMT_WORD", 12, "OPT_BATCH_GROUPS"))
+PAIRS = Family(OPT_BATCH_PAIRS, "decode", FMT_BYTE, 2, 32, PAIR_ROWS, PMAIN, "k_decode_batch<byte>", BATCH_BYTE_PAIRS_DECODE,
+               PAIR_SHAPES, ("FMT_BYTE", 14, "OPT_BATCH_PAIRS"))
+LANES = Family(OPT_BATCH_LANES, "decode", FMT_R64, 2, 64, LANE_ROWS, LMAIN, "k_decode_batch<r64>", BATCH_R64_LANES_DECODE,
+               LANE_SHAPES, ("FMT_R64", 14, "OPT_BATCH_LANES"))
+ENC_GROUPS = Family(OPT_BATCH_ENCODE_GROUPS, "encode", FMT_WORD, 8, 8, ENC_GROUP_ROWS, EROW, "k_encode_batch<word>",
+                    BATCH_WORD_GROUPS_ENCODE, [(12, 256)], ("FMT_WORD", 12, "OPT_BATCH_ENCODE_GROUPS"))
+ENC_PAIRS = Family(OPT_BATCH_ENCODE_PAIRS, "encode", FMT_BYTE, 2, 32, ENC_PAIR_ROWS, EMAIN, "k_encode_batch<byte>",
+                   BATCH_BYTE_PAIRS_ENCODE, PAIR_SHAPES, ("FMT_BYTE", 14, "OPT_BATCH_ENCODE_PAIRS"))
+WAVE_ENCODER = {FMT_WORD: "k_encode_batch<word>", FMT_BYTE: "k_encode_batch<byte>", FMT_R64: "k_encode_batch<r64>"}
+
+
+def check_family_rows(d):
+    """Every name of the registry's family is the kernel of a row of the family's table on its side, and the table names no
+    kernel the registry does not hold; the rows are the family's shapes (a decoder's rows name the wave encoder); and the check
+    has teeth: without the family's rows its kernel is reported missing.  (Disjointness from the other families: registry()
+    asserts that no name occurs twice.)"""
+    names, kernel = registry()[d.family], d.main[d.side]
+    assert kernel in names
+    rows = {r[d.side] for r in d.rows}
+    assert names == rows, ("kernels no row expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
+    assert all(r["ways"] == d.ways and r["fmt"] == d.fmt for r in d.rows)
+    assert d.side == "encode" or all(r["encode"] == WAVE_ENCODER[d.fmt] for r in d.rows)
+    assert sorted((r["sb"], r["K"]) for r in d.rows) == d.shapes
+    less = {r[d.side] for r in d.rows if not r["id"].startswith(d.main["id"])}
+    assert kernel in names - less

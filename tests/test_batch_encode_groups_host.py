@@ -7,42 +7,24 @@ test_no_group_batch_enc_kernel_without_a_row: every name of the registry's batch
 (tests/_kernel_rows.py reads ryg_rans_amd/csrc/kernel_names.hpp) must be the encode name of a row of ENC_GROUP_ROWS, and
 ENC_GROUP_ROWS must name no encoder the registry does not hold."""
 import os
-import re
 
 import numpy as np
 
 import _stream_rate as S
 import ryg_rans_amd as R
 from _batch import NO_ZERO_OCTETS, RATE_OCTET_KINDS, finish_octet, no_zero_batch, rate_octet
-from _kernel_rows import BATCH_WORD_GROUPS_ENCODE, ENC_GROUP_ROWS, ROOT, registry
+from _kernel_rows import ENC_GROUPS, ROOT, check_family_rows, check_option_constant
 from _oracle import FMT_WORD
 
 
 def test_no_group_batch_enc_kernel_without_a_row():
     """(No count of assignment statements and no disjointness from other scans any more: the launchers report a KernelId, and
     registry() asserts that no name occurs twice.)"""
-    names = registry()[BATCH_WORD_GROUPS_ENCODE]
-    assert "k_encode_batch_word_groups" in names
-    rows = {r["encode"] for r in ENC_GROUP_ROWS}
-    assert names == rows, ("kernels no row of ENC_GROUP_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
-    # the check has teeth: without its row a kernel is reported missing
-    less = {r["encode"] for r in ENC_GROUP_ROWS if r["id"] != "word-8-enc-groups"}
-    assert "k_encode_batch_word_groups" in names - less
+    check_family_rows(ENC_GROUPS)
 
 
 def test_batch_encode_groups_option_constant():
-    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
-    m = re.search(r"RANS_AMD_OPT_BATCH_ENCODE_GROUPS\s*=\s*(\d+)", header)
-    assert m and int(m.group(1)) == 6
-    assert R.OPT_BATCH_ENCODE_GROUPS == 6
-    # the five older constants are where they were
-    older = ("LANE_KERNELS", "LANE_FUSED_PLACEMENT", "FUSED_PLACEMENT", "DUAL_DECODE", "ENC_SCRATCH_RING", "BATCH_GROUPS")
-    for value, name in enumerate(older):
-        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % name, header)
-        assert m and int(m.group(1)) == value and getattr(R, "OPT_" + name) == value, name
-    # (a NULL context is refused before the option is looked at; the values need a context: tests/test_gpu_batch_encode_groups.py)
-    assert R.lib().rans_amd_ctx_set_option(None, 6, 1) == R.E_ARG
-    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+    check_option_constant("BATCH_ENCODE_GROUPS", 6)
 
 
 def test_encode_batch_ordered_refuses_a_null_context():

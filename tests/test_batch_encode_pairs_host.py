@@ -5,9 +5,6 @@ tests/test_gpu_batch_encode_pairs.py reach the bounds that file claims.
 test_no_pair_batch_enc_kernel_without_a_row: every name of the registry's batch_byte_pairs_encode family (tests/_kernel_rows.py
 reads ryg_rans_amd/csrc/kernel_names.hpp) must be the encode name of a row of ENC_PAIR_ROWS, and ENC_PAIR_ROWS must name no
 encoder the registry does not hold."""
-import os
-import re
-
 import numpy as np
 
 import _batch as G
@@ -15,42 +12,21 @@ import _kernel_rows as K
 import _stream_rate as S
 import ryg_rans_amd as R
 from _batch import NO_ZERO_WAVE_LOADS, RATE_WAVES, rate_kind, rate_model
-from _kernel_rows import BATCH_BYTE_PAIRS_ENCODE, ENC_PAIR_ROWS, ROOT, registry
+from _kernel_rows import ENC_PAIR_ROWS, ENC_PAIRS, check_family_rows, check_option_constant
 from _oracle import FMT_BYTE
 
 
 def test_no_pair_batch_enc_kernel_without_a_row():
     """(No count of assignment statements and no disjointness from other scans any more: the launchers report a KernelId, and
     registry() asserts that no name occurs twice.)"""
-    names = registry()[BATCH_BYTE_PAIRS_ENCODE]
-    assert "k_encode_batch_byte_pairs" in names
-    rows = {r["encode"] for r in ENC_PAIR_ROWS}
-    assert names == rows, ("kernels no row of ENC_PAIR_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
-    assert all(r["ways"] == 2 and r["fmt"] == FMT_BYTE for r in ENC_PAIR_ROWS)
-    assert sorted((r["sb"], r["K"]) for r in ENC_PAIR_ROWS) == [(8, 256), (10, 64), (12, 256), (14, 256), (16, 256)]
+    check_family_rows(ENC_PAIRS)
     # the decoder is named where the issue names it, and asked of the default context elsewhere (None)
     assert {(r["sb"], r["decode"]) for r in ENC_PAIR_ROWS} == {(14, "k_decode_batch<byte>"), (16, "k_decode_batch<byte>"), (12, None), (8, None),
                                                               (10, None)}
-    # the check has teeth: without its rows the kernel is reported missing
-    less = {r["encode"] for r in ENC_PAIR_ROWS if not r["id"].startswith("byte-2-enc-pairs")}
-    assert "k_encode_batch_byte_pairs" in names - less
 
 
 def test_batch_encode_pairs_option_constant():
-    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
-    m = re.search(r"RANS_AMD_OPT_BATCH_ENCODE_PAIRS\s*=\s*(\d+)", header)
-    assert m and int(m.group(1)) == 8
-    assert R.OPT_BATCH_ENCODE_PAIRS == 8
-    # options 0..7 are where they were, and the version has not moved (additions only)
-    for name, value in (("LANE_KERNELS", 0), ("LANE_FUSED_PLACEMENT", 1), ("FUSED_PLACEMENT", 2), ("DUAL_DECODE", 3),
-                        ("ENC_SCRATCH_RING", 4), ("BATCH_GROUPS", 5), ("BATCH_ENCODE_GROUPS", 6), ("BATCH_PAIRS", 7)):
-        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % name, header)
-        assert m and int(m.group(1)) == value, name
-        assert getattr(R, "OPT_" + name) == value, name
-    assert re.search(r"#define\s+RANS_AMD_VERSION\s+600\b", header)
-    # (a NULL context is refused before the option is looked at; the values need a context: tests/test_gpu_batch_encode_pairs.py)
-    assert R.lib().rans_amd_ctx_set_option(None, 8, 1) == R.E_ARG
-    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+    check_option_constant("BATCH_ENCODE_PAIRS", 8)
 
 
 def _full_windows(rb, n):

@@ -1,9 +1,8 @@
 """Ragged batches with sixty-four 2-way rans64 streams per wave (RANS_AMD_OPT_BATCH_LANES), the part that needs no GPU: the
-option's constant, the registry's second list held to LANE_ROWS, the proof that the rate inputs of
+option's constant, the registry's family held to LANE_ROWS, a pin of the registry's one list, the proof that the rate inputs of
 tests/test_gpu_batch_lanes.py reach the bounds that file claims, and the verdict of every case of its damage catalogue, worked
 out by the plain reference decoder of tests/_verdict.py."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -11,61 +10,39 @@ import pytest
 
 import _batch_lanes as L
 import _stream_rate as S
-import ryg_rans_amd as R
-from _kernel_rows import ROOT, registry
+from _kernel_rows import BATCH_R64_LANES_DECODE, CSRC, LANES, ROOT, check_family_rows, check_option_constant, registry
 from _oracle import FMT_R64
 
 
 def test_batch_lanes_option_constant():
-    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
-    m = re.search(r"RANS_AMD_OPT_BATCH_LANES\s*=\s*(\d+)", header)
-    assert m and int(m.group(1)) == 9
-    assert R.OPT_BATCH_LANES == 9
-    # options 0..8 are where they were, and the version has not moved (additions only)
-    for name, value in (("LANE_KERNELS", 0), ("LANE_FUSED_PLACEMENT", 1), ("FUSED_PLACEMENT", 2), ("DUAL_DECODE", 3),
-                        ("ENC_SCRATCH_RING", 4), ("BATCH_GROUPS", 5), ("BATCH_ENCODE_GROUPS", 6), ("BATCH_PAIRS", 7),
-                        ("BATCH_ENCODE_PAIRS", 8)):
-        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % name, header)
-        assert m and int(m.group(1)) == value, name
-        assert getattr(R, "OPT_" + name) == value, name
-    assert re.search(r"#define\s+RANS_AMD_VERSION\s+600\b", header)
-    # (a NULL context is refused before the option is looked at; the values need a context: tests/test_gpu_batch_lanes.py)
-    assert R.lib().rans_amd_ctx_set_option(None, 9, 1) == R.E_ARG
-    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+    check_option_constant("BATCH_LANES", 9)
 
 
 def test_no_lane_batch_kernel_without_a_row():
-    """The second list's driver prints exactly one line; the family's names are the decode names of LANE_ROWS, in both
-    directions; and the check has teeth: without its rows the name is reported missing."""
-    assert L.lane_registry_lines() == ["batch_r64_lanes_decode\tk_decode_batch_r64_lanes"]
-    names = L.lane_registry()[L.BATCH_R64_LANES_DECODE]
-    rows = {r["decode"] for r in L.LANE_ROWS}
-    assert names == rows, ("kernels no row of LANE_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
-    assert all(r["ways"] == 2 and r["fmt"] == FMT_R64 and r["encode"] == "k_encode_batch<r64>" for r in L.LANE_ROWS)
-    assert sorted((r["sb"], r["K"]) for r in L.LANE_ROWS) == [(7, 64), (10, 64), (12, 256), (14, 256), (16, 256)]
-    less = {r["decode"] for r in L.LANE_ROWS if not r["id"].startswith("r64-2-lanes")}
-    assert "k_decode_batch_r64_lanes" in names - less
-    # no name of the second list is one of the first
-    first = set().union(*registry().values())
-    assert not (names & first)
+    """The family holds exactly one name; the family's names are the decode names of LANE_ROWS, in both directions; and the
+    check has teeth: without its rows the name is reported missing."""
+    check_family_rows(LANES)
+    assert registry()[BATCH_R64_LANES_DECODE] == {"k_decode_batch_r64_lanes"}
 
 
-def test_the_first_list_is_what_it_was():
-    """tests/kernel_names_driver.cpp still prints its 51 lines, none of them of the new family."""
+def test_the_one_list_is_what_it_is():
+    """tests/kernel_names_driver.cpp prints the registry's 52 lines: the 51 it always printed, in their order, and the lane
+    family's one behind them (its id stays what it was)."""
     registry()
     exe = os.path.join(ROOT, "build", "kernel_names", "kernel_names_driver")
     lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
-    assert len(lines) == 51 and lines[0] == "uniform\tk_decode_word64" and lines[-1] == "batch_byte_pairs_encode\tk_encode_batch_byte_pairs"
-    assert not any("r64_lanes" in ln for ln in lines)
+    assert len(lines) == 52 and lines[0] == "uniform\tk_decode_word64"
+    assert lines[50] == "batch_byte_pairs_encode\tk_encode_batch_byte_pairs" and lines[51] == "batch_r64_lanes_decode\tk_decode_batch_r64_lanes"
+    assert [ln for ln in lines if "r64_lanes" in ln] == lines[51:]
 
 
-def test_a_name_in_neither_list_does_not_compile(tmp_path):
+def test_a_name_not_in_the_list_does_not_compile(tmp_path):
     src = tmp_path / "no_such_kernel.cpp"
     src.write_text('#include "kernel_names.hpp"\nint main() { return (int)rans_amd::KernelId::decode_batch_r64_lanes_no_such; }\n')
-    r = subprocess.run(["g++", "-std=c++17", "-I", L.CSRC, "-fsyntax-only", str(src)], capture_output=True, text=True)
+    r = subprocess.run(["g++", "-std=c++17", "-I", CSRC, "-fsyntax-only", str(src)], capture_output=True, text=True)
     assert r.returncode != 0 and "decode_batch_r64_lanes_no_such" in r.stderr
     src.write_text('#include "kernel_names.hpp"\nint main() { return (int)rans_amd::KernelId::decode_batch_r64_lanes; }\n')
-    assert subprocess.run(["g++", "-std=c++17", "-I", L.CSRC, "-fsyntax-only", str(src)]).returncode == 0
+    assert subprocess.run(["g++", "-std=c++17", "-I", CSRC, "-fsyntax-only", str(src)]).returncode == 0
 
 
 def test_rate_inputs_reach_the_rings_bound():

@@ -5,48 +5,24 @@ reach the bounds that file claims.
 test_no_pair_batch_kernel_without_a_row: every name of the registry's batch_byte_pairs_decode family (tests/_kernel_rows.py
 reads ryg_rans_amd/csrc/kernel_names.hpp) must be the decode name of a row of PAIR_ROWS, and PAIR_ROWS must name no decoder
 the registry does not hold."""
-import os
-import re
-
 import numpy as np
 
 import _batch as G
 import _kernel_rows as K
 import _stream_rate as S
 import ryg_rans_amd as R
-from _kernel_rows import BATCH_BYTE_PAIRS_DECODE, PAIR_ROWS, ROOT, registry
+from _kernel_rows import PAIRS, check_family_rows, check_option_constant
 from _oracle import FMT_BYTE
 
 
 def test_no_pair_batch_kernel_without_a_row():
     """(No count of assignment statements and no disjointness from other scans any more: the launchers report a KernelId, and
     registry() asserts that no name occurs twice.)"""
-    names = registry()[BATCH_BYTE_PAIRS_DECODE]
-    assert "k_decode_batch_byte_pairs" in names
-    rows = {r["decode"] for r in PAIR_ROWS}
-    assert names == rows, ("kernels no row of PAIR_ROWS expects", sorted(names - rows), "names no launcher reports", sorted(rows - names))
-    assert all(r["ways"] == 2 and r["fmt"] == FMT_BYTE and r["encode"] == "k_encode_batch<byte>" for r in PAIR_ROWS)
-    assert sorted((r["sb"], r["K"]) for r in PAIR_ROWS) == [(8, 256), (10, 64), (12, 256), (14, 256), (16, 256)]
-    # the check has teeth: without its rows the kernel is reported missing
-    less = {r["decode"] for r in PAIR_ROWS if not r["id"].startswith("byte-2-pairs")}
-    assert "k_decode_batch_byte_pairs" in names - less
+    check_family_rows(PAIRS)
 
 
 def test_batch_pairs_option_constant():
-    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
-    m = re.search(r"RANS_AMD_OPT_BATCH_PAIRS\s*=\s*(\d+)", header)
-    assert m and int(m.group(1)) == 7
-    assert R.OPT_BATCH_PAIRS == 7
-    # options 0..6 are where they were, and the version has not moved (additions only)
-    for name, value in (("LANE_KERNELS", 0), ("LANE_FUSED_PLACEMENT", 1), ("FUSED_PLACEMENT", 2), ("DUAL_DECODE", 3),
-                        ("ENC_SCRATCH_RING", 4), ("BATCH_GROUPS", 5), ("BATCH_ENCODE_GROUPS", 6)):
-        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % name, header)
-        assert m and int(m.group(1)) == value, name
-        assert getattr(R, "OPT_" + name) == value, name
-    assert re.search(r"#define\s+RANS_AMD_VERSION\s+600\b", header)
-    # (a NULL context is refused before the option is looked at; the values need a context: tests/test_gpu_batch_pairs.py)
-    assert R.lib().rans_amd_ctx_set_option(None, 7, 1) == R.E_ARG
-    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+    check_option_constant("BATCH_PAIRS", 7)
 
 
 def test_rate_inputs_reach_the_rings_bound():
@@ -61,7 +37,7 @@ def test_rate_inputs_reach_the_rings_bound():
         stream's.)
     The inputs are the GPU file's own generators (tests/_batch.py)."""
     assert K.OPT_BATCH_PAIRS == R.OPT_BATCH_PAIRS and K.OPT_BATCH_GROUPS == R.OPT_BATCH_GROUPS  # (the option these inputs are decoded under)
-    assert 16 in G.RATE_BITS and K.RATE_ROW[16]["sb"] == 16
+    assert 16 in G.RATE_BITS and K.PAIR_RATE_ROW[16]["sb"] == 16
     freqs, counts, contents, phases = G.rate_batch(16)
     b_freqs = np.ones(256, dtype=np.uint32)
     b_freqs[S.COMMON] = (1 << 16) - 255

@@ -19,24 +19,18 @@ Wall time on an MI355X: 12.7 s for the 21 cases of this file -- 6.0 s of it the 
 import numpy as np
 import pytest
 
-from _batch import (NO_ZERO_OCTETS, POISON, Batch, draw_lengths, draw_log_uniform, encode_poisoned, finish_octet, graph_encode_script,
-                    mandatory_lengths, no_zero_batch, rate_octet, resident_waves, run_graph_script, run_row, same_result)
-from _kernel_rows import EROW, OPT_BATCH_ENCODE_GROUPS, OPT_BATCH_GROUPS, ROW
+from _batch import (NO_ZERO_OCTETS, Batch, check_bad_slots, check_encode_order, check_no_false_e_model, check_option_takes_zero_or_one,
+                    check_other_shape_keeps_its_kernels, check_true_e_model, draw_lengths, draw_log_uniform, finish_octet, mandatory_lengths,
+                    option_contexts, rate_octet, resident_waves, run_family_graph, run_row, same_result)
+from _kernel_rows import ENC_GROUPS, EROW, OPT_BATCH_ENCODE_GROUPS, OPT_BATCH_GROUPS, ROW
 from _oracle import FMT_WORD
 
-WAVE = "k_encode_batch<word>"
+WAVE = ENC_GROUPS.wave_kernel
+
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    import ryg_rans_amd as R
-    ctx = R.Context(0)
-    ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 1)  # (only the new option)
-    off = R.Context(0)  # everything at its default: the wave-per-stream kernels
-    yield R, ctx, torch, off
-    off.close()
-    ctx.close()
+    yield from option_contexts(OPT_BATCH_ENCODE_GROUPS)
 
 
 OCTETS = {
@@ -96,44 +90,14 @@ def test_no_false_e_model_from_parked_groups(gpu, oracle):
     """A model without byte value 0, contents that never use it, uneven lengths: dead groups are fed zeros and read the
     record of byte value 0, which must not reach the flags.  encode_status() is OK (run_row asks) and every stream is the
     oracle's."""
-    R, ctx, torch, _ = gpu
-    freqs, counts, contents = no_zero_batch(*NO_ZERO_OCTETS)
-    assert freqs[0] == 0 and all(not np.any(c == 0) for c in contents.values())
-    b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
-    for align in (4, 1):
-        run_row(b, align)
+    check_no_false_e_model(gpu, oracle, ENC_GROUPS, NO_ZERO_OCTETS)
 
 
 @pytest.mark.gpu
 def test_true_e_model_is_reported_and_contained(gpu, oracle):
     """The same batch with one symbol of one stream overwritten by 0 on the device: E_MODEL, as the default context reports
     for the same batch; every stream of the other octets is the oracle's; nothing is written outside the container."""
-    R, ctx, torch, off = gpu
-    freqs, counts, contents = no_zero_batch(*NO_ZERO_OCTETS)
-    b = Batch(R, ctx, torch, oracle, EROW, counts, contents=contents, freqs=freqs)
-    gm_off = off.model(FMT_WORD, freqs, 12)
-    d_buf, sym_offs, slot_offs = b.laid_out(4)
-    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
-    victim = 8 + int(np.argmax(counts[8:16]))  # (the longest stream of the second octet)
-    assert counts[victim] >= 256
-    bad = d_buf.clone()
-    bad[int(sym_offs[victim]) + int(counts[victim]) // 2] = 0
-    cap = int(slot_offs[-1])
-    for cx, gm, kernel in ((ctx, b.gm, EROW["encode"]), (off, gm_off, WAVE)):
-        cont, offs, lens = encode_poisoned(b, cx, gm, bad, d_sym, d_slot, cap)
-        assert cx.last_encode_kernel()[0] == kernel, cx.last_encode_kernel()
-        with pytest.raises(R.RansAmdError) as e:
-            cx.encode_status()
-        assert e.value.status == R.E_MODEL, kernel
-        h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
-        for c in range(b.n):
-            if c // 8 != victim // 8:
-                a = int(h_offs[c])
-                assert h_lens[c] == b.lens[c] and a + int(h_lens[c]) == int(slot_offs[c + 1]), (kernel, c)
-                assert np.array_equal(h[a:a + int(h_lens[c])], b.streams[c]), (kernel, "stream", c)
-        assert np.all(h[cap:] == POISON), (kernel, "written behind the container")
-    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, 8, d_slot)  # the next call succeeds
-    ctx.encode_status()
+    check_true_e_model(gpu, oracle, ENC_GROUPS, NO_ZERO_OCTETS)
 
 
 @pytest.mark.gpu
@@ -142,46 +106,10 @@ def test_order(gpu, oracle):
     order with one entry replaced by n_streams reports E_ARG, every stream still named is exact, and the stream that lost
     its position keeps its slot's poison and its pre-filled index entries.  The same on the default context and on a
     64-way batch, which report the wave kernel."""
-    R, ctx, torch, off = gpu
-    n = 17
-    counts = draw_lengths(n, 8, 23)
+    _, ctx, _, off = gpu
+    counts = draw_lengths(17, 8, 23)
     for cx, row in ((ctx, EROW), (off, ROW["word-8"]), (ctx, ROW["word-64"])):
-        b = Batch(R, cx, torch, oracle, row, counts)
-        d_buf, sym_offs, slot_offs = b.laid_out(4)
-        d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
-        cap = int(slot_offs[-1])
-        d_order = cx.batch_order(b.d_counts)
-        assert sorted(d_order.cpu().tolist()) == list(range(n))
-        results = []
-        for name, order in (("no order", None), ("reversed identity", b.dev(np.arange(n)[::-1], np.int32)), ("batch_order", d_order)):
-            res = encode_poisoned(b, cx, b.gm, d_buf, d_sym, d_slot, cap, d_order=order)
-            assert cx.last_encode_kernel()[0] == row["encode"] and cx.last_encode_placement() == 2, (name, cx.last_encode_kernel())
-            cx.encode_status()
-            b.check_streams(res[0].cpu().numpy(), res[1].cpu().numpy().astype(np.uint64), res[2].cpu().numpy().view(np.uint32),
-                            "%s, %s" % (row["id"], name))
-            assert np.all(res[0].cpu().numpy()[cap:] == POISON)
-            results.append(res)
-        same_result(torch, results[0], results[1], n, "reversed identity")
-        same_result(torch, results[0], results[2], n, "batch_order")
-        lost = int(np.argmax(counts))
-        order = np.arange(n)
-        order[lost] = n
-        cont, offs, lens = encode_poisoned(b, cx, b.gm, d_buf, d_sym, d_slot, cap, d_order=b.dev(order, np.int32), sentinel=-77)
-        assert cx.last_encode_kernel()[0] == row["encode"], cx.last_encode_kernel()
-        with pytest.raises(R.RansAmdError) as e:
-            cx.encode_status()
-        assert e.value.status == R.E_ARG, row["id"]
-        h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
-        for c in range(n):
-            lo, hi = int(slot_offs[c]), int(slot_offs[c + 1])
-            if c == lost:
-                assert h_offs[c] == -77 and h_lens[c] == -77, "the index entry of the stream without a position was written"
-                assert np.all(h[lo:hi] == POISON), "the slot of the stream without a position was written"
-            else:
-                ln = int(h_lens[c])
-                assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, (row["id"], c)
-                assert np.array_equal(h[hi - ln:hi], b.streams[c]), (row["id"], "stream", c)
-        assert np.all(h[cap:] == POISON)
+        check_encode_order(gpu, oracle, cx, row, counts)
 
 
 @pytest.mark.gpu
@@ -216,44 +144,7 @@ def test_bad_slots(gpu, oracle):
     than its bound; a slot off 16 bytes on both sides (two streams), one a granule too small, one beyond out_cap -- each in
     an octet with valid streams.  E_SPACE, the rejected slots keep their poison and get lengths 0, every other stream is
     exact, the first 16 bytes of every accepted slot are still poison, nothing is written behind the container."""
-    R, ctx, torch, _ = gpu
-    counts = draw_lengths(400, 8, 71)
-    b = Batch(R, ctx, torch, oracle, EROW, counts)
-    d_buf, sym_offs, _ = b.laid_out(4)
-    bound = np.array([R.chunk_bound(FMT_WORD, int(c), 8) for c in counts], dtype=np.int64)
-    sizes = bound + 32
-    idx = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
-    cap = int(idx[-1])
-    big = np.nonzero(counts >= 1000)[0]
-    off16, past = int(big[0]), 399
-    small = int(big[(big > off16 + 2) & (big < past - 1)][0])
-    bad_idx = idx.copy()
-    bad_idx[off16 + 1] += 8
-    bad_idx[small] = bad_idx[small + 1] - (bound[small] - 16)
-    rejected = {off16, off16 + 1, small, past}
-    assert len(rejected) == 4
-    for c in rejected:  # (its octet holds valid streams as well)
-        assert any(k not in rejected for k in range(8 * (c // 8), min(8 * (c // 8) + 8, 400)))
-    d_out = torch.full((cap + 4096,), POISON, dtype=torch.uint8, device="cuda")
-    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, b.dev(sym_offs, np.int64), b.d_counts, 8, b.dev(bad_idx, np.int64), d_out=d_out,
-                                        out_cap=cap - 16)
-    assert ctx.last_encode_kernel()[0] == EROW["encode"], ctx.last_encode_kernel()
-    with pytest.raises(R.RansAmdError) as e:
-        ctx.encode_status()
-    assert e.value.status == R.E_SPACE
-    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
-    for c in range(b.n):
-        lo, hi = int(bad_idx[c]), int(bad_idx[c + 1])
-        if c in rejected:
-            assert h_lens[c] == 0 and int(h_offs[c]) == hi, c
-            if hi > lo:
-                assert np.all(h[lo:hi] == POISON), ("a rejected slot was written", c)
-        else:
-            ln = int(h_lens[c])
-            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, c
-            assert np.array_equal(h[hi - ln:hi], b.streams[c]), ("stream", c)
-            assert np.all(h[lo:lo + 16] == POISON), ("the head of a slot was written", c)
-    assert np.all(h[cap:] == POISON), "written behind the container"
+    check_bad_slots(gpu, oracle, ENC_GROUPS)
 
 
 @pytest.mark.gpu
@@ -261,31 +152,15 @@ def test_bad_slots(gpu, oracle):
 def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_streams):
     """64-way, u16 symbols, fewer than eight 8-way streams and the byte format take the wave-per-stream kernels on the
     context with the option on, and code right."""
-    R, ctx, torch, _ = gpu
-    row = ROW[rid]
-    assert row["encode"] != EROW["encode"]
-    b = Batch(R, ctx, torch, oracle, row, draw_lengths(n_streams, row["ways"], 29))
-    run_row(b, 4)  # (asserts the row's kernel names)
-    assert ctx.decode_errors() == 0
+    check_other_shape_keeps_its_kernels(gpu, oracle, ENC_GROUPS, rid, n_streams)
 
 
 @pytest.mark.gpu
 def test_option_takes_zero_or_one(gpu, oracle):
     """Any other value is E_ARG and changes nothing; 0 restores the wave-per-stream kernel, 1 the group kernel; the
     decoder's option alone leaves the encoder where it was."""
-    R, ctx, torch, off = gpu
-    b = Batch(R, ctx, torch, oracle, EROW, np.array([300] * 9, dtype=np.uint32))
-    for bad in (2, -1):
-        with pytest.raises(R.RansAmdError) as e:
-            ctx.set_option(OPT_BATCH_ENCODE_GROUPS, bad)
-        assert e.value.status == R.E_ARG
-    run_row(b, 4)
-    ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 0)
-    try:
-        run_row(Batch(R, ctx, torch, oracle, ROW["word-8"], b.counts), 4)
-    finally:
-        ctx.set_option(OPT_BATCH_ENCODE_GROUPS, 1)
-    run_row(b, 4)
+    off = gpu[3]
+    b = check_option_takes_zero_or_one(gpu, oracle, ENC_GROUPS)
     off.set_option(OPT_BATCH_GROUPS, 1)
     try:
         d_buf, sym_offs, slot_offs = b.laid_out(4)
@@ -302,5 +177,4 @@ def test_group_batch_encode_in_a_captured_graph(tmp_path):
     poison-refilled container, each equal to the eager result (stream bytes, offsets, lengths), in a child process under a
     time limit of its own.  Graph replay needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set
     below that the test does not apply."""
-    run_graph_script(tmp_path, "graph_batch_encode_groups.py",
-                     graph_encode_script(EROW["encode"], "FMT_WORD", 8, 12, "OPT_BATCH_ENCODE_GROUPS"))
+    run_family_graph(tmp_path, ENC_GROUPS, "graph_batch_encode_groups.py")

@@ -23,28 +23,21 @@ dead pairs, 0.13 s the `several` regime and the per-stream-models case, 0.06 s a
 import numpy as np
 import pytest
 
-from _batch import (NO_ZERO_WAVE_LOADS, POISON, POOL, Batch, ModelBatch, PoolBatch, draw_lengths, draw_log_uniform, encode_poisoned,
-                    finish_batch, graph_encode_script, mandatory_lengths, no_zero_batch, rate_batch, rate_wave, resident_waves,
-                    run_graph_script, run_model_row, run_row, same_result)
-from _kernel_rows import E16, EMAIN, ENC_PAIR_ROWS, MODEL_ROW, OPT_BATCH_ENCODE_GROUPS, OPT_BATCH_ENCODE_PAIRS, OPT_BATCH_PAIRS, ROW
+from _batch import (NO_ZERO_WAVE_LOADS, POISON, POOL, Batch, ModelBatch, PoolBatch, check_bad_slots, check_encode_order, check_no_false_e_model,
+                    check_option_takes_zero_or_one, check_other_shape_keeps_its_kernels, check_true_e_model, draw_lengths, draw_log_uniform,
+                    finish_batch, mandatory_lengths, option_contexts, padded, rate_batch, rate_wave, resident_waves, run_family_graph,
+                    run_model_row, run_row, same_result, wave_load_cases)
+from _kernel_rows import (E16, EMAIN, ENC_PAIR_ROWS, ENC_PAIRS, MODEL_ROW, OPT_BATCH_ENCODE_GROUPS, OPT_BATCH_ENCODE_PAIRS, OPT_BATCH_PAIRS,
+                          ROW)
 from _kernel_rows import PMAIN as DEC_PAIR_ROW
 from _oracle import FMT_BYTE
 
-KERNEL = "k_encode_batch_byte_pairs"
-WAVE = "k_encode_batch<byte>"
+KERNEL, WAVE = EMAIN["encode"], ENC_PAIRS.wave_kernel
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    import ryg_rans_amd as R
-    ctx = R.Context(0)
-    ctx.set_option(OPT_BATCH_ENCODE_PAIRS, 1)  # (only the new option)
-    off = R.Context(0)  # everything at its default: the wave-per-stream kernels
-    yield R, ctx, torch, off
-    off.close()
-    ctx.close()
+    yield from option_contexts(OPT_BATCH_ENCODE_PAIRS)
 
 
 _DECODERS = {}
@@ -69,29 +62,19 @@ def decoder_of(gpu, oracle, row):
     return dict(row, decode=_DECODERS[row["id"]])
 
 
-def _padded(lengths, n=32, pad=200):
-    return list(lengths) + [pad] * (n - len(lengths))
-
-
 WAVE_LOADS = {
     "one-piece-x4-each": [128] * 32,
-    "boundaries": _padded([0, 1, 2, 3, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256]),
+    "boundaries": padded(32, [0, 1, 2, 3, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256]),
     "31-dead-one-flushing": [65536] + [255] * 31,
     "every-pair-finishes-elsewhere": [128 * (g + 1) + 3 * g for g in range(32)],
     "quad-mates-differ": [640, 0, 128, 385] * 8,
     "all-empty": [0] * 32,
     "second-load-of-one": [300] * 33,
-    "mandatory-and-200s": _padded(mandatory_lengths(2)),
+    "mandatory-and-200s": padded(32, mandatory_lengths(2)),
 }
 
 
-def _wave_load_cases():
-    for name in WAVE_LOADS:
-        for row in (ENC_PAIR_ROWS if name == "one-piece-x4-each" else (EMAIN, E16)):
-            yield pytest.param(name, row, id="%s-%s" % (name, row["id"]), marks=pytest.mark.gpu)
-
-
-@pytest.mark.parametrize("name,row", list(_wave_load_cases()))
+@pytest.mark.parametrize("name,row", list(wave_load_cases(WAVE_LOADS, ENC_PAIR_ROWS, (EMAIN, E16))))
 def test_single_wave_loads(gpu, oracle, name, row):
     """One or two wave-loads: four whole pieces each and no tail; every piece and tail boundary in one wave; 31 pairs dead for
     2040 pieces while one keeps flushing; every pair finishing at another piece, some with an odd count; quad-mates that
@@ -154,12 +137,7 @@ def test_no_false_e_model_from_dead_pairs(gpu, oracle):
     """A model without byte value 0, contents that never use it, uneven counts: dead pairs are fed zeros and read the record
     of byte value 0, which must not reach the flags.  encode_status() is OK (run_row asks) and every stream is the oracle's,
     at both alignments."""
-    R, ctx, torch, _ = gpu
-    freqs, counts, contents = no_zero_batch(*NO_ZERO_WAVE_LOADS)
-    assert freqs[0] == 0 and all(not np.any(c == 0) for c in contents.values())
-    b = Batch(R, ctx, torch, oracle, EMAIN, counts, contents=contents, freqs=freqs)
-    for align in (4, 1):
-        run_row(b, align)
+    check_no_false_e_model(gpu, oracle, ENC_PAIRS, NO_ZERO_WAVE_LOADS)
 
 
 @pytest.mark.gpu
@@ -167,33 +145,7 @@ def test_true_e_model_is_reported_and_contained(gpu, oracle):
     """The same batch with one symbol of the longest stream of the second wave-load overwritten by 0 on the device: E_MODEL, as
     the default context reports for the same batch; every stream of the other wave-loads is the oracle's; the poison behind
     out_cap is intact; the next call succeeds."""
-    R, ctx, torch, off = gpu
-    freqs, counts, contents = no_zero_batch(*NO_ZERO_WAVE_LOADS)
-    b = Batch(R, ctx, torch, oracle, EMAIN, counts, contents=contents, freqs=freqs)
-    gm_off = off.model(FMT_BYTE, freqs, 14)
-    d_buf, sym_offs, slot_offs = b.laid_out(4)
-    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
-    victim = 32 + int(np.argmax(counts[32:64]))
-    assert counts[victim] >= 256
-    bad = d_buf.clone()
-    bad[int(sym_offs[victim]) + int(counts[victim]) // 2] = 0
-    cap = int(slot_offs[-1])
-    for cx, gm, kernel in ((ctx, b.gm, KERNEL), (off, gm_off, WAVE)):
-        cont, offs, lens = encode_poisoned(b, cx, gm, bad, d_sym, d_slot, cap)
-        assert cx.last_encode_kernel()[0] == kernel, cx.last_encode_kernel()
-        with pytest.raises(R.RansAmdError) as e:
-            cx.encode_status()
-        assert e.value.status == R.E_MODEL, kernel
-        h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
-        for c in range(b.n):
-            if c // 32 != victim // 32:
-                a = int(h_offs[c])
-                assert h_lens[c] == b.lens[c] and a + int(h_lens[c]) == int(slot_offs[c + 1]), (kernel, c)
-                assert np.array_equal(h[a:a + int(h_lens[c])], b.streams[c]), (kernel, "stream", c)
-        assert np.all(h[cap:] == POISON), (kernel, "written behind the container")
-    ctx.encode_batch(b.gm, d_buf, d_sym, b.d_counts, 2, d_slot)  # the next call succeeds
-    assert ctx.last_encode_kernel()[0] == KERNEL
-    ctx.encode_status()
+    check_true_e_model(gpu, oracle, ENC_PAIRS, NO_ZERO_WAVE_LOADS)
 
 
 @pytest.mark.gpu
@@ -201,44 +153,7 @@ def test_order(gpu, oracle):
     """70 streams (two wave-loads and a partial third).  No order, the reversed identity and batch_order's result give the same
     streams, offsets and lengths; an order with one entry replaced by n_streams reports E_ARG, every stream still named is
     exact, and the stream that lost its position keeps its slot's poison and its pre-filled index entries."""
-    R, ctx, torch, _ = gpu
-    n = 70
-    counts = draw_lengths(n, 2, 23)
-    b = Batch(R, ctx, torch, oracle, EMAIN, counts)
-    d_buf, sym_offs, slot_offs = b.laid_out(4)
-    d_sym, d_slot = b.dev(sym_offs, np.int64), b.dev(slot_offs, np.int64)
-    cap = int(slot_offs[-1])
-    d_order = ctx.batch_order(b.d_counts)
-    assert sorted(d_order.cpu().tolist()) == list(range(n))
-    results = []
-    for name, order in (("no order", None), ("reversed identity", b.dev(np.arange(n)[::-1], np.int32)), ("batch_order", d_order)):
-        res = encode_poisoned(b, ctx, b.gm, d_buf, d_sym, d_slot, cap, d_order=order)
-        assert ctx.last_encode_kernel()[0] == KERNEL and ctx.last_encode_placement() == 2, (name, ctx.last_encode_kernel())
-        ctx.encode_status()
-        b.check_streams(res[0].cpu().numpy(), res[1].cpu().numpy().astype(np.uint64), res[2].cpu().numpy().view(np.uint32), name)
-        assert np.all(res[0].cpu().numpy()[cap:] == POISON)
-        results.append(res)
-    same_result(torch, results[0], results[1], n, "reversed identity")
-    same_result(torch, results[0], results[2], n, "batch_order")
-    lost = int(np.argmax(counts))
-    order = np.arange(n)
-    order[lost] = n
-    cont, offs, lens = encode_poisoned(b, ctx, b.gm, d_buf, d_sym, d_slot, cap, d_order=b.dev(order, np.int32), sentinel=-77)
-    assert ctx.last_encode_kernel()[0] == KERNEL, ctx.last_encode_kernel()
-    with pytest.raises(R.RansAmdError) as e:
-        ctx.encode_status()
-    assert e.value.status == R.E_ARG
-    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy()
-    for c in range(n):
-        lo, hi = int(slot_offs[c]), int(slot_offs[c + 1])
-        if c == lost:
-            assert h_offs[c] == -77 and h_lens[c] == -77, "the index entry of the stream without a position was written"
-            assert np.all(h[lo:hi] == POISON), "the slot of the stream without a position was written"
-        else:
-            ln = int(h_lens[c])
-            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, c
-            assert np.array_equal(h[hi - ln:hi], b.streams[c]), ("stream", c)
-    assert np.all(h[cap:] == POISON)
+    check_encode_order(gpu, oracle, gpu[1], EMAIN, draw_lengths(70, 2, 23))
 
 
 @pytest.mark.gpu
@@ -247,44 +162,7 @@ def test_bad_slots(gpu, oracle):
     than its bound; a slot off 16 bytes on both sides (two streams), one a granule too small, one beyond out_cap -- each in a
     wave-load with valid streams.  E_SPACE, the rejected slots keep their poison and get lengths 0, every other stream is
     exact, the first 16 bytes of every accepted slot are still poison, nothing is written behind the container."""
-    R, ctx, torch, _ = gpu
-    counts = draw_lengths(400, 2, 71)
-    b = Batch(R, ctx, torch, oracle, EMAIN, counts)
-    d_buf, sym_offs, _ = b.laid_out(4)
-    bound = np.array([R.chunk_bound(FMT_BYTE, int(c), 2) for c in counts], dtype=np.int64)
-    sizes = bound + 32
-    idx = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
-    cap = int(idx[-1])
-    big = np.nonzero(counts >= 1000)[0]
-    off16, past = int(big[0]), 399
-    small = int(big[(big > off16 + 2) & (big < past - 1)][0])
-    bad_idx = idx.copy()
-    bad_idx[off16 + 1] += 8
-    bad_idx[small] = bad_idx[small + 1] - (bound[small] - 16)
-    rejected = {off16, off16 + 1, small, past}
-    assert len(rejected) == 4
-    for c in rejected:  # (its wave-load holds valid streams as well)
-        assert any(k not in rejected for k in range(32 * (c // 32), min(32 * (c // 32) + 32, 400)))
-    d_out = torch.full((cap + 4096,), POISON, dtype=torch.uint8, device="cuda")
-    cont, offs, lens = ctx.encode_batch(b.gm, d_buf, b.dev(sym_offs, np.int64), b.d_counts, 2, b.dev(bad_idx, np.int64), d_out=d_out,
-                                        out_cap=cap - 16)
-    assert ctx.last_encode_kernel()[0] == KERNEL, ctx.last_encode_kernel()
-    with pytest.raises(R.RansAmdError) as e:
-        ctx.encode_status()
-    assert e.value.status == R.E_SPACE
-    h, h_offs, h_lens = cont.cpu().numpy(), offs.cpu().numpy(), lens.cpu().numpy().view(np.uint32)
-    for c in range(b.n):
-        lo, hi = int(bad_idx[c]), int(bad_idx[c + 1])
-        if c in rejected:
-            assert h_lens[c] == 0 and int(h_offs[c]) == hi, c
-            if hi > lo:
-                assert np.all(h[lo:hi] == POISON), ("a rejected slot was written", c)
-        else:
-            ln = int(h_lens[c])
-            assert ln == b.lens[c] and int(h_offs[c]) == hi - ln, c
-            assert np.array_equal(h[hi - ln:hi], b.streams[c]), ("stream", c)
-            assert np.all(h[lo:lo + 16] == POISON), ("the head of a slot was written", c)
-    assert np.all(h[cap:] == POISON), "written behind the container"
+    check_bad_slots(gpu, oracle, ENC_PAIRS)
 
 
 def _streams_equal_prototypes(torch, pb, cont, offs, lens, what):
@@ -351,12 +229,7 @@ def test_half_and_several(gpu, oracle, regime):
 def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_streams):
     """Fewer than 32 2-way byte streams, the 64-way byte rows, the 8-way word layout, the alias and the rans64 2-way rows take
     the wave-per-stream kernels on the context with the option on, and code right."""
-    R, ctx, torch, _ = gpu
-    row = ROW[rid]
-    assert row["encode"] != KERNEL
-    b = Batch(R, ctx, torch, oracle, row, draw_lengths(n_streams, row["ways"], 29))
-    run_row(b, 4)  # (asserts the row's kernel names)
-    assert ctx.decode_errors() == 0
+    check_other_shape_keeps_its_kernels(gpu, oracle, ENC_PAIRS, rid, n_streams)
 
 
 @pytest.mark.gpu
@@ -395,19 +268,7 @@ def test_options_are_independent(gpu, oracle):
 @pytest.mark.gpu
 def test_option_takes_zero_or_one(gpu, oracle):
     """Any other value is E_ARG and changes nothing; 0 restores the wave-per-stream kernel, 1 the pair kernel."""
-    R, ctx, torch, _ = gpu
-    b = Batch(R, ctx, torch, oracle, EMAIN, np.array([300] * 33, dtype=np.uint32))
-    for bad in (2, -1):
-        with pytest.raises(R.RansAmdError) as e:
-            ctx.set_option(OPT_BATCH_ENCODE_PAIRS, bad)
-        assert e.value.status == R.E_ARG
-    run_row(b, 4)
-    ctx.set_option(OPT_BATCH_ENCODE_PAIRS, 0)
-    try:
-        run_row(Batch(R, ctx, torch, oracle, ROW["byte-2"], b.counts), 4)
-    finally:
-        ctx.set_option(OPT_BATCH_ENCODE_PAIRS, 1)
-    run_row(b, 4)
+    check_option_takes_zero_or_one(gpu, oracle, ENC_PAIRS)
 
 
 @pytest.mark.gpu
@@ -416,5 +277,4 @@ def test_pair_batch_encode_in_a_captured_graph(tmp_path):
     poison-refilled container, each equal to the eager result (stream bytes, offsets, lengths), in a child process under a
     time limit of its own.  Graph replay needs the process's default of four hardware queues: with GPU_MAX_HW_QUEUES set
     below that the test does not apply."""
-    run_graph_script(tmp_path, "graph_batch_encode_pairs.py",
-                     graph_encode_script(KERNEL, "FMT_BYTE", 2, 14, "OPT_BATCH_ENCODE_PAIRS"))
+    run_family_graph(tmp_path, ENC_PAIRS, "graph_batch_encode_pairs.py")

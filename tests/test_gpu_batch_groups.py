@@ -13,23 +13,15 @@ are the smallest at which that can go wrong."""
 import numpy as np
 import pytest
 
-from _batch import (GUARD, POISON, Batch, Coded, draw_lengths, draw_log_uniform, graph_decode_script, mandatory_lengths, resident_waves,
-                    run_graph_script, run_row)
-from _kernel_rows import GROW, OPT_BATCH_GROUPS, ROW
-from _oracle import FMT_WORD
+from _batch import (Batch, check_damage_inside_one_wave_load, check_decode_order, check_option_takes_zero_or_one,
+                    check_other_shape_keeps_its_kernels, draw_lengths, draw_log_uniform, mandatory_lengths, option_contexts, resident_waves,
+                    run_family_graph, run_row)
+from _kernel_rows import GROUPS, GROW, OPT_BATCH_GROUPS
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    import ryg_rans_amd as R
-    ctx = R.Context(0)
-    ctx.set_option(OPT_BATCH_GROUPS, 1)
-    off = R.Context(0)  # the option at its default: the wave-per-stream kernels
-    yield R, ctx, torch, off
-    off.close()
-    ctx.close()
+    yield from option_contexts(OPT_BATCH_GROUPS)
 
 
 OCTETS = {
@@ -64,30 +56,7 @@ def test_order(gpu, oracle):
     """17 streams: the reversed identity, the result of batch_order, and an order with one entry replaced by n_streams --
     that position is one failed stream, every stream still named decodes right, the stream that lost its position is not
     written.  0.03 s."""
-    R, ctx, torch, _ = gpu
-    n = 17
-    b = Batch(R, ctx, torch, oracle, GROW, draw_lengths(n, 8, 23))
-    for align in (1, 4):
-        c = Coded(b, align)
-        c.decode_all(None, "no order")
-        c.decode_all(b.dev(np.arange(n)[::-1], np.int32), "reversed identity")
-        d_order = ctx.batch_order(b.d_counts)
-        assert sorted(d_order.cpu().tolist()) == list(range(n))
-        c.decode_all(d_order, "batch_order")
-        lost = int(np.argmax(b.counts))  # (a stream with symbols: its range would show a write)
-        order = np.arange(n)
-        order[lost] = n
-        want = c.d_buf.cpu().numpy().copy()
-        lo = int(c.sym_offs[lost])
-        want[lo:lo + int(b.counts[lost])] = POISON
-        for name, cont, nbytes, offs, lens in c.containers():
-            out = torch.full_like(c.d_buf, b.poison())
-            with pytest.raises(R.RansAmdError) as e:
-                ctx.decode_batch(b.gm, cont, nbytes, offs, lens, c.d_sym, b.d_counts, 8, out, d_order=b.dev(order, np.int32))
-            assert e.value.status == R.E_CORRUPT and e.value.bad_streams == 1, (name, e.value.bad_streams)
-            assert ctx.last_decode_kernel() == GROW["decode"]
-            assert np.array_equal(out.cpu().numpy(), want), (name, "a named stream differs, or the stream without a position was written")
-    assert ctx.decode_errors() == 0
+    check_decode_order(gpu, oracle, GROUPS, 17, (1, 4))
 
 
 @pytest.mark.gpu
@@ -123,41 +92,7 @@ def test_damage_is_counted_and_contained_inside_one_octet(gpu, oracle):
     a length shortened by 2, an odd offset, a sym_offset one symbol past out_syms.  bad_streams is 4, as the
     wave-per-stream kernel reports for the same damaged batch; the other twelve streams, the padding and the guard are
     exact; the streams with the bad sym_offset and the odd offset are not written.  0.01 s."""
-    R, ctx, torch, off = gpu
-    counts = np.random.default_rng(17).integers(300, 5001, 16).astype(np.uint32)
-    b = Batch(R, ctx, torch, oracle, GROW, counts)
-    gm_off = off.model(FMT_WORD, b.freqs, 12)
-    flipped, short, odd, far = 1, 3, 4, 6
-    damaged = (flipped, short, odd, far)
-    for align in (1, 4):
-        c = Coded(b, align)
-        for name, cont, nbytes, offs, lens in c.containers():
-            h_offs = offs.cpu().numpy()
-            bad_cont = cont.clone()
-            bad_cont[int(h_offs[flipped]) + 1] ^= 0x40  # inside the flushed states
-            bad_lens = lens.clone()
-            bad_lens[short] -= 2
-            bad_offs = offs.clone()
-            bad_offs[odd] += 1
-            bad_sym = c.d_sym.clone()
-            bad_sym[far] = c.d_buf.numel() - int(counts[far]) + 1  # one symbol past the end
-            reported = []
-            for cx, gm, kernel in ((ctx, b.gm, GROW["decode"]), (off, gm_off, "k_decode_batch<word>")):
-                out = torch.full_like(c.d_buf, b.poison())
-                with pytest.raises(R.RansAmdError) as e:
-                    cx.decode_batch(gm, bad_cont, nbytes, bad_offs, bad_lens, bad_sym, b.d_counts, 8, out)
-                assert e.value.status == R.E_CORRUPT and cx.last_decode_kernel() == kernel, (name, cx.last_decode_kernel())
-                assert cx.decode_errors() == 0  # (reported and reset by that call)
-                reported.append(e.value.bad_streams)
-                got, want = out.cpu().numpy(), c.d_buf.cpu().numpy()
-                keep = np.ones(want.size, dtype=bool)
-                for s in damaged:
-                    keep[int(c.sym_offs[s]):int(c.sym_offs[s]) + int(counts[s])] = False
-                assert np.array_equal(got[keep], want[keep]), (name, kernel, "an undamaged stream, the padding or the guard differs")
-                for s in (far, odd):
-                    assert np.all(got[int(c.sym_offs[s]):int(c.sym_offs[s]) + int(counts[s])] == POISON), (name, kernel, "stream", s, "was written")
-                assert np.all(got[int(c.sym_offs[-1]):] == POISON) and got.size == int(c.sym_offs[-1]) + GUARD
-            assert reported == [4, 4], (name, align, reported)
+    check_damage_inside_one_wave_load(gpu, oracle, GROUPS, 16, (1, 3, 4, 6), 2, lambda off, ln, nbytes: off + 1, (4,))
 
 
 @pytest.mark.gpu
@@ -165,30 +100,13 @@ def test_damage_is_counted_and_contained_inside_one_octet(gpu, oracle):
 def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_streams):
     """64-way, u16 symbols, fewer than eight 8-way streams and the byte format take the wave-per-stream kernels on the
     context with the option on, and decode right.  0.03 s per case."""
-    R, ctx, torch, _ = gpu
-    row = ROW[rid]
-    assert row["decode"] != GROW["decode"]
-    b = Batch(R, ctx, torch, oracle, row, draw_lengths(n_streams, row["ways"], 29))
-    run_row(b, 4)  # (asserts the row's kernel names)
-    assert ctx.decode_errors() == 0
+    check_other_shape_keeps_its_kernels(gpu, oracle, GROUPS, rid, n_streams)
 
 
 @pytest.mark.gpu
 def test_option_takes_zero_or_one(gpu, oracle):
     """Any other value is E_ARG and changes nothing; 0 restores the wave-per-stream kernel, 1 the group kernel."""
-    R, ctx, torch, _ = gpu
-    b = Batch(R, ctx, torch, oracle, GROW, np.array([300] * 9, dtype=np.uint32))
-    for bad in (2, -1):
-        with pytest.raises(R.RansAmdError) as e:
-            ctx.set_option(OPT_BATCH_GROUPS, bad)
-        assert e.value.status == R.E_ARG
-    run_row(b, 4)
-    ctx.set_option(OPT_BATCH_GROUPS, 0)
-    try:
-        run_row(Batch(R, ctx, torch, oracle, ROW["word-8"], b.counts), 4)
-    finally:
-        ctx.set_option(OPT_BATCH_GROUPS, 1)
-    run_row(b, 4)
+    check_option_takes_zero_or_one(gpu, oracle, GROUPS)
 
 
 @pytest.mark.gpu
@@ -196,5 +114,4 @@ def test_group_batch_decode_in_a_captured_graph(tmp_path):
     """One captured decode_batch of 3000 8-way streams with the option on: one eager call first, then three replays, each
     equal to the eager result, in a child process under a time limit of its own.  Graph replay needs the process's default
     of four hardware queues: with GPU_MAX_HW_QUEUES set below that the test does not apply.  2.5 s."""
-    run_graph_script(tmp_path, "graph_batch_groups.py",
-                     graph_decode_script(GROW["decode"], ways=8, option="OPT_BATCH_GROUPS"))
+    run_family_graph(tmp_path, GROUPS, "graph_batch_groups.py")

@@ -1,8 +1,8 @@
 """Ragged batches of the reference's 2-way rans64 layout with SIXTY-FOUR streams per wave, one per lane:
 k_decode_batch_r64_lanes, the kernel rans_amd_decode_batch launches on a context with RANS_AMD_OPT_BATCH_LANES = 1.
 
-LANE_ROWS (tests/_batch_lanes.py) names the kernel the library must report (tests/test_batch_lanes_host.py holds the rows to
-the registry's second list).  The harness is tests/_batch.py's: every decode is checked against the symbols the oracle's
+LANE_ROWS (tests/_kernel_rows.py) names the kernel the library must report (tests/test_batch_lanes_host.py holds the rows to
+the registry's family).  The harness is tests/_batch.py's: every decode is checked against the symbols the oracle's
 streams were made from, from the GPU's own container and from one the oracle made (shuffled, 4-byte-aligned offsets, gaps),
 into a poison-filled buffer whose padding and guard must come back untouched.
 
@@ -21,34 +21,22 @@ import numpy as np
 import pytest
 
 import _batch_lanes as L
-import _stream_rate as S
-from _batch import (GUARD, POISON, Batch, Coded, draw_lengths, draw_log_uniform, graph_decode_script, resident_waves, run_graph_script,
-                    run_row)
-from _batch_lanes import ALIGNS, L16, LANE_KERNEL, LANE_ROWS, LMAIN, RATE_ROW, WAVE_KERNEL, WAVE_LOADS
-from _kernel_rows import OPT_BATCH_GROUPS, OPT_BATCH_PAIRS, ROW
+from _batch import (GUARD, POISON, Batch, Coded, check_decode_order, check_option_takes_zero_or_one, check_other_shape_keeps_its_kernels,
+                    check_rate_phase_parking, draw_lengths, draw_log_uniform, option_contexts, resident_waves, run_family_graph, run_row,
+                    wave_load_cases)
+from _batch_lanes import ALIGNS, WAVE_LOADS
+from _kernel_rows import LANE16, LANE_RATE_ROW, LANE_ROWS, LANES, LMAIN, OPT_BATCH_GROUPS, OPT_BATCH_LANES, OPT_BATCH_PAIRS, ROW
 from _oracle import FMT_R64
+
+LANE_KERNEL, WAVE_KERNEL = LMAIN["decode"], LANES.wave_kernel  # (the wave kernel: what every row reports with the option off)
 
 
 @pytest.fixture(scope="module")
 def gpu():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    import ryg_rans_amd as R
-    ctx = R.Context(0)
-    ctx.set_option(R.OPT_BATCH_LANES, 1)
-    off = R.Context(0)  # the option at its default: the wave-per-stream kernels
-    yield R, ctx, torch, off
-    off.close()
-    ctx.close()
+    yield from option_contexts(OPT_BATCH_LANES)
 
 
-def _wave_load_cases():
-    for name in WAVE_LOADS:
-        for row in (LANE_ROWS if name == "one-trip-each" else (LMAIN, L16)):
-            yield pytest.param(name, row, id="%s-%s" % (name, row["id"]), marks=pytest.mark.gpu)
-
-
-@pytest.mark.parametrize("name,row", list(_wave_load_cases()))
+@pytest.mark.parametrize("name,row", list(wave_load_cases(WAVE_LOADS, LANE_ROWS, (LMAIN, LANE16))))
 def test_single_wave_loads(gpu, oracle, name, row):
     """One or two wave-loads: one trip each and no tail (every row: 14, 16, 12 and 7 bits, 64 symbols at 10 bits); every trip
     and tail boundary in one wave; 63 lanes parked for 1023 trips while one refills its ring throughout, each owing a
@@ -80,27 +68,7 @@ def test_rate_phase_parking(gpu, oracle, sb):
     64 b + t, b in {0, 1, 5}, t in {0, 1, 31, 63}, the oracle's stream at offset == 4 k (mod 64) of a container packed by hand.
     Lanes with b = 0 and b = 1 are parked while their quad- and wave-mates run on at the bound.  Each from three containers at
     sym_align 64, 4 and 1, with and without batch_order, with the option and without; all must equal the input."""
-    R, ctx, torch, off = gpu
-    row = RATE_ROW[sb]
-    freqs, counts, contents, phases = L.rate_batch(sb)
-    b = Batch(R, ctx, torch, oracle, row, counts, contents=contents, freqs=freqs)
-    gm_off = off.model(FMT_R64, b.freqs, sb)
-    p_cont, p_starts, p_bytes = S.pack_at_phases(b.streams, phases, 64, order=np.random.default_rng(11).permutation(b.n))
-    assert sorted(set(int(s) % 64 for s in p_starts)) == list(range(0, 64, 4))
-    d_lens = b.dev(b.lens, np.int32)
-    d_order = ctx.batch_order(b.d_counts)
-    for align in (64, 4, 1):
-        cont, offs, lens, d_buf, d_sym, d_slot, sym_offs, slot_offs = run_row(b, align)  # (the GPU's and the oracle's container)
-        containers = (("gpu", cont, int(slot_offs[-1]), offs, lens),
-                      ("phases", b.dev(p_cont, np.uint8), p_bytes, b.dev(p_starts, np.int64), d_lens))
-        for cx, gm, kernel in ((ctx, b.gm, LANE_KERNEL), (off, gm_off, WAVE_KERNEL)):
-            for name, c, nbytes, o, ln in containers:
-                for order in (None, d_order):
-                    out = torch.full_like(d_buf, b.poison())
-                    cx.decode_batch(gm, c, nbytes, o, ln, d_sym, b.d_counts, 2, out, d_order=order)
-                    assert cx.last_decode_kernel() == kernel, (cx.last_decode_kernel(), name)
-                    assert torch.equal(out, d_buf), (kernel, name, "align", align, "order" if order is not None else "no order")
-                    assert cx.decode_errors() == 0, (kernel, name)
+    check_rate_phase_parking(gpu, oracle, LANES, LANE_RATE_ROW[sb], L.rate_batch(sb), (64, 4, 1), start_phases=list(range(0, 64, 4)))
 
 
 @pytest.mark.gpu
@@ -108,30 +76,7 @@ def test_order(gpu, oracle):
     """130 streams (two wave-loads and two streams of a third): the reversed identity, the result of batch_order, and an order
     with one entry replaced by n_streams -- that position is one failed stream, every stream still named decodes right, the
     stream that lost its position is not written."""
-    R, ctx, torch, _ = gpu
-    n = 130
-    b = Batch(R, ctx, torch, oracle, LMAIN, draw_lengths(n, 2, 23))
-    for align in (4, 64):
-        c = Coded(b, align)
-        c.decode_all(None, "no order")
-        c.decode_all(b.dev(np.arange(n)[::-1], np.int32), "reversed identity")
-        d_order = ctx.batch_order(b.d_counts)
-        assert sorted(d_order.cpu().tolist()) == list(range(n))
-        c.decode_all(d_order, "batch_order")
-        lost = int(np.argmax(b.counts))  # (a stream with symbols: its range would show a write)
-        order = np.arange(n)
-        order[lost] = n
-        want = c.d_buf.cpu().numpy().copy()
-        lo = int(c.sym_offs[lost])
-        want[lo:lo + int(b.counts[lost])] = POISON
-        for name, cont, nbytes, offs, lens in c.containers():
-            out = torch.full_like(c.d_buf, b.poison())
-            with pytest.raises(R.RansAmdError) as e:
-                ctx.decode_batch(b.gm, cont, nbytes, offs, lens, c.d_sym, b.d_counts, 2, out, d_order=b.dev(order, np.int32))
-            assert e.value.status == R.E_CORRUPT and e.value.bad_streams == 1, (name, e.value.bad_streams)
-            assert ctx.last_decode_kernel() == LANE_KERNEL
-            assert np.array_equal(out.cpu().numpy(), want), (name, "a named stream differs, or the stream without a position was written")
-    assert ctx.decode_errors() == 0
+    check_decode_order(gpu, oracle, LANES, 130, (4, 64))
 
 
 @functools.lru_cache(maxsize=None)
@@ -261,11 +206,7 @@ def test_several_rounds_of_the_grid(gpu, oracle):
 def test_other_shapes_keep_their_kernels_with_the_option_on(gpu, oracle, rid, n_streams):
     """The 64-way rans64 rows (cum2sym and search), the 2-way byte and the 8-way word layout take the wave-per-stream kernels on
     the context with the option on, and decode right."""
-    R, ctx, torch, _ = gpu
-    row = ROW[rid]
-    assert row["decode"] != LANE_KERNEL
-    run_row(Batch(R, ctx, torch, oracle, row, draw_lengths(n_streams, row["ways"], 29)), 4)  # (asserts the row's kernel names)
-    assert ctx.decode_errors() == 0
+    check_other_shape_keeps_its_kernels(gpu, oracle, LANES, rid, n_streams)
 
 
 @pytest.mark.gpu
@@ -288,19 +229,7 @@ def test_option_nine_is_independent_of_five_and_seven(gpu, oracle):
 @pytest.mark.gpu
 def test_option_takes_zero_or_one(gpu, oracle):
     """Any other value is E_ARG and changes nothing; 0 restores the wave-per-stream kernel, 1 the lane kernel."""
-    R, ctx, torch, _ = gpu
-    b = Batch(R, ctx, torch, oracle, LMAIN, np.array([300] * 65, dtype=np.uint32))
-    for bad in (2, -1):
-        with pytest.raises(R.RansAmdError) as e:
-            ctx.set_option(R.OPT_BATCH_LANES, bad)
-        assert e.value.status == R.E_ARG
-    run_row(b, 64)
-    ctx.set_option(R.OPT_BATCH_LANES, 0)
-    try:
-        run_row(Batch(R, ctx, torch, oracle, ROW["r64-2"], b.counts), 64)
-    finally:
-        ctx.set_option(R.OPT_BATCH_LANES, 1)
-    run_row(b, 64)
+    check_option_takes_zero_or_one(gpu, oracle, LANES, align=64)
 
 
 @pytest.mark.gpu
@@ -308,5 +237,4 @@ def test_lane_batch_decode_in_a_captured_graph(tmp_path):
     """One captured decode_batch of 3000 2-way rans64 streams with the option on: one eager call first, then three replays, each
     equal to the eager result, in a child process under a time limit of its own.  Graph replay needs the process's default
     of four hardware queues: with GPU_MAX_HW_QUEUES set below that the test does not apply."""
-    run_graph_script(tmp_path, "graph_batch_lanes.py",
-                     graph_decode_script(LANE_KERNEL, fmt="FMT_R64", ways=2, sb=14, option="OPT_BATCH_LANES"))
+    run_family_graph(tmp_path, LANES, "graph_batch_lanes.py")
