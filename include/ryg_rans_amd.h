@@ -189,7 +189,7 @@ enum rans_amd_option {
                                               options 5, 6 and 7 (RANS_AMD_OPT_BATCH_PAIRS is the decoder's alone);
                                               rans_amd_encode_batch_adaptive is not affected.  Default 0: one stream per
                                               wavefront.  Any other value is RANS_AMD_E_ARG. */
-    RANS_AMD_OPT_BATCH_LANES = 9           /* 1 = rans_amd_decode_batch decodes SIXTY-FOUR streams per wavefront, one per
+    RANS_AMD_OPT_BATCH_LANES = 9,          /* 1 = rans_amd_decode_batch decodes SIXTY-FOUR streams per wavefront, one per
                                               lane, where the batch is the reference's 2-way rans64 layout (rans64 format, u8
                                               symbols, n_ways 2, scale_bits 7..16, at least 64 streams, tables + wave rings
                                               within the CU's 160 KiB of LDS): k_decode_batch_r64_lanes; every other shape
@@ -198,6 +198,23 @@ enum rans_amd_option {
                                               Measured with d_order on 181 992 streams of up to 64 Ki symbols at
                                               sym_align 64: 5.13 ms against 30.85 ms on k_decode_batch<r64> with the same
                                               d_order (6.02 x).
+                                              Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
+    RANS_AMD_OPT_BATCH_ENCODE_LANES = 10   /* 1 = rans_amd_encode_batch[_ordered] codes SIXTY-FOUR streams per wavefront, one
+                                              per lane, where the batch is that same shape (rans64 format, u8 symbols, n_ways
+                                              2, scale_bits 7..16, at least 64 streams; the 8 KiB record table and a wave's
+                                              8 KiB ring always fit the CU's LDS): k_encode_batch_r64_lanes, the same bytes;
+                                              every other shape takes the wave-per-stream kernels as before.  Independent of
+                                              options 5 to 9 (RANS_AMD_OPT_BATCH_LANES is the decoder's alone);
+                                              rans_amd_encode_batch_adaptive and every decoder are not affected.
+                                              Symbol loads by the address of a stream's first symbol: on a 64-byte line
+                                              (sym_align 64, the fast layout) a quad of lanes fetches its lanes' lines, the
+                                              next 64 symbols in flight during the current ones; on the 4-byte grid the lane
+                                              fetches its own 16-byte pieces, not ahead; any other address is coded a
+                                              symbol and a byte load at a time.  All code the same bytes.
+                                              Measured with d_order on 181 992 streams of up to 64 Ki symbols at
+                                              sym_align 64: 6.29 ms against 37.07 ms on k_encode_batch<r64> with the same
+                                              d_order (5.90 x; its slowest pass beats the wave kernel's fastest); 2 Mi
+                                              streams of 512 symbols: 1.26 ms against 36.33 ms (28.8 x).
                                               Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
 };
 int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value);
@@ -427,13 +444,13 @@ int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, u
  * the same rules: the wavefront lasts as long as the longest of its 32 streams (pass d_order), and sym_align = 4 is the fast
  * layout.  A third shape packs SIXTY-FOUR streams into a wavefront, one per lane: the 2-way rans64 layout main64.cpp writes
  * (rans64 format, u8 symbols, n_ways 2, scale_bits 7..16) in a batch of at least 64 streams, decoded by rans_amd_decode_batch
- * on a context with RANS_AMD_OPT_BATCH_LANES = 1 (the decoder's alone: the encoders stay one stream per wavefront for this
- * layout) -- the same bytes, the same advice: the wavefront lasts as long as the longest of its 64 streams (pass d_order),
- * and here sym_align = 64 is the fast layout (a stream whose symbols start on a 64-byte line has its lines written by a quad
- * of lanes; one on the 4-byte grid is stored in 16-byte pieces by its own lane, any other byte by byte -- all decode
- * right).  A stream of more than 2^30 bytes is reported as failed by that kernel.  Every other interleave stays one stream
- * per wavefront in both directions; the ragged form of the 2-way rans64 ENCODER and ragged forms of the other lane kernels
- * (1-, 4- and 8-way interleaves, the other formats) are later work.  A stream of 0 symbols is the n_ways flushed initial
+ * on a context with RANS_AMD_OPT_BATCH_LANES = 1 and coded by rans_amd_encode_batch[_ordered] on a context with
+ * RANS_AMD_OPT_BATCH_ENCODE_LANES = 1 (independent again, the same bytes), the same advice: the wavefront lasts as long as the
+ * longest of its 64 streams (pass d_order), and here sym_align = 64 is the fast layout (a stream whose symbols start on a
+ * 64-byte line has its lines written, or fetched, by a quad of lanes; one on the 4-byte grid is stored, or fetched, in 16-byte
+ * pieces by its own lane, any other byte by byte -- all decode, and code, right).  A stream of more than 2^30 bytes is
+ * reported as failed by that decoder.  Every other interleave stays one stream per wavefront in both directions; ragged forms
+ * of the other lane kernels (1-, 4- and 8-way interleaves, the other formats) are later work.  A stream of 0 symbols is the n_ways flushed initial
  * states.
  * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
  * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).

@@ -1,7 +1,9 @@
 // encode_lanes.hip -- lane-per-stream encoders for narrow interleaves (N = 1, 2, 4, 8), all generations, and the fused
-// placement of their chunks.
+// placement of their chunks.  Behind k_encode_lanes_r64x2: k_encode_batch_r64_lanes, its ragged form for
+// rans_amd_encode_batch[_ordered] (sixty-four STREAMS per wave, each with its own count, symbol address and slot).
 
 #include "lanes_common.hpp"
+#include "groups_common.hpp" // the ragged kernel's work hand-out and wave maximum
 
 namespace rans_amd {
 
@@ -896,6 +898,302 @@ __global__ void __launch_bounds__(1024) k_encode_lanes_r64x2(const EncParams p)
         atomicOr(p.flags, 1u);
 }
 
+// ---------------------------------------------------------------------------
+// k_encode_batch_r64_lanes -- the ragged form of k_encode_lanes_r64x2 (rans_amd_encode_batch[_ordered] under
+// RANS_AMD_OPT_BATCH_ENCODE_LANES): a wave's sixty-four lanes hold sixty-four STREAMS of the reference's 2-way rans64 layout
+// (main64.cpp:224-246), the mirror image of decode_lanes.hip's k_decode_batch_r64_lanes.  The unit of work is one wave-load
+// of the hand-out order, claimed through the pooled counters: lane l of claim w holds the stream at position 64 w + l --
+// stream order[64 w + l], or 64 w + l without an order; a position at or past nchunks has no stream.  The group of sixteen
+// (E64_*, r64x2_encode_group), the 16-byte records at LDS address 0 and the ring (32 dwords per lane, dword d of lane l at
+// ring + 256 d + 4 l, 8 KiB aligned) are k_encode_lanes_r64x2's as they are; the prologue that builds the records is that
+// kernel's, written out again here (a shared helper would be one more thing the uniform kernel's code depends on).
+//   * the coder runs from a stream's last symbol to its first: symbol i is state (i & 1)'s, an odd count's last symbol is
+//     state 0's alone and is coded first (main64.cpp:232-236); Rans64EncFlush of state 1 comes first, then state 0, so
+//     state 0's two dwords are the stream's lowest.  A stream of 0 symbols is the two flushed initial states, 16 bytes;
+//   * the stream ends at its slot's end.  Ring dword d holds the bytes [4 d, 4 d + 4) of a 128-byte window whose end is the
+//     slot's end (mod 128); LINES of 64 bytes are counted DOWN from the slot's end, line j (1, 2, ...) = the bytes
+//     (64 (j - 1), 64 j] below it, in ring half j & 1.  `fl` lines have left; what the ring alone holds (pending) follows
+//     from fl and the ring position, as in the uniform kernel -- bytes are never counted per symbol.  A group emits at most
+//     64 bytes and a flush follows every group, so pending < 64 in front of a group and < 128 behind it;
+//   * flushes by quads: a lane that has filled line j asks for it (req = j << 2 | first piece), its quad writes the line's
+//     16-byte pieces, lane m the piece m at slot_end - 64 j + 16 m, with the asking lane's slot end and slot size through
+//     DPP.  Slots are multiples of 16 bytes, not of 64: a piece that would start below the slot's first byte is never
+//     stored (it is the neighbour's), and of the last line only the pieces that hold stream bytes are (the piece with the
+//     stream's first byte whole, as the wave kernels store it).  All stores lie inside [slot_at, slot_end), which the
+//     index check has put inside [0, out_cap);
+//   * symbols, by the address of the stream's first symbol:
+//       64-byte aligned (rans_amd_batch_layout with sym_align = 64, the fast layout): whole 64-symbol blocks are fetched by
+//         the quad, instruction t the line of the quad's lane t, transposed in registers, the next block in flight during
+//         the current one (k_encode_lanes_r64x2's loads, each under "lane t still has a block");
+//       on the 4-byte grid: the same blocks, but the lane fetches its own four 16-byte pieces at the top of the block,
+//         not ahead of it;
+//       any other address: no blocks, every symbol goes through the rounds below.
+//     The count - 64 blocks symbols behind the last whole block are the END of the stream, so they are coded FIRST, one
+//     compiler-scheduled round (one symbol per lane, a byte load fetched a round ahead) at a time, lanes without a symbol
+//     sitting out (r64x2_put_one: E64_FRONT / E64_BACK in C++, the same records, the same ring);
+//   * whole blocks run under full exec on the asm sequence, four groups each, the lane's last block first.
+// The 64 lanes START together and finish at different times.  A lane is FINALISED at the top of the iteration q ==
+// blocks_l, right behind its last group: the two flushed states, its last line or two, lengths[s] and offsets[s] =
+// slot_end - lengths[s].  From then on it is DEAD, and so is, from the start, a lane without a stream or with a rejected
+// one.  A dead lane rides along under full exec (E64_FRONT sets exec = -1 itself) and is left to run free -- it is never
+// resumed, so nothing is put back but `worst`:
+//   * nothing of its own leaves the ring: flush() asks for a line under `live` only, which is cleared for good, and a
+//     quad reads a member's column only for the line that member asked for; everything of its stream had left the ring
+//     when it was finalised (the two final flushes);
+//   * it still takes part in its quad-mates' flushes: flush() is called by the whole wave outside any divergent branch,
+//     and the piece a lane stores is chosen by the ASKING lane's request alone;
+//   * it writes only into its own column of the ring: the write position moves by -256 and is folded into the ring by
+//     v_bfi (mask 0x1fff), which keeps its low eight bits, 4 l -- whatever its state becomes;
+//   * it loads no symbol: the quad's load of lane t's line stands under q < that lane's blocks (0 for a lane that was dead
+//     from the start), the lane's own loads under the same, the rounds' byte loads under k < tail; it codes zeros and
+//     reads only the record of byte value 0;
+//   * it cannot raise the model flag, even when byte value 0 has no record: `worst` is put back from a copy behind every
+//     block for the lanes that did not run it, and the rounds track under `active` only;
+//   * it cannot raise any other flag: bits 1 and 11 are set in the claim's set-up alone, bit 2 in the prologue.
+// (k_encode_batch_byte_pairs needs a test with a dead pair at its ring's bound because a dead pair's CURSOR counts on without
+// limit and is folded into the row at every write; here there is no cursor -- the write position IS the folded ring address,
+// 13 bits of a register whose other bits v_bfi takes from the ring's base at every step, so there is no bound to run past.)
+// Index entries are the caller's data and checked exactly as k_encode_batch_byte_pairs checks them, with need = align16(4 *
+// count + 2 * 8) = rans_amd_chunk_bound(): a state emits at most one dword per symbol (rans64.h:83-88).  A slot that fails
+// is not written, lengths[s] = 0, offsets[s] = the slot's end, bit 1 of the flags; an order entry that names no stream codes
+// nothing, writes no index entry and sets bit 11.  Every lane addresses symbols and slots in 64 bits.
+// No MFMA: integer, table-driven, serial per state.
+// ---------------------------------------------------------------------------
+typedef uint32_t lanes_enc_u32x4_a4 __attribute__((ext_vector_type(4), aligned(4))); // 16 bytes on the 4-byte grid
+
+// one symbol on state x, compiler-scheduled: E64_FRONT and E64_BACK on the group sequence's record {rcp lo, rcp hi,
+// bias << 6 | rcp_shift, cmpl} and ring (wk: the lane's folded write position); a lane that is not `active` does nothing
+__device__ __forceinline__ void r64x2_put_one(uint64_t &x, uint32_t sym, bool active, uint8_t *smem, uint32_t &wk, uint32_t ringbase,
+                                              uint32_t kv, uint32_t &worst)
+{
+    const uint4 rec = reinterpret_cast<const uint4 *>(smem)[sym];
+    if (active) {
+        worst = rec.w > worst ? rec.w : worst;
+        if ((int32_t)((rec.w << kv) + (uint32_t)(x >> 32)) < 0) { // rans64.h:83-88 on the high dword (see the uniform kernel)
+            wk = ringbase + ((wk - 256u) & 0x1fffu);
+            *reinterpret_cast<uint32_t *>(smem + wk) = (uint32_t)x;
+            x >>= 32;
+        }
+        const uint64_t rcp = (uint64_t)rec.x | ((uint64_t)rec.y << 32);
+        const uint64_t qv = __umul64hi(x, rcp) >> (rec.z & 63u); // rans64.h:91
+        x = x + (rec.z >> 6) + qv * rec.w;                       // rans64.h:92
+    }
+}
+
+template <bool TRACK>
+__global__ void __launch_bounds__(1024) k_encode_batch_r64_lanes(const EncParams p)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    {   // (k_encode_lanes_r64x2's prologue, written out) EncRec {freq | rcp_shift << 24, bias, rcp lo, rcp hi} (model.h) ->
+        // {rcp lo, rcp hi, bias << 6 | rcp_shift, cmpl}; a symbol without a frequency: cmpl = M, the largest value any record holds
+        const uint4 *g = reinterpret_cast<const uint4 *>(p.enc_recs);
+        uint4 *l = reinterpret_cast<uint4 *>(smem);
+        for (uint32_t i = threadIdx.x; i < 256u; i += blockDim.x) {
+            uint4 r = i < p.nsyms ? g[i] : uint4{0u, 0u, 0u, 0u};
+            const uint32_t freq = r.x & 0xffffffu;
+            l[i] = freq ? uint4{r.z, r.w, (r.y << 6) | (r.x >> 24), (1u << p.scale_bits) - freq}
+                        : uint4{0u, 0u, 0u, 1u << p.scale_bits};
+        }
+    }
+    __syncthreads();
+    if (!lds_starts_at_zero(smem)) { // the asm addresses the record table by raw LDS offsets
+        if (threadIdx.x == 0)
+            atomicOr(p.flags, 4u);
+        return;
+    }
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t ringbase = kR64EncTable + wave * kR64EncRing; // LDS byte offset, 8 KiB aligned
+    const uint32_t *ringp = reinterpret_cast<const uint32_t *>(smem + ringbase);
+    uint32_t k4 = 4u, m256 = 0xffffff00u, m1fff = 0x1fffu, ringv = ringbase, kv = 31u - p.scale_bits;
+    asm volatile("v_mov_b32 %0, %0" : "+v"(k4)); // VGPR copies: a VALU op with a literal or an SGPR operand issues slower
+    asm volatile("v_mov_b32 %0, %0" : "+v"(m256));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(m1fff));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(ringv));
+    asm volatile("v_mov_b32 %0, %0" : "+v"(kv));
+    const uint32_t m = lane & 3u, q4 = lane & ~3u;
+    const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 63u) >> 6); // wave-loads, one per claim (the last one may hold fewer than 64
+                                                                         // streams); stream indices are 32-bit
+    uint32_t worst = 0;
+    WorkClaims work;
+    work.init(p.claims, wave, waves_per_block);
+    for (;;) {
+        const uint64_t load = work.take(lane);
+        if ((load >> 32) != 0 || (uint32_t)load >= loads) // (scalar compares)
+            break;
+        // ---- this lane's stream: its index entries, all of them the caller's data
+        const uint64_t pos = load * 64u + lane;
+        const bool exists = pos < p.nchunks;
+        uint32_t s = (uint32_t)pos; // (stream indices are 32-bit)
+        if (exists && p.order)
+            s = p.order[pos];
+        const bool named = exists && s < p.nchunks;
+        if (exists && !named) // an order entry that names no stream: nothing coded, no index entry
+            atomicOr(p.flags, 2048u);
+        uint64_t first = 0, slot_at = 0, slot_end = 0;
+        uint32_t count = 0;
+        if (named) {
+            first = p.sym_offsets[s];
+            count = p.sym_counts[s];
+            slot_at = p.slot_offsets[s];
+            slot_end = p.slot_offsets[(uint64_t)s + 1u];
+        }
+        // what rans_amd_chunk_bound() asks for this stream: a dword per symbol + the two flushed states
+        const uint64_t need = ((uint64_t)count * 4u + 2u * 8u + 15u) & ~15ull;
+        const uint64_t slot_size = slot_end - slot_at;
+        const bool fits = ((slot_at | slot_end) & 15u) == 0 && slot_end >= slot_at && slot_end <= p.out_cap && slot_size >= need &&
+                          slot_size <= 0xfffffff0ull;
+        if (named && !fits) { // nothing of this stream is written
+            atomicOr(p.flags, 2u);
+            p.lengths[s] = 0u;
+            p.offsets[s] = slot_end;
+        }
+        bool live = named && fits; // the lane holds a stream that is still being coded
+        const uint32_t slot16 = live ? (uint32_t)(slot_size >> 4) : 0u; // the slot in 16-byte pieces
+        const uint64_t out_end = reinterpret_cast<uint64_t>(p.scratch) + slot_end; // (live: 16-byte aligned, inside the container)
+        const uint64_t src = reinterpret_cast<uint64_t>(p.syms) + first;
+        const bool by_quad = (src & 63u) == 0, by_dwords = (src & 3u) == 0;
+        const uint32_t blocks = (live && by_dwords) ? count >> 6 : 0u; // (count < 2^30 follows from the slot's size)
+        const uint32_t tail = live ? count - (blocks << 6) : 0u;
+        const uint32_t qblocks = by_quad ? blocks : 0u; // blocks that the quad fetches
+        // (wave_max32 is the pair kernels': it takes a value that both lanes of a pair hold, so the pair's larger one goes in)
+        const uint32_t blocks_o = quad_perm<0xB1>(blocks), tail_o = quad_perm<0xB1>(tail); // the lane ^ 1's
+        const uint32_t max_blocks = wave_max32(blocks > blocks_o ? blocks : blocks_o), max_tail = wave_max32(tail > tail_o ? tail : tail_o);
+
+        uint64_t xA = 1ull << 31, xB = 1ull << 31; // Rans64EncInit
+        uint32_t wk = ringbase + lane * 4u;        // the window's end: the first dword goes to ring dword 31
+        uint32_t fl = 0;                           // lines 1 .. fl of this lane's stream are in memory
+
+        // bytes of this lane's stream that are in the ring only: below line fl, at most 127
+        auto pending = [&]() { return (((fl & 1u) << 6) - ((wk >> 6) & 124u)) & 127u; };
+        // The whole wave takes part, outside any divergent branch.  A lane that `wants` has its next line, fl + 1, written
+        // by its quad: the pieces that hold any of the `have` stream bytes so far, and none that starts below the slot.
+        auto flush = [&](bool wants, uint32_t have) {
+            uint32_t req = 0; // line << 2 | first piece with stream bytes
+            if (wants) {
+                const uint64_t reach = 64ull * (fl + 1u);
+                req = ((fl + 1u) << 2) | (reach > have ? (uint32_t)((reach - have) >> 4) : 0u);
+                fl += 1u;
+            }
+            if (__builtin_amdgcn_ballot_w64(req != 0u) == 0)
+                return;
+            const uint32_t elo = (uint32_t)out_end, ehi = (uint32_t)(out_end >> 32);
+            auto piece = [&](auto tc, uint32_t rt, uint32_t lo, uint32_t hi, uint32_t sl) { // rt: what the quad's lane t asked for
+                constexpr uint32_t t = decltype(tc)::value;
+                const uint32_t line = rt >> 2;
+                const uint32_t below16 = 4u * line - m; // this lane's piece starts 16 * below16 bytes under the slot's end
+                if (rt != 0u && m >= (rt & 3u) && below16 <= sl) {
+                    // ring half (line & 1), dwords 4 m .. 4 m + 3 of lane q4 + t
+                    const uint32_t *at = ringp + (line & 1u) * 1024u + m * 256u + q4 + t;
+                    const u32x4 v = {at[0], at[64], at[128], at[192]};
+                    *reinterpret_cast<u32x4 RANS_GLOBAL *>((((uint64_t)hi << 32) | lo) - 16ull * below16) = v;
+                }
+            };
+            piece(std::integral_constant<uint32_t, 0>{}, quad_perm<0x00>(req), quad_perm<0x00>(elo), quad_perm<0x00>(ehi), quad_perm<0x00>(slot16));
+            piece(std::integral_constant<uint32_t, 1>{}, quad_perm<0x55>(req), quad_perm<0x55>(elo), quad_perm<0x55>(ehi), quad_perm<0x55>(slot16));
+            piece(std::integral_constant<uint32_t, 2>{}, quad_perm<0xAA>(req), quad_perm<0xAA>(elo), quad_perm<0xAA>(ehi), quad_perm<0xAA>(slot16));
+            piece(std::integral_constant<uint32_t, 3>{}, quad_perm<0xFF>(req), quad_perm<0xFF>(elo), quad_perm<0xFF>(ehi), quad_perm<0xFF>(slot16));
+        };
+
+        // ---- the rounds: the symbols behind the last whole block, the stream's last symbol first
+        {
+            const uint8_t RANS_GLOBAL *tsrc = reinterpret_cast<const uint8_t RANS_GLOBAL *>(src);
+            uint32_t sym_next = tail != 0u ? (uint32_t)tsrc[count - 1u] : 0u;
+            for (uint32_t k = 0; k < max_tail; ++k) {
+                const bool active = k < tail;
+                const uint32_t i = count - 1u - k; // (active lanes: the symbol's index in the stream)
+                const uint32_t sym = sym_next;
+                sym_next = k + 1u < tail ? (uint32_t)tsrc[i - 1u] : 0u;
+                const bool odd = (i & 1u) != 0u;
+                uint64_t x = odd ? xB : xA;
+                uint32_t w = 0;
+                r64x2_put_one(x, sym, active, smem, wk, ringbase, kv, w);
+                if (TRACK)
+                    worst = w > worst ? w : worst;
+                xA = active && !odd ? x : xA;
+                xB = active && odd ? x : xB;
+                if ((k & 15u) == 15u) // (sixteen rounds: at most 64 bytes)
+                    flush(live && pending() >= 64u, ~0u);
+            }
+            flush(live && pending() >= 64u, ~0u);
+        }
+
+        // ---- whole blocks, the lane's last block first
+        // symbol lines: instruction t = the line of the quad's lane t (while that lane has blocks left), this lane its piece m
+        auto load_block = [&](u32x4 (&v)[4], uint32_t q) {
+            const uint32_t slo = (uint32_t)src, shi = (uint32_t)(src >> 32);
+            const uint32_t qbs[4] = {quad_perm<0x00>(qblocks), quad_perm<0x55>(qblocks), quad_perm<0xAA>(qblocks), quad_perm<0xFF>(qblocks)};
+            const uint32_t los[4] = {quad_perm<0x00>(slo), quad_perm<0x55>(slo), quad_perm<0xAA>(slo), quad_perm<0xFF>(slo)};
+            const uint32_t his[4] = {quad_perm<0x00>(shi), quad_perm<0x55>(shi), quad_perm<0xAA>(shi), quad_perm<0xFF>(shi)};
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                v[t] = u32x4{0u, 0u, 0u, 0u}; // (a lane without a block codes zeros)
+                if (q < qbs[t]) // block qbs[t] - 1 - q of lane t's stream, my piece of it
+                    v[t] = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(
+                        (((uint64_t)his[t] << 32) | los[t]) + ((uint64_t)(qbs[t] - 1u - q) << 6) + 16u * m));
+            }
+        };
+        u32x4 cur[4], nxt[4];
+        load_block(cur, 0u);
+        quad_transpose(cur[0], cur[1], cur[2], cur[3], lane);
+        for (uint32_t q = 0;; ++q) {
+            // ---- finalise the lanes whose last group is behind them
+            const bool fin = live && q == blocks;
+            if (__builtin_amdgcn_ballot_w64(fin) != 0) {
+                uint32_t len = 0, in_ring = 0;
+                if (fin) {
+                    // state 1 first, state 0 ends up first in memory (main64.cpp:244-245; Rans64EncFlush: two dwords, low first)
+                    auto emit = [&](uint32_t v) {
+                        wk = ringbase + ((wk - 256u) & 0x1fffu);
+                        *reinterpret_cast<uint32_t *>(smem + wk) = v;
+                    };
+                    emit((uint32_t)(xB >> 32));
+                    emit((uint32_t)xB);
+                    emit((uint32_t)(xA >> 32));
+                    emit((uint32_t)xA);
+                    in_ring = pending(); // <= 63 + 16
+                    len = fl * kLaneLine + in_ring;
+                }
+                flush(fin && in_ring > 0u, len); // the line(s) that hold anything
+                flush(fin && in_ring > 64u, len);
+                if (fin) {
+                    p.lengths[s] = len;
+                    p.offsets[s] = out_end - reinterpret_cast<uint64_t>(p.scratch) - len; // the slot's end - len
+                }
+                live = live && !fin; // dead: no line, no index store ever again
+            }
+            if (q == max_blocks)
+                break;
+            const bool run = q < blocks;
+            if (q + 1u < max_blocks)
+                load_block(nxt, q + 1u);
+            if (run && !by_quad) { // a stream on the 4-byte grid: the lane's own 64 bytes
+                const uint64_t a = src + ((uint64_t)(blocks - 1u - q) << 6);
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    cur[g] = *reinterpret_cast<const lanes_enc_u32x4_a4 RANS_GLOBAL *>(a + 16u * g);
+            }
+            const uint32_t worst_keep = worst;
+#pragma unroll
+            for (int g = 3; g >= 0; --g) {
+                r64x2_encode_group<TRACK>(xA, xB, wk, worst, cur[g][3], cur[g][2], cur[g][1], cur[g][0], k4, m256, m1fff, ringv,
+                                          kv); // (under full exec: see the head)
+                flush(live && pending() >= 64u, ~0u);
+            }
+            worst = run ? worst : worst_keep;
+            if (q + 1u < max_blocks) {
+                quad_transpose(nxt[0], nxt[1], nxt[2], nxt[3], lane);
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    cur[t] = nxt[t];
+            }
+        }
+    }
+    if (TRACK && __builtin_amdgcn_ballot_w64(worst >= (1u << p.scale_bits)) != 0 && lane == 0)
+        atomicOr(p.flags, 1u);
+}
+
 // Lane-per-stream encoder, second generation: symbols arrive as 16-byte per-lane loads
 // (one scattered access per 16 symbols instead of per symbol), one group prefetched.
 template <int FMT, int NW>
@@ -1112,6 +1410,35 @@ bool encode_lanes_sized_ok(int format, const EncParams &p, int num_cus)
     if (format == FMT_WORD && encode_word_groups_applicable(p)) // (its block stores stop at the slot's first byte: encode_groups.hip)
         return true;
     return encode_lanes_staged_waves(p, num_cus, encode_lanes_min_batches(format, p, num_cus)) >= 1;
+}
+
+// The ragged form of the 2-way rans64 lane encoder: rans64 over u8 symbols at the scale_bits the group sequence takes (the
+// caller has checked the format: the full-width variant is another kernel format), from 64 streams on; any symbol count, any
+// symbol address.  The record table and at least one wave's ring inside the CU's 160 KiB of LDS (they always are: 16 KiB).
+bool encode_batch_r64_lanes_applicable(const EncParams &p)
+{
+    return p.n_ways == 2 && p.sym_bytes == 1 && p.nsyms <= 256 && p.scale_bits >= 7 && p.scale_bits <= 16 && p.nchunks >= 64 &&
+           (reinterpret_cast<uintptr_t>(p.scratch) & 15u) == 0 && kR64EncTable + kR64EncRing <= 160 * 1024;
+}
+
+hipError_t launch_encode_batch_r64_lanes(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
+{
+    if (!encode_batch_r64_lanes_applicable(p) || !p.enc_recs || !p.sym_offsets || !p.sym_counts || !p.slot_offsets || !p.lengths || !p.offsets ||
+        !p.flags)
+        return hipErrorInvalidValue;
+    // one block per CU, as many waves as the table leaves rings for, sixteen at the most; a batch that does not fill them
+    // spreads its wave-loads evenly (lanes_even_waves), as the lane decoder's launcher does
+    const uint32_t room = (uint32_t)((160 * 1024 - kR64EncTable) / kR64EncRing);
+    const uint32_t max_waves = room > 16 ? 16 : room;
+    const uint64_t loads = (p.nchunks + 63) / 64;
+    const uint32_t sw = loads >= (uint64_t)num_cus * max_waves ? max_waves : lanes_even_waves(loads, num_cus, max_waves);
+    static std::atomic<uint64_t> lds_ok[2] = {{0}, {0}};
+    if (name)
+        *name = KernelId::encode_batch_r64_lanes;
+    const size_t lds = kR64EncTable + (size_t)sw * kR64EncRing;
+    // (a model in which every byte value has a frequency: the variant without the search for record-less symbols)
+    return p.dense256 ? launch_lanes(k_encode_batch_r64_lanes<false>, lds_ok[0], 160 * 1024, lanes_grid(loads, sw, num_cus), 64 * sw, lds, stream, p)
+                      : launch_lanes(k_encode_batch_r64_lanes<true>, lds_ok[1], 160 * 1024, lanes_grid(loads, sw, num_cus), 64 * sw, lds, stream, p);
 }
 
 hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)

@@ -116,6 +116,11 @@ hipError_t launch_encode_lanes(int format, const EncParams &p, int num_cus, hipS
 // and at least one wave's rings inside the CU's 160 KiB of LDS (the launcher sizes the block from what the tables leave)
 bool decode_batch_r64_lanes_applicable(const DecParams &p);
 hipError_t launch_decode_batch_r64_lanes(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+// ... and of the 2-way rans64 lane encoder (rans_amd_encode_batch[_ordered], kBatchFamilies; encode_lanes.hip): 64 STREAMS per
+// wave, one per lane, each with its own symbol count, symbol address and slot, from 64 streams on, scale_bits 7..16 (the
+// launcher sizes the block: 8 KiB of records and 8 KiB of ring per wave)
+bool encode_batch_r64_lanes_applicable(const EncParams &p);
+hipError_t launch_encode_batch_r64_lanes(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 // true when launch_encode_lanes would take the staged kernel for this request -- the one that can place its chunks
 // itself (EncParams::status); everything but status / offsets / out / out_cap must be filled in
 bool encode_lanes_fused(const EncParams &p, int num_cus);
@@ -125,8 +130,8 @@ bool encode_lanes_sized_ok(int format, const EncParams &p, int num_cus);
 // The streams-per-wave families of the ragged batches, in the order the launchers ask them: a context option sets the bit, and
 // a batch of the row's public format that the row's *_applicable accepts goes to the row's kernel; every other batch takes the
 // wave-per-stream kernels, under the options as well.  A decoder's row leaves the encoder's pair null and the other way round.
-// `streams` completes the option's E_ARG text.  (The ragged forms of the other lane kernels and of the 2-way rans64 ENCODER are
-// later work: one more row each.)
+// `streams` completes the option's E_ARG text.  (The ragged forms of the other lane kernels -- the 1-, 4- and 8-way interleaves -- are later
+// work: one more row each.)
 struct BatchFamily {
     int option; // RANS_AMD_OPT_*
     const char *option_name;
@@ -146,6 +151,7 @@ constexpr BatchFamily kBatchFamilies[] = {
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_LANES, kVarBatchLanes, RANS_AMD_FMT_R64, decode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_GROUPS, kVarBatchEncGroups, RANS_AMD_FMT_WORD, encode_batch_word_groups, "eight 8-way word streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_PAIRS, kVarBatchEncPairs, RANS_AMD_FMT_BYTE, encode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
+    RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_LANES, kVarBatchEncLanes, RANS_AMD_FMT_R64, encode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
 };
 #undef RANS_BATCH_DECODER
 #undef RANS_BATCH_ENCODER
