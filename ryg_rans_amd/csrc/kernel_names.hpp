@@ -12,13 +12,9 @@
 //   batch_byte_pairs_decode   ragged 2-way byte streams, 32 per wave, decoder (RANS_AMD_OPT_BATCH_PAIRS)
 //   batch_byte_pairs_encode   ... encoder (RANS_AMD_OPT_BATCH_ENCODE_PAIRS)
 //   batch_r64_lanes_decode    ragged 2-way rans64 streams, 64 per wave, decoder (RANS_AMD_OPT_BATCH_LANES)
-// A second list follows the first one: RANS_AMD_KERNEL_NAMES_ENCODE_LANES, the family
 //   batch_r64_lanes_encode    ... encoder (RANS_AMD_OPT_BATCH_ENCODE_LANES)
-// Its ids follow the first list's in KernelId, its rows are kEncodeLaneKernelEntries; kKernelEntries (what
-// tests/kernel_names_driver.cpp prints and tests/_kernel_rows.py reads) is the first list alone, and
-// tests/kernel_names_batch_encode_lanes_driver.cpp with tests/_batch_encode_lanes.py hold the second list to its rows.
-// kernel_entry(), kernel_name() and kernel_family() resolve ids from both.  (Folding the two into one list is a later refactor:
-// the row module has to know the family first, and the first list's printed lines are pinned by a test.)
+// Nine families in one list: a new kernel is one more row at the list's end (an id is its row's place, counted from 1, and the
+// ids that exist stay where they are); tests/kernel_names_driver.cpp prints every row and tests/_kernel_rows.py reads them.
 #pragma once
 
 namespace rans_amd {
@@ -75,9 +71,7 @@ namespace rans_amd {
     X(encode_batch_word_groups, "k_encode_batch_word_groups", batch_word_groups_encode)           \
     X(decode_batch_byte_pairs, "k_decode_batch_byte_pairs", batch_byte_pairs_decode)              \
     X(encode_batch_byte_pairs, "k_encode_batch_byte_pairs", batch_byte_pairs_encode)              \
-    X(decode_batch_r64_lanes, "k_decode_batch_r64_lanes", batch_r64_lanes_decode)
-
-#define RANS_AMD_KERNEL_NAMES_ENCODE_LANES(X)                                                     \
+    X(decode_batch_r64_lanes, "k_decode_batch_r64_lanes", batch_r64_lanes_decode)                 \
     X(encode_batch_r64_lanes, "k_encode_batch_r64_lanes", batch_r64_lanes_encode)
 
 enum class KernelFamily {
@@ -96,7 +90,6 @@ enum class KernelId {
     none, // no launch yet: the name is ""
 #define X(id, name, family) id,
     RANS_AMD_KERNEL_NAMES(X)
-    RANS_AMD_KERNEL_NAMES_ENCODE_LANES(X) // (behind the first list: an id of this one is kKernelEntryCount + 1 + its row)
 #undef X
 };
 
@@ -115,22 +108,8 @@ constexpr KernelEntry kKernelEntries[] = {
 };
 constexpr int kKernelEntryCount = (int)(sizeof(kKernelEntries) / sizeof(kKernelEntries[0]));
 
-// the second list's entries, in its order
-constexpr KernelEntry kEncodeLaneKernelEntries[] = {
-#define X(id, name, family) {KernelId::id, name, KernelFamily::family, #family},
-    RANS_AMD_KERNEL_NAMES_ENCODE_LANES(X)
-#undef X
-};
-constexpr int kEncodeLaneKernelEntryCount = (int)(sizeof(kEncodeLaneKernelEntries) / sizeof(kEncodeLaneKernelEntries[0]));
-
-constexpr const KernelEntry &kernel_entry(KernelId id) // (not for KernelId::none)
-{
-    return (int)id <= kKernelEntryCount ? kKernelEntries[(int)id - 1] : kEncodeLaneKernelEntries[(int)id - 1 - kKernelEntryCount];
-}
+constexpr const KernelEntry &kernel_entry(KernelId id) { return kKernelEntries[(int)id - 1]; } // (not for KernelId::none)
 constexpr const char *kernel_name(KernelId id) { return id == KernelId::none ? "" : kernel_entry(id).name; }
 constexpr KernelFamily kernel_family(KernelId id) { return kernel_entry(id).family; } // (not for KernelId::none)
-static_assert(kernel_entry(KernelId::decode_batch_r64_lanes).id == KernelId::decode_batch_r64_lanes &&
-                  kernel_entry(KernelId::encode_batch_r64_lanes).id == KernelId::encode_batch_r64_lanes,
-              "ids of both lists resolve to their own rows");
 
 } // namespace rans_amd

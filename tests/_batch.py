@@ -205,9 +205,10 @@ class Coded:
 class PoolBatch:
     """n streams, each one of at most POOL prototypes: the oracle codes every prototype once, the batch (index, container,
     expected output) is put together from them on the device.  The container is the oracle's -- the prototypes' streams in a
-    shuffled order at 1-byte-aligned offsets with gaps, every stream of the batch pointing at its prototype's."""
+    shuffled order at 1-byte-aligned offsets with gaps, every stream of the batch pointing at its prototype's.  The symbols are
+    laid out at sym_align = `align`."""
 
-    def __init__(self, R, ctx, torch, oracle, row, proto_counts, n, seed):
+    def __init__(self, R, ctx, torch, oracle, row, proto_counts, n, seed, align=4):
         import bench
         self.R, self.torch = R, torch
         pc = np.ascontiguousarray(proto_counts, dtype=np.uint32)
@@ -237,7 +238,7 @@ class PoolBatch:
         pick = np.concatenate((np.arange(min(pc.size, n)), rng.integers(0, pc.size, max(0, n - pc.size))))
         pick = pick[rng.permutation(pick.size)]
         self.counts = pc[pick]
-        self.sym_offs, self.slot_offs = R.batch_layout(self.counts, row["fmt"], 2, 4)
+        self.sym_offs, self.slot_offs = R.batch_layout(self.counts, row["fmt"], 2, align)
 
         def dev(a, t):
             return torch.from_numpy(np.ascontiguousarray(a).astype(t)).cuda()

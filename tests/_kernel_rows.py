@@ -22,9 +22,9 @@ CSRC = os.path.join(ROOT, "ryg_rans_amd", "csrc")
 UNIFORM, BATCH, BATCH_MODELS = "uniform", "batch", "batch_models"
 BATCH_WORD_GROUPS_DECODE, BATCH_WORD_GROUPS_ENCODE = "batch_word_groups_decode", "batch_word_groups_encode"
 BATCH_BYTE_PAIRS_DECODE, BATCH_BYTE_PAIRS_ENCODE = "batch_byte_pairs_decode", "batch_byte_pairs_encode"
-BATCH_R64_LANES_DECODE = "batch_r64_lanes_decode"
+BATCH_R64_LANES_DECODE, BATCH_R64_LANES_ENCODE = "batch_r64_lanes_decode", "batch_r64_lanes_encode"
 FAMILIES = (UNIFORM, BATCH, BATCH_MODELS, BATCH_WORD_GROUPS_DECODE, BATCH_WORD_GROUPS_ENCODE, BATCH_BYTE_PAIRS_DECODE,
-            BATCH_BYTE_PAIRS_ENCODE, BATCH_R64_LANES_DECODE)
+            BATCH_BYTE_PAIRS_ENCODE, BATCH_R64_LANES_DECODE, BATCH_R64_LANES_ENCODE)
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,17 +48,20 @@ def registry():
 # context options (the numbers are the ABI's, tests/test_abi.py)
 LANE_FUSED, FUSED, DUAL = R.OPT_LANE_FUSED_PLACEMENT, R.OPT_FUSED_PLACEMENT, R.OPT_DUAL_DECODE
 OPT_BATCH_GROUPS, OPT_BATCH_ENCODE_GROUPS = R.OPT_BATCH_GROUPS, R.OPT_BATCH_ENCODE_GROUPS
-OPT_BATCH_PAIRS, OPT_BATCH_ENCODE_PAIRS, OPT_BATCH_LANES = R.OPT_BATCH_PAIRS, R.OPT_BATCH_ENCODE_PAIRS, R.OPT_BATCH_LANES
+OPT_BATCH_PAIRS, OPT_BATCH_ENCODE_PAIRS = R.OPT_BATCH_PAIRS, R.OPT_BATCH_ENCODE_PAIRS
+OPT_BATCH_LANES, OPT_BATCH_ENCODE_LANES = R.OPT_BATCH_LANES, R.OPT_BATCH_ENCODE_LANES
 OPTIONS = ("LANE_KERNELS", "LANE_FUSED_PLACEMENT", "FUSED_PLACEMENT", "DUAL_DECODE", "ENC_SCRATCH_RING", "BATCH_GROUPS",
-           "BATCH_ENCODE_GROUPS", "BATCH_PAIRS", "BATCH_ENCODE_PAIRS", "BATCH_LANES")  # RANS_AMD_OPT_*, by value
+           "BATCH_ENCODE_GROUPS", "BATCH_PAIRS", "BATCH_ENCODE_PAIRS", "BATCH_LANES", "BATCH_ENCODE_LANES")  # RANS_AMD_OPT_*, by value
 
 
 def check_option_constant(name, value):
-    """RANS_AMD_OPT_<name> is `value` in the header and in the package, every option 0..9 is where it was, the version has not
-    moved (additions only), and a NULL context is refused before the option is looked at (the values need a context: the
-    family's GPU file)."""
+    """RANS_AMD_OPT_<name> is `value` in the header and in the package, every option of OPTIONS is where it was and the
+    header's enum holds no other, the version has not moved (additions only), and a NULL context is refused before the option is
+    looked at (the values need a context: the family's GPU file)."""
     header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
     assert OPTIONS[value] == name
+    enum = re.search(r"enum rans_amd_option \{(.*?)\n\};", header, re.S).group(1)
+    assert len(re.findall(r"^    RANS_AMD_OPT_\w+\s*=\s*\d+", enum, re.M)) == len(OPTIONS) == 11
     for v, n in enumerate(OPTIONS):
         m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % n, header)
         assert m and int(m.group(1)) == v, n
@@ -304,7 +307,24 @@ LROW = {r["id"]: r for r in LANE_ROWS}
 LMAIN, LANE16 = LROW["r64-2-lanes"], LROW["r64-2-lanes-16bit"]  # (L16 is the lane ENCODER's name above)
 LANE_RATE_ROW = {14: LMAIN, 16: LANE16}  # the rows of _batch_lanes.rate_batch, by scale_bits
 
-# ---- the five streams-per-wave families, one descriptor each: what their GPU and host files differ in -----------------------
+
+# ... and encoder (tests/test_gpu_batch_encode_lanes.py)
+def _enc_lane_row(rid, sb, K):
+    return {"id": rid, "fmt": FMT_R64, "sb": sb, "K": K, "ways": 2, "decode": "k_decode_batch<r64>", "encode": "k_encode_batch_r64_lanes"}
+
+
+ENC_LANE_ROWS = [
+    _enc_lane_row("r64-2-enc-lanes", 14, 256),            # the reference's scale_bits (main64.cpp)
+    _enc_lane_row("r64-2-enc-lanes-16bit", 16, 256),      # a frequency of 2^16 is inside the working range
+    _enc_lane_row("r64-2-enc-lanes-12bit", 12, 256),
+    _enc_lane_row("r64-2-enc-lanes-64sym-7bit", 7, 64),   # the smallest scale_bits; the record table is padded to 256
+    _enc_lane_row("r64-2-enc-lanes-64sym-10bit", 10, 64),
+]
+ELROW = {r["id"]: r for r in ENC_LANE_ROWS}
+ELMAIN, EL16 = ELROW["r64-2-enc-lanes"], ELROW["r64-2-enc-lanes-16bit"]
+ENC_LANE_RATE_ROW = {14: ELMAIN, 16: EL16}
+
+# ---- the six streams-per-wave families, one descriptor each: what their GPU and host files differ in -----------------------
 # side: the row key of the family's own kernel; streams: per wave; wave_kernel: what the main row's shape reports with the option
 # off; shapes: the (sb, K) of the rows; graph: the captured-graph child's format, scale_bits and option, by name
 Family = collections.namedtuple("Family", "option side fmt ways streams rows main wave_kernel family shapes graph")
@@ -319,6 +339,9 @@ ENC_GROUPS = Family(OPT_BATCH_ENCODE_GROUPS, "encode", FMT_WORD, 8, 8, ENC_GROUP
                     BATCH_WORD_GROUPS_ENCODE, [(12, 256)], ("FMT_WORD", 12, "OPT_BATCH_ENCODE_GROUPS"))
 ENC_PAIRS = Family(OPT_BATCH_ENCODE_PAIRS, "encode", FMT_BYTE, 2, 32, ENC_PAIR_ROWS, EMAIN, "k_encode_batch<byte>",
                    BATCH_BYTE_PAIRS_ENCODE, PAIR_SHAPES, ("FMT_BYTE", 14, "OPT_BATCH_ENCODE_PAIRS"))
+ENC_LANES = Family(OPT_BATCH_ENCODE_LANES, "encode", FMT_R64, 2, 64, ENC_LANE_ROWS, ELMAIN, "k_encode_batch<r64>",
+                   BATCH_R64_LANES_ENCODE, LANE_SHAPES, ("FMT_R64", 14, "OPT_BATCH_ENCODE_LANES"))
+STREAM_FAMILIES = (GROUPS, ENC_GROUPS, PAIRS, ENC_PAIRS, LANES, ENC_LANES)
 WAVE_ENCODER = {FMT_WORD: "k_encode_batch<word>", FMT_BYTE: "k_encode_batch<byte>", FMT_R64: "k_encode_batch<r64>"}
 
 

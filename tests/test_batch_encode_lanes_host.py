@@ -1,9 +1,8 @@
 """Ragged batches CODED with sixty-four 2-way rans64 streams per wave (RANS_AMD_OPT_BATCH_ENCODE_LANES), the part that needs no
-GPU: the option's constant, the registry's second list held to ENC_LANE_ROWS, the first list left as it was, the proof that
-the rate inputs of tests/test_gpu_batch_encode_lanes.py reach the bounds that file claims, and every stream of that file's
+GPU: the option's constant, the registry's family held to ENC_LANE_ROWS, the family's id at the end of the one list, the proof
+that the rate inputs of tests/test_gpu_batch_encode_lanes.py reach the bounds that file claims, and every stream of that file's
 wave-loads inside its slot under the oracle."""
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -13,54 +12,36 @@ import _batch_lanes as L
 import _stream_rate as S
 import ryg_rans_amd as R
 from _batch import no_zero_batch
-from _kernel_rows import CSRC, LANE_SHAPES, ROOT, registry
+from _kernel_rows import (BATCH_R64_LANES_ENCODE, CSRC, ENC_LANE_ROWS, ENC_LANES, LANE_SHAPES, check_family_rows, check_option_constant,
+                          registry)
 from _oracle import FMT_R64
 
 
 def test_batch_encode_lanes_option_constant():
-    """RANS_AMD_OPT_BATCH_ENCODE_LANES is 10 in the header and in the package, every option 0..9 is where it was, the version
-    has not moved (additions only), and a NULL context is refused before the option is looked at.  (tests/_kernel_rows.py's
-    check_option_constant indexes its own ten-entry tuple: this is that check over eleven.)"""
-    header = open(os.path.join(ROOT, "include", "ryg_rans_amd.h")).read()
-    assert len(E.OPTIONS) == 11 and E.OPTIONS[10] == "BATCH_ENCODE_LANES" and E.OPT_BATCH_ENCODE_LANES == 10
-    for v, n in enumerate(E.OPTIONS):
-        m = re.search(r"RANS_AMD_OPT_%s\s*=\s*(\d+)" % n, header)
-        assert m and int(m.group(1)) == v, n
-        assert getattr(R, "OPT_" + n) == v, n
-    enum = re.search(r"enum rans_amd_option \{(.*?)\n\};", header, re.S).group(1)
-    assert len(re.findall(r"^    RANS_AMD_OPT_\w+\s*=\s*\d+", enum, re.M)) == 11
-    assert re.search(r"#define\s+RANS_AMD_VERSION\s+600\b", header)
-    assert R.lib().rans_amd_ctx_set_option(None, 10, 1) == R.E_ARG
-    assert b"ctx is NULL" in R.lib().rans_amd_last_error()
+    check_option_constant("BATCH_ENCODE_LANES", 10)
 
 
 def test_no_lane_batch_enc_kernel_without_a_row():
-    """The second list prints exactly one line; its family's names are the encode names of ENC_LANE_ROWS, in both directions
-    (the driver itself fails unless the id is kKernelEntryCount + 1 and leads back to its row, and on a name or family of the
-    first list); the rows are LANE_SHAPES with the wave decoder; and the check has teeth: without the rows the name is reported
-    missing."""
-    assert E.second_list() == [("batch_r64_lanes_encode", "k_encode_batch_r64_lanes")]
-    d = E.ENC_LANES
-    E.check_second_list_rows(d)
+    """The family holds exactly one name; the family's names are the encode names of ENC_LANE_ROWS, in both directions; the rows
+    are LANE_SHAPES with the wave decoder; and the check has teeth: without its rows the name is reported missing
+    (check_family_rows)."""
+    d = ENC_LANES
+    check_family_rows(d)
+    assert registry()[BATCH_R64_LANES_ENCODE] == {"k_encode_batch_r64_lanes"}
     assert d.option == 10 and d.side == "encode" and d.fmt == FMT_R64 and d.ways == 2 and d.streams == 64
     assert d.main["sb"] == 14 and d.wave_kernel == "k_encode_batch<r64>" and d.shapes == LANE_SHAPES
     assert d.graph == ("FMT_R64", 14, "OPT_BATCH_ENCODE_LANES")
-    assert all(r["decode"] == "k_decode_batch<r64>" and r["encode"] == E.KERNEL for r in E.ENC_LANE_ROWS)
-    try:
-        E.check_second_list_rows(d, rows=[])
-    except AssertionError as e:
-        assert "k_encode_batch_r64_lanes" in str(e) and "kernels no row expects" in str(e)
-    else:
-        raise AssertionError("a name without a row went unnoticed")
+    assert all(r["decode"] == "k_decode_batch<r64>" and r["encode"] == "k_encode_batch_r64_lanes" for r in ENC_LANE_ROWS)
     src = open(os.path.join(CSRC, "kernel_names.hpp")).read()
     assert src.count('"k_encode_batch_r64_lanes"') == 1
 
 
 def test_the_id_follows_the_first_list(tmp_path):
-    """The second list's one id is kKernelEntryCount + 1 = 53, and an identifier in neither list does not compile."""
+    """The lane encoder's id is the one list's last, 53 as it was behind a list of 52; both lane ids lead to their own
+    families; and an identifier that is in no list does not compile."""
     src = tmp_path / "id.cpp"
     src.write_text('#include "kernel_names.hpp"\nusing namespace rans_amd;\n'
-                   'static_assert((int)KernelId::encode_batch_r64_lanes == kKernelEntryCount + 1 && kKernelEntryCount == 52, "id");\n'
+                   'static_assert((int)KernelId::encode_batch_r64_lanes == 53 && kKernelEntryCount == 53, "id");\n'
                    'static_assert(kernel_entry(KernelId::encode_batch_r64_lanes).family == KernelFamily::batch_r64_lanes_encode, "row");\n'
                    'static_assert(kernel_entry(KernelId::decode_batch_r64_lanes).family == KernelFamily::batch_r64_lanes_decode, "row");\n'
                    'int main() { return 0; }\n')
@@ -68,15 +49,6 @@ def test_the_id_follows_the_first_list(tmp_path):
     src.write_text('#include "kernel_names.hpp"\nint main() { return (int)rans_amd::KernelId::encode_batch_r64_lanes_no_such; }\n')
     r = subprocess.run(["g++", "-std=c++17", "-I", CSRC, "-fsyntax-only", str(src)], capture_output=True, text=True)
     assert r.returncode != 0 and "encode_batch_r64_lanes_no_such" in r.stderr
-
-
-def test_the_first_list_does_not_hold_the_name():
-    """(tests/test_batch_lanes_host.py pins the first list's 52 lines; here only: the new name is not among them.)"""
-    registry()
-    exe = os.path.join(ROOT, "build", "kernel_names", "kernel_names_driver")
-    lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
-    assert lines and not [ln for ln in lines if "k_encode_batch_r64_lanes" in ln or "batch_r64_lanes_encode" in ln]
-    assert all(E.KERNEL not in names for names in registry().values())
 
 
 def test_rate_inputs_reach_the_rings_bound():

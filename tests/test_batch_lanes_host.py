@@ -26,13 +26,14 @@ def test_no_lane_batch_kernel_without_a_row():
 
 
 def test_the_one_list_is_what_it_is():
-    """tests/kernel_names_driver.cpp prints the registry's 52 lines: the 51 it always printed, in their order, and the lane
-    family's one behind them (its id stays what it was)."""
+    """tests/kernel_names_driver.cpp prints the registry's 53 lines: the 52 it printed before the lane encoder's family joined
+    the list, in their order, and that family's one behind them (every id stays what it was)."""
     registry()
     exe = os.path.join(ROOT, "build", "kernel_names", "kernel_names_driver")
     lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
-    assert len(lines) == 52 and lines[0] == "uniform\tk_decode_word64"
+    assert len(lines) == 53 and lines[0] == "uniform\tk_decode_word64"
     assert lines[50] == "batch_byte_pairs_encode\tk_encode_batch_byte_pairs" and lines[51] == "batch_r64_lanes_decode\tk_decode_batch_r64_lanes"
+    assert lines[52] == "batch_r64_lanes_encode\tk_encode_batch_r64_lanes"
     assert [ln for ln in lines if "r64_lanes" in ln] == lines[51:]
 
 

@@ -1,8 +1,8 @@
 """Ragged batches of the reference's 2-way rans64 layout CODED with sixty-four streams per wave: k_encode_batch_r64_lanes, the
 kernel rans_amd_encode_batch[_ordered] launches on a context with RANS_AMD_OPT_BATCH_ENCODE_LANES = 1.
 
-ENC_LANE_ROWS (tests/_batch_encode_lanes.py) names the kernel the library must report (tests/test_batch_encode_lanes_host.py
-holds the rows to the registry's second list).  The helpers are tests/_batch.py's: run_row checks the reported kernel, every
+ENC_LANE_ROWS (tests/_kernel_rows.py) names the kernel the library must report (tests/test_batch_encode_lanes_host.py holds the
+rows to the registry's family).  The helpers are tests/_batch.py's: run_row checks the reported kernel, every
 stream byte for byte against the oracle's, each ending at its slot's end, and decodes the result (k_decode_batch<r64>: the
 context has the encoder's option alone).
 
@@ -23,15 +23,15 @@ import numpy as np
 import pytest
 
 import _batch_lanes as L
-from _batch import (POISON, POOL, Batch, ModelBatch, check_bad_slots, check_encode_order, check_no_false_e_model,
+from _batch import (POISON, POOL, Batch, ModelBatch, PoolBatch, check_bad_slots, check_encode_order, check_no_false_e_model,
                     check_option_takes_zero_or_one, check_other_shape_keeps_its_kernels, check_true_e_model, draw_lengths, draw_log_uniform,
                     mandatory_lengths, option_contexts, resident_waves, run_family_graph, run_model_row, run_row, same_result)
-from _batch_encode_lanes import (ALIGNS, EL16, ELMAIN, ENC_LANE_RATE_ROW, ENC_LANE_ROWS, ENC_LANES, KERNEL, NO_ZERO_LANE_LOADS,
-                                 OPT_BATCH_ENCODE_LANES, WAVE_LOADS, PoolBatch64, rate_wave)
-from _kernel_rows import EMAIN, EROW, LMAIN, MODEL_ROW, OPT_BATCH_ENCODE_GROUPS, OPT_BATCH_ENCODE_PAIRS, OPT_BATCH_LANES
+from _batch_encode_lanes import ALIGNS, NO_ZERO_LANE_LOADS, WAVE_LOADS, rate_wave
+from _kernel_rows import (EL16, ELMAIN, EMAIN, ENC_LANE_RATE_ROW, ENC_LANE_ROWS, ENC_LANES, EROW, LMAIN, MODEL_ROW, OPT_BATCH_ENCODE_GROUPS,
+                          OPT_BATCH_ENCODE_LANES, OPT_BATCH_ENCODE_PAIRS, OPT_BATCH_LANES)
 from _oracle import FMT_R64
 
-WAVE = ENC_LANES.wave_kernel
+KERNEL, WAVE = ELMAIN["encode"], ENC_LANES.wave_kernel
 
 
 @pytest.fixture(scope="module")
@@ -153,7 +153,7 @@ def test_half_and_several(gpu, oracle, regime):
     """half: fewer wave-loads than the launch has resident waves (one block of sixteen per CU), prototype lengths log-uniform
     up to 64 Ki with the mandatory ones.  several: at least 1.25 x as many wave-loads as resident waves, so that waves come
     back for further claims and must reset states, ring position and flush count; prototype lengths log-uniform up to 1024.
-    Every stream is one of at most 4096 prototypes the oracle coded once (PoolBatch64: tests/_batch.py's PoolBatch at
+    Every stream is one of at most 4096 prototypes the oracle coded once (tests/_batch.py's PoolBatch at
     sym_align = 64); every stream of the batch is compared on the device with its prototype's.  The last wave-load is
     partial; with and without d_order; the result decodes back on the wave kernel and, on a third context with
     RANS_AMD_OPT_BATCH_LANES, on k_decode_batch_r64_lanes."""
@@ -169,7 +169,7 @@ def test_half_and_several(gpu, oracle, regime):
         protos = draw_log_uniform(POOL, 1024, 9)
         assert 4 * loads >= 5 * waves
     n = loads * 64 - 5
-    pb = PoolBatch64(R, ctx, torch, oracle, ELMAIN, protos, n, 31)
+    pb = PoolBatch(R, ctx, torch, oracle, ELMAIN, protos, n, 31, align=64)
     assert pb.counts.size == n and n % 64 != 0 and protos.size <= POOL
     cap = int(pb.slot_offs[-1])
     dec = R.Context(0)
