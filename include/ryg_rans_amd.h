@@ -217,6 +217,23 @@ enum rans_amd_option {
                                               streams of 512 symbols: 1.26 ms against 36.33 ms (28.8 x).
                                               Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
 };
+/* Options added behind the first eleven: the same call takes them (an option is an int). */
+enum rans_amd_option_more {
+    RANS_AMD_OPT_BATCH_ALIAS_PAIRS = 11    /* 1 = rans_amd_decode_batch decodes THIRTY-TWO streams per wavefront where the
+                                              batch is the reference's 2-way alias layout (main_alias.cpp: alias format, u8
+                                              symbols, n_ways 2, scale_bits 8..16, a power-of-two alphabet of at most 256
+                                              symbols, at least 32 streams): k_decode_batch_alias_pairs; every other shape
+                                              (u16 symbols, other interleaves, fewer streams) takes the wave-per-stream
+                                              kernels as before.  The stream is the byte format's, so the plan is
+                                              RANS_AMD_OPT_BATCH_PAIRS'; the tables are the alias decoder's divider and
+                                              half-bucket records, about 5 KiB for 256 symbols at ANY scale_bits (the byte
+                                              pairs' cum2sym is 64 KiB at 16 bits), so two blocks share a CU at 16 bits as
+                                              well.  Independent of options 5 to 10; the encoders are not affected.
+                                              Measured with d_order on 181 992 streams of up to 64 Ki symbols under a 16-bit
+                                              model: 4.34 ms against 38.49 ms on k_decode_batch<alias> with the same d_order
+                                              (8.87 x); the byte pairs at 16 bits on the same counts: 4.82 ms.
+                                              Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
+};
 int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value);
 
 /* ---- model building (SymbolStats, main.cpp:49-129) ---------------------- */
@@ -449,8 +466,13 @@ int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, u
  * longest of its 64 streams (pass d_order), and here sym_align = 64 is the fast layout (a stream whose symbols start on a
  * 64-byte line has its lines written, or fetched, by a quad of lanes; one on the 4-byte grid is stored, or fetched, in 16-byte
  * pieces by its own lane, any other byte by byte -- all decode, and code, right).  A stream of more than 2^30 bytes is
- * reported as failed by that decoder.  Every other interleave stays one stream per wavefront in both directions; ragged forms
- * of the other lane kernels (1-, 4- and 8-way interleaves, the other formats) are later work.  A stream of 0 symbols is the n_ways flushed initial
+ * reported as failed by that decoder.  A fourth shape packs thirty-two streams into a wavefront: the 2-way alias layout
+ * main_alias.cpp writes (alias format, u8 symbols, n_ways 2, scale_bits 8..16, a power-of-two alphabet of at most 256 symbols)
+ * in a batch of at least 32 streams, decoded by rans_amd_decode_batch on a context with RANS_AMD_OPT_BATCH_ALIAS_PAIRS = 1
+ * (the decoder's alone: alias batches are coded one stream per wavefront) -- the same bytes, the same advice as for the byte
+ * pairs: pass d_order, and sym_align = 4 is the fast layout.  Every other interleave stays one stream per wavefront in both
+ * directions; ragged forms of the other lane kernels (1-, 4- and 8-way interleaves) and of the alias pairs ENCODER are later
+ * work.  A stream of 0 symbols is the n_ways flushed initial
  * states.
  * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
  * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).

@@ -24,7 +24,8 @@
 // kernel); a ragged last chunk sends the input's last octet one round at a time; what a chunk size off 128 leaves goes four rounds, then one round
 // at a time.  The mirror image, the 8-way encoder: encode_groups.hip.  The ragged form for rans_amd_decode_batch -- eight
 // STREAMS per wave, each with its own symbol count -- is k_decode_batch_word_groups, behind the uniform kernel; the 2-way byte
-// layout's, thirty-two streams per wave, is k_decode_batch_byte_pairs behind k_decode_byte_pairs.
+// layout's, thirty-two streams per wave, is k_decode_batch_byte_pairs behind k_decode_byte_pairs, and the alias format's 2-way
+// layout's k_decode_batch_alias_pairs behind that.
 //
 // No MFMA: integer, table-driven, serial per state.
 
@@ -439,6 +440,9 @@ constexpr int kPairAux = kAuxStore; // nt sc1, as the other decoders' symbol sto
     "v_lshrrev_b32_e32 %[t2], %[sbv], %[x]\n\t"                                                    \
     "s_waitcnt lgkmcnt(0)\n\t"                                                                     \
     RANS_P_RECORD(SREG)                                                                            \
+    RANS_P_RENORM(FILL)
+// (the renormalisation on its own: the alias pairs' round below ends with the same text)
+#define RANS_P_RENORM(FILL)                                                                        \
     "v_cmp_gt_u32_e64 %[n1], %[l23], %[x]\n\t"                                                     \
     "v_cmp_gt_u32_e64 %[n2], %[l15], %[x]\n\t"                                                     \
     FILL                                                                                           \
@@ -481,6 +485,69 @@ __device__ __forceinline__ void decode_pairs_8rounds(uint32_t &x, uint32_t &cur,
 #undef RANS_P_FOUR
 #undef RANS_P_RECORD
 #undef RANS_P_ROUND
+
+// The same eight rounds for the ALIAS format's 2-way layout (main_alias.cpp:252-267 for the symbol, then rans_byte.h:307-318:
+// the stream IS the byte format's, so RANS_P_RENORM follows unchanged).  The tables are the FMT_ALIAS ones of
+// fill_decoder_tables: {freq | sym << 16, adjust} per half bucket at LDS address 0, divider u32[nsyms] at `div`.  A bucket's two
+// halves lie side by side -- 2 b the donor's, 2 b + 1 the bucket's own symbol's --, so ONE 16-byte read at 16 b brings both
+// records, and it does not wait for the divider: the two gathers of a round leave together where the byte format's second
+// gather waits for the first, and the divider only SELECTS.  The symbol step is 13 VALU + 2 LDS where the byte format's is
+// 6 + 2 -- 24 VALU + 4 LDS per round -- but one LDS round trip shorter in sequence, and a launch of ragged streams lasts as
+// long as the rounds of its longest stream one after the other:
+//   v_and                       xm = x & mask
+//   v_lshrrev                   bucket = xm >> (scale_bits - log2 nsyms)                     (< nsyms for ANY x)
+//   v_lshl_add, ds_read_b32     divider[bucket]
+//   v_lshlrev, ds_read_b128     both half records of the bucket, at 16 bucket                (< 16 nsyms for ANY x)
+//   v_lshrrev                   q = x >> scale_bits
+//   v_sub, v_ashrrev            xm - divider (both < 2^17) as a mask: all ones where the slot is the bucket's own symbol's
+//   v_bfi x2                    {freq | sym << 16, adjust} of the half the mask selects
+//   v_mul_u32_u24 (sdwa)        freq * q, freq the record's low word (freq < 2^16, q < 2^23 for a state in the working range)
+//   v_sub, v_add                x = freq * q + (xm - adjust)
+//   v_perm                      the symbol, byte 2 of the record, goes straight into its byte of the accumulator (in the
+//                               renormalisation's fill slot; bytes not written yet are zeroed by the selector)
+//   + the 11 VALU and 2 LDS of RANS_P_RENORM.
+// Both gathers stay inside the tables whatever x is -- the bucket comes out of log2 nsyms bits of x and nothing else goes into
+// either address -- and the symbol comes out of the record: no further lookup depends on what a table holds.  That is what lets
+// a parked or rejected pair free-run (k_decode_batch_alias_pairs).  DPP and exec as above: the s_nop in front of the DPP reads of
+// freshly written VGPRs is RANS_P_RENORM's, and exec is -1 again at the end of every round.
+#define RANS_A_ROUND(ACC, SEL)                                                                     \
+    "v_and_b32_e32 %[t0], %[maskv], %[x]\n\t"                                                      \
+    "v_lshrrev_b32_e32 %[t1], %[bsh], %[t0]\n\t"                                                   \
+    "v_lshl_add_u32 %[t3], %[t1], 2, %[div]\n\t"                                                   \
+    "ds_read_b32 %[t3], %[t3]\n\t"                                                                 \
+    "v_lshlrev_b32_e32 %[t1], 4, %[t1]\n\t"                                                        \
+    "ds_read_b128 v[56:59], %[t1]\n\t"                                                             \
+    "v_lshrrev_b32_e32 %[t2], %[sbv], %[x]\n\t"                                                    \
+    "s_waitcnt lgkmcnt(1)\n\t"                                                                     \
+    "v_sub_u32_e32 %[t3], %[t0], %[t3]\n\t"                                                        \
+    "v_ashrrev_i32_e32 %[t3], 31, %[t3]\n\t"                                                       \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                     \
+    "v_bfi_b32 v56, %[t3], v58, v56\n\t"                                                           \
+    "v_bfi_b32 v57, %[t3], v59, v57\n\t"                                                           \
+    "v_mul_u32_u24_sdwa %[x], v56, %[t2] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD\n\t" \
+    "v_sub_u32_e32 %[t0], %[t0], v57\n\t"                                                          \
+    "v_add_u32_e32 %[x], %[x], %[t0]\n\t"                                                          \
+    RANS_P_RENORM("v_perm_b32 " ACC ", v56, " ACC ", " SEL "\n\t")
+#define RANS_A_FOUR(ACC) RANS_A_ROUND(ACC, "%[s0]") RANS_A_ROUND(ACC, "%[s1]") RANS_A_ROUND(ACC, "%[s2]") RANS_A_ROUND(ACC, "%[s3]")
+// div: the dividers' LDS address (PairLane::rec); bsh = scale_bits - log2 nsyms (wave-uniform)
+__device__ __forceinline__ void decode_alias_pairs_8rounds(uint32_t &x, uint32_t &cur, uint32_t &acc_a, uint32_t &acc_b, uint32_t maskv,
+                                                           uint32_t sbv, uint32_t div, uint32_t bsh, uint32_t l23, uint32_t l15, uint32_t ring)
+{
+    uint32_t t0, t1, t2, t3;
+    uint64_t n1, n2, dm;
+    asm volatile("s_mov_b64 vcc, %[evens]\n\t" // the even lanes (the pair's state 0), for the whole sequence
+                 RANS_A_FOUR("%[pa]") RANS_A_FOUR("%[pb]")
+                 : [x] "+v"(x), [cur] "+v"(cur), [pa] "=&v"(acc_a), [pb] "=&v"(acc_b), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2),
+                   [t3] "=&v"(t3), [n1] "=&s"(n1), [n2] "=&s"(n2), [dm] "=&s"(dm)
+                 : [maskv] "v"(maskv), [sbv] "v"(sbv), [div] "v"(div), [bsh] "s"(bsh), [l23] "v"(l23), [l15] "v"(l15), [ring] "v"(ring),
+                   [evens] "s"(0x5555555555555555ull),
+                   // v_perm(record, accumulator): byte 2 of the record -> byte k, the bytes below kept, those above zero
+                   [s0] "s"(0x0c0c0c06u), [s1] "s"(0x0c0c0600u), [s2] "s"(0x0c060100u), [s3] "s"(0x06020100u)
+                 : "vcc", "memory", "v56", "v57", "v58", "v59");
+}
+#undef RANS_A_FOUR
+#undef RANS_A_ROUND
+#undef RANS_P_RENORM
 
 // sixteen rounds of a pair -> 32 bytes of its chunk, 16 per lane: d0..d3 are the four 4-round accumulators of this lane's
 // state.  Pair-interleave (the even lane keeps the first dword of every eight bytes, the odd lane the second), then the even
@@ -932,6 +999,158 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_byte_pairs(cons
     record_span(p, t_start, smem, wave * 64u + lane_now());
 }
 
+// ---------------------------------------------------------------------------
+// k_decode_batch_alias_pairs -- k_decode_batch_byte_pairs' plan for the ALIAS format's 2-way layout (main_alias.cpp;
+// rans_amd_decode_batch under RANS_AMD_OPT_BATCH_ALIAS_PAIRS).  An alias stream is a byte-format stream -- the same
+// renormalisation, the same pair interleave, 0, 1 or 2 bytes per state and round -- so everything but the symbol step is the
+// byte kernel's: lane 2 g + i holds state i of the stream at position 32 load + g of the hand-out order; 68-byte ring rows fed
+// through load16 and refills behind the pair's own checkpoint(); whole 128-byte lines in the common loop under full exec, pairs
+// that have run out of lines PARKED (no checkpoint, x and the cursor put back from copies behind every line, no store); tails
+// a round at a time with byte stores; an output off the 4-byte grid by rounds entirely; 64-bit output addresses in every lane;
+// index entries checked per pair (fetch_stream_entry) and counted once by the even lane; the stream accepted when both states
+// are back at L and the cursor stands at its end.  Here all of that comes through the shared pieces (PairRing, PairRowPinned,
+// PairLane, fetch_stream_entry, wave_max32, lane_number_now, pair_lines, quad_half), which the byte kernel, left as it compiles,
+// partly keeps written out.
+// The tables are the FMT_ALIAS ones fill_decoder_tables hands every alias decoder: {freq | sym << 16, adjust} per half bucket
+// (table 0, LDS address 0, 16 nsyms bytes) and divider u32[nsyms] (table 1) -- 5 KiB for 256 symbols at ANY scale_bits, where
+// the byte kernel's cum2sym is 64 KiB at 16 bits and leaves one block per CU: here two blocks share a CU at every scale_bits.
+// A parked pair, and one without a stream or with a rejected one, free-runs the rounds on whatever its state becomes, as in the
+// byte kernel, and that is safe for the same reason: a round reads only LDS and writes only the pair's own registers.  It reads
+// divider[bucket] with bucket = (x & mask) >> (scale_bits - log2 nsyms) < nsyms, inside table 1 whatever x is; the 16 bytes at
+// 16 bucket, the records of halves 2 bucket and 2 bucket + 1 < 2 nsyms, inside table 0 whatever x is (the divider selects
+// between them and goes into no address); the symbol comes out of the selected record, so no further address depends on a
+// table's content; and the ring at ring + (position & 63) and one byte further, inside the pair's
+// own 68-byte row whatever the cursor is.  No global memory: refills are checkpoint()'s, and that is gated.
+// ---------------------------------------------------------------------------
+__global__ void __launch_bounds__(kGrpThreads, 8) k_decode_batch_alias_pairs(const DecParams p)
+{
+    using Tr = FmtTraits<FMT_ALIAS>;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const unsigned long long t_start = p.span ? wall_clock64() : 0ull;
+    const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u; // {freq | sym << 16, adjust}[2 nsyms]
+    const uint32_t t1_bytes = (p.table1_bytes + 15u) & ~15u; // divider u32[nsyms]
+    stage_table(smem, p.table0, t0_bytes);
+    stage_table(smem + t0_bytes, p.table1, t1_bytes);
+    __syncthreads();
+    if (!lds_starts_at_zero(smem)) { // cannot happen without static LDS; never decode on a wrong assumption
+        if (threadIdx.x == 0)
+            atomicAdd(p.err_count, 1ull << 32);
+        return;
+    }
+    reset_for_next_launch(p);
+
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    const uint32_t ring_c = t0_bytes + t1_bytes + wave * kPairWaveLds + (lane >> 1) * kPairRow; // raw LDS byte address of the pair's ring
+    uint32_t ring_i = ring_c + 16u * (lane & 1u); // where this lane's 16 bytes of a block go
+    pin_vgpr(ring_i);
+    const PairLane L(ring_c, p.scale_bits, t0_bytes, lane & 1u); // (L.rec: the dividers' address)
+    const uint32_t bsh = uniform(p.scale_bits - p.log2nsyms);     // slot -> bucket (the launcher: log2nsyms <= 8 <= scale_bits)
+    const PairRowPinned row{L.ring, ring_i};
+
+    const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
+    const uint64_t glo = cbase & ~uint64_t(15), glimit = (cbase + p.container_bytes + 15u) & ~uint64_t(15);
+    const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 31u) >> 5); // wave-loads, one per claim (the last one may hold fewer than 32
+                                                                         // streams); stream indices are 32-bit
+    uint32_t nbad = 0;
+    WorkClaims work;
+    work.init(p.work_counter, wave, waves_per_block);
+    for (;;) {
+        const uint64_t load = work.take(lane);
+        if ((load >> 32) != 0 || (uint32_t)load >= loads) // (scalar compares)
+            break;
+        // ---- this pair's stream: its index entries, all of them the caller's data
+        const uint32_t ln = lane_number_now();
+        const uint32_t g = ln >> 1, i = ln & 1u;
+        bool exists, valid;
+        uint64_t off, first;
+        uint32_t len, count;
+        fetch_stream_entry<2u * 4u, false>(p, load * 32u + g, exists, valid, off, first, len, count);
+        if (exists && !valid && i == 0)
+            nbad++;
+        const uint64_t src = cbase + (valid ? off : 0u);
+        uint32_t x = Tr::kL;
+        if (valid) // RansDecInit order: state 0 first (main_alias.cpp: as main.cpp:261-262)
+            x = reinterpret_cast<const uint32_t RANS_GLOBAL *>(src)[i];
+        PairRing R; // (a pair without a valid stream fetches nothing, now or later)
+        const uint32_t start = R.open(src, i, row, valid, glo, glimit);
+        uint32_t &cur = R.cur;
+        const uint32_t end = len + (start - 2u * 4u); // the cursor at the end of the stream
+
+        // ---- the pair's own counts: whole lines through the common loop, the rest a round at a time
+        const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + first; // (valid: [dst, dst + count) lies inside the output)
+        const uint32_t blocks = (valid && (dst & 3u) == 0) ? count >> 7 : 0u;
+        const uint32_t tail = valid ? count - (blocks << 7) : 0u;
+        const uint32_t max_blocks = wave_max32(blocks), max_tail = wave_max32(tail);
+        // the quad's two streams A = g & ~1 and B = A + 1, as lane t = lane & 3 of the quad addresses them: 16 t bytes in
+        auto from = [&](uint32_t v, int addr) -> uint32_t { return (uint32_t)__builtin_amdgcn_ds_bpermute(addr, (int)v); };
+        const int lane_a = (int)(4u * (ln & ~3u)), lane_b = (int)(4u * (ln | 2u));
+        const uint32_t blocks_a = from(blocks, lane_a), blocks_b = from(blocks, lane_b);
+        uint64_t line_a = ((uint64_t)from((uint32_t)(dst >> 32), lane_a) << 32 | from((uint32_t)dst, lane_a)) + 16u * (ln & 3u);
+        uint64_t line_b = ((uint64_t)from((uint32_t)(dst >> 32), lane_b) << 32 | from((uint32_t)dst, lane_b)) + 16u * (ln & 3u);
+        const bool pair_b = (ln & 2u) != 0; // this lane's own stream is the quad's B
+        bool run = false;
+        auto sixteen = [&]() -> u32x4 { // sixteen rounds -> this lane's 16 of the pair's 32 bytes
+            uint32_t a0, a1, a2, a3;
+            R.checkpoint(row, run);
+            decode_alias_pairs_8rounds(x, cur, a0, a1, L.maskv, L.sbv, L.rec, bsh, L.l23, L.l15, L.ring);
+            R.checkpoint(row, run);
+            decode_alias_pairs_8rounds(x, cur, a2, a3, L.maskv, L.sbv, L.rec, bsh, L.l23, L.l15, L.ring);
+            return pair_lines(a0, a1, a2, a3, L.sel_p);
+        };
+        for (uint32_t q = 0; q < max_blocks; ++q) {
+            run = pair_b ? q < blocks_b : q < blocks_a; // q < this pair's blocks
+            const uint32_t x_keep = x, cur_keep = cur;
+            const u32x4 v0 = sixteen();
+            const u32x4 v1 = sixteen();
+            const u32x4 v2 = sixteen();
+            const u32x4 v3 = sixteen();
+            // the gathers under full exec (their DPP moves read all four lanes), the stores under q < blocks of the stream they
+            // belong to; plain stores: a stream starts anywhere on the 4-byte grid
+            const u32x4 ha0 = quad_half<0>(v0, v1), ha1 = quad_half<0>(v2, v3);
+            if (q < blocks_a) {
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_a) = ha0;
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_a + 64u) = ha1;
+            }
+            const u32x4 hb0 = quad_half<1>(v0, v1), hb1 = quad_half<1>(v2, v3);
+            if (q < blocks_b) {
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_b) = hb0;
+                *reinterpret_cast<u32x4_a4 RANS_GLOBAL *>(line_b + 64u) = hb1;
+            }
+            line_a += 128u; // (past a stream's last line the address is not used any more)
+            line_b += 128u;
+            x = run ? x : x_keep;
+            cur = run ? cur : cur_keep;
+        }
+        // ---- count - 128 blocks symbols (all of them where the output is not 4-byte aligned): one round at a time, compiler-scheduled
+        // (this pair's address from the quad's: the lines have moved on by max_blocks, the pair's tail follows its own blocks)
+        const uint32_t lt = lane_number_now();
+        const uint32_t gt = lt >> 1, it = lt & 1u;
+        const bool tail_b = (lt & 2u) != 0;
+        const int lane_o = (int)(4u * (lt ^ 1u)); // the pair's other lane
+        const uint64_t tail_dst = (tail_b ? line_b : line_a) - 16u * (lt & 3u) - ((uint64_t)(max_blocks - (tail_b ? blocks_b : blocks_a)) << 7);
+        const uint32_t tail_rounds = (uint32_t)(((uint64_t)max_tail + 1u) >> 1);
+        for (uint32_t rr = 0; rr < tail_rounds; ++rr) {
+            if ((rr & 7u) == 0)
+                R.checkpoint(row, valid);
+            const uint32_t s0 = rr << 1; // < max_tail
+            const bool active = s0 < tail && it < tail - s0;
+            const uint32_t sy = decode_pair_round<true, true>(x, cur, active, it, L.maskv, L.sbv, L.rec, L.l23, L.l15, L.ring, lane_o, bsh);
+            if (active)
+                *reinterpret_cast<uint8_t RANS_GLOBAL *>(tail_dst + s0 + it) = (uint8_t)sy;
+        }
+        // integrity: both states back at L, the cursor exactly at the end of the stream
+        const bool bad = valid && (x != Tr::kL || cur != end);
+        const uint64_t bm = __builtin_amdgcn_ballot_w64(bad);
+        if (it == 0 && ((bm >> (2u * gt)) & 3u) != 0)
+            nbad++;
+    }
+    if (nbad)
+        atomicAdd(p.err_count, (unsigned long long)nbad);
+    record_span(p, t_start, smem, wave * 64u + lane_number_now());
+}
+
 } // namespace
 
 // (a ragged last chunk included: its octet goes one round at a time and is handed out first)
@@ -998,6 +1217,23 @@ hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipSt
     if (name)
         *name = KernelId::decode_batch_byte_pairs;
     return launch_group_kernel<k_decode_batch_byte_pairs>((p.nchunks + 31u) / 32u, pair_lds(p), kGrpLdsCap, num_cus, stream, p); // one wave-load per wave
+}
+
+// The alias format's 2-way layout over u8 symbols with the FMT_ALIAS tables (the caller has checked the format): the alphabet
+// a power of two of at most 256 symbols -- what the alias builder accepts, with 16 nsyms bytes of half-bucket records and
+// 4 nsyms of dividers, so that the table sizes say it --, from 32 streams on; any symbol count, any output address.
+bool decode_batch_alias_pairs_applicable(const DecParams &p)
+{
+    return p.n_ways == 2 && p.sym_bytes == 1 && p.scale_bits >= 8 && p.scale_bits <= 16 && p.log2nsyms <= 8 &&
+           p.table0_bytes == (16u << p.log2nsyms) && p.table1_bytes == (4u << p.log2nsyms) && p.nchunks >= 32 && p.sym_offsets && p.sym_counts &&
+           !p.trace && pair_lds(p) <= kGrpLdsCap;
+}
+
+hipError_t launch_decode_batch_alias_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
+{
+    if (name)
+        *name = KernelId::decode_batch_alias_pairs;
+    return launch_group_kernel<k_decode_batch_alias_pairs>((p.nchunks + 31u) / 32u, pair_lds(p), kGrpLdsCap, num_cus, stream, p); // one wave-load per wave
 }
 
 } // namespace rans_amd

@@ -1,5 +1,5 @@
-// groups_common.hpp -- what the seven group kernels share (internal): decode_groups.hip's k_decode_word_groups,
-// k_decode_batch_word_groups, k_decode_byte_pairs, k_decode_batch_byte_pairs and encode_groups.hip's k_encode_word_groups,
+// groups_common.hpp -- what the eight group kernels share (internal): decode_groups.hip's k_decode_word_groups,
+// k_decode_batch_word_groups, k_decode_byte_pairs, k_decode_batch_byte_pairs, k_decode_batch_alias_pairs and encode_groups.hip's k_encode_word_groups,
 // k_encode_batch_word_groups, k_encode_batch_byte_pairs.  Every piece is written once here, forceinline, and where the kernels differ the difference is
 // an argument or a template parameter that is constant at the call site (profiles/groups_common_isa.md: what each kernel
 // compiles to with them).  The hand-scheduled sequences stay with their kernels.  Helpers that took the place of a lambda
@@ -327,18 +327,29 @@ struct PairRing : RingFeed<kPairBlock> {
 // bytes first).  Lanes without a symbol sit the round out; returns the symbol.  The other lane's byte count comes through
 // __shfl_xor, or (BPERMUTE) through ds_bpermute with lane_o, the byte address of the lane to read: __shfl keeps a lane
 // number of its own in a register.
+// ALIAS: the alias format's symbol step instead (main_alias.cpp:252-267, dec_step's FMT_ALIAS form): the half-bucket records
+// {freq | sym << 16, adjust} at LDS address 0, `rec` the dividers' address, bsh = scale_bits - log2 nsyms.
 // (by reference: see head)
-template <bool BPERMUTE>
+template <bool BPERMUTE, bool ALIAS = false>
 __device__ __forceinline__ uint32_t decode_pair_round(uint32_t &x, uint32_t &cur, const bool &active, const uint32_t &odd, const uint32_t &maskv,
                                                       const uint32_t &sbv, const uint32_t &rec, const uint32_t &l23, const uint32_t &l15,
-                                                      const uint32_t &ring, const int &lane_o)
+                                                      const uint32_t &ring, const int &lane_o, const uint32_t &bsh = 0u)
 {
     uint32_t sy = 0, n = 0;
     if (active) {
         const uint32_t cf = x & maskv;
-        sy = *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)cf);
-        const u32x2 fr = *reinterpret_cast<RANS_LDS const u32x2 *>((uintptr_t)(rec + 8u * sy));
-        x = (fr.x & 0xffffffu) * ((x >> sbv) & 0xffffffu) + cf - fr.y;
+        if constexpr (ALIAS) {
+            const uint32_t bucket = cf >> bsh;
+            const uint32_t div = *reinterpret_cast<RANS_LDS const uint32_t *>((uintptr_t)(rec + 4u * bucket));
+            const uint32_t half = 2u * bucket + ((cf - div) >> 31); // + 1: the bucket's own symbol (cf < divider; both < 2^17)
+            const u32x2 e = *reinterpret_cast<RANS_LDS const u32x2 *>((uintptr_t)(8u * half));
+            sy = e.x >> 16;
+            x = (e.x & 0xffffu) * ((x >> sbv) & 0xffffffu) + cf - e.y;
+        } else {
+            sy = *reinterpret_cast<RANS_LDS const uint8_t *>((uintptr_t)cf);
+            const u32x2 fr = *reinterpret_cast<RANS_LDS const u32x2 *>((uintptr_t)(rec + 8u * sy));
+            x = (fr.x & 0xffffffu) * ((x >> sbv) & 0xffffffu) + cf - fr.y;
+        }
         n = (uint32_t)(x < l23) + (uint32_t)(x < l15);
     }
     const uint32_t n_other = BPERMUTE ? (uint32_t)__builtin_amdgcn_ds_bpermute(lane_o, (int)n) : (uint32_t)__shfl_xor((int)n, 1, 64);

@@ -13,7 +13,14 @@
 //   batch_byte_pairs_encode   ... encoder (RANS_AMD_OPT_BATCH_ENCODE_PAIRS)
 //   batch_r64_lanes_decode    ragged 2-way rans64 streams, 64 per wave, decoder (RANS_AMD_OPT_BATCH_LANES)
 //   batch_r64_lanes_encode    ... encoder (RANS_AMD_OPT_BATCH_ENCODE_LANES)
-// Nine families in one list: a new kernel is one more row at the list's end (an id is its row's place, counted from 1, and the
+// A second list follows the first one: RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS, the family
+//   batch_alias_pairs_decode  ragged 2-way alias streams, 32 per wave, decoder (RANS_AMD_OPT_BATCH_ALIAS_PAIRS)
+// Its ids follow the first list's in KernelId, its rows are kAliasPairKernelEntries; kKernelEntries (what
+// tests/kernel_names_driver.cpp prints and tests/_kernel_rows.py reads) is the first list alone, and
+// tests/kernel_names_alias_pairs_driver.cpp with tests/_batch_alias_pairs.py hold the second list to its rows.
+// kernel_entry(), kernel_name() and kernel_family() resolve ids from both.  (Folding the two into one list is a later refactor:
+// the row module has to know the family first, and the first list's printed lines and count are pinned by tests.)
+// Nine families in the first list: a new kernel is one more row at the list's end (an id is its row's place, counted from 1, and the
 // ids that exist stay where they are); tests/kernel_names_driver.cpp prints every row and tests/_kernel_rows.py reads them.
 #pragma once
 
@@ -74,6 +81,9 @@ namespace rans_amd {
     X(decode_batch_r64_lanes, "k_decode_batch_r64_lanes", batch_r64_lanes_decode)                 \
     X(encode_batch_r64_lanes, "k_encode_batch_r64_lanes", batch_r64_lanes_encode)
 
+#define RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS(X)                                                      \
+    X(decode_batch_alias_pairs, "k_decode_batch_alias_pairs", batch_alias_pairs_decode)
+
 enum class KernelFamily {
     uniform,
     batch,
@@ -84,12 +94,14 @@ enum class KernelFamily {
     batch_byte_pairs_encode,
     batch_r64_lanes_decode,
     batch_r64_lanes_encode,
+    batch_alias_pairs_decode,
 };
 
 enum class KernelId {
     none, // no launch yet: the name is ""
 #define X(id, name, family) id,
     RANS_AMD_KERNEL_NAMES(X)
+    RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS(X) // (behind the first list: an id of this one is kKernelEntryCount + 1 + its row)
 #undef X
 };
 
@@ -108,8 +120,22 @@ constexpr KernelEntry kKernelEntries[] = {
 };
 constexpr int kKernelEntryCount = (int)(sizeof(kKernelEntries) / sizeof(kKernelEntries[0]));
 
-constexpr const KernelEntry &kernel_entry(KernelId id) { return kKernelEntries[(int)id - 1]; } // (not for KernelId::none)
+// the second list's entries, in its order
+constexpr KernelEntry kAliasPairKernelEntries[] = {
+#define X(id, name, family) {KernelId::id, name, KernelFamily::family, #family},
+    RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS(X)
+#undef X
+};
+constexpr int kAliasPairKernelEntryCount = (int)(sizeof(kAliasPairKernelEntries) / sizeof(kAliasPairKernelEntries[0]));
+
+constexpr const KernelEntry &kernel_entry(KernelId id) // (not for KernelId::none)
+{
+    return (int)id <= kKernelEntryCount ? kKernelEntries[(int)id - 1] : kAliasPairKernelEntries[(int)id - 1 - kKernelEntryCount];
+}
 constexpr const char *kernel_name(KernelId id) { return id == KernelId::none ? "" : kernel_entry(id).name; }
 constexpr KernelFamily kernel_family(KernelId id) { return kernel_entry(id).family; } // (not for KernelId::none)
+static_assert(kernel_entry(KernelId::encode_batch_r64_lanes).id == KernelId::encode_batch_r64_lanes &&
+                  kernel_entry(KernelId::decode_batch_alias_pairs).id == KernelId::decode_batch_alias_pairs,
+              "ids of both lists resolve to their own rows");
 
 } // namespace rans_amd

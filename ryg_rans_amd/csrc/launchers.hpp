@@ -89,6 +89,11 @@ hipError_t launch_decode_byte_pairs(const DecParams &p, int num_cus, hipStream_t
 // output address, from 32 streams on, the tables and the wave rings inside the CU's 160 KiB of LDS
 bool decode_batch_byte_pairs_applicable(const DecParams &p);
 hipError_t launch_decode_batch_byte_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+// ... and the same plan for the alias format's 2-way layout (main_alias.cpp; rans_amd_decode_batch, kBatchFamilies): 32 STREAMS
+// per wave over the FMT_ALIAS tables (divider + half-bucket records, about 5 KiB for 256 symbols at any scale_bits), u8
+// symbols, a power-of-two alphabet of at most 256 symbols, scale_bits 8..16, from 32 streams on
+bool decode_batch_alias_pairs_applicable(const DecParams &p);
+hipError_t launch_decode_batch_alias_pairs(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // the 8-way word layout's encoder, eight chunks per wave (encode_groups.hip): chunks of a multiple of 4 u8 symbols, the
 // three-kernel placement, the slot layout or sized slots (no fused placement)
@@ -149,6 +154,7 @@ constexpr BatchFamily kBatchFamilies[] = {
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_GROUPS, kVarBatchGroups, RANS_AMD_FMT_WORD, decode_batch_word_groups, "eight 8-way word streams per wave"),
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_PAIRS, kVarBatchPairs, RANS_AMD_FMT_BYTE, decode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_LANES, kVarBatchLanes, RANS_AMD_FMT_R64, decode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
+    RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_ALIAS_PAIRS, kVarBatchAliasPairs, RANS_AMD_FMT_ALIAS, decode_batch_alias_pairs, "thirty-two 2-way alias streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_GROUPS, kVarBatchEncGroups, RANS_AMD_FMT_WORD, encode_batch_word_groups, "eight 8-way word streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_PAIRS, kVarBatchEncPairs, RANS_AMD_FMT_BYTE, encode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_LANES, kVarBatchEncLanes, RANS_AMD_FMT_R64, encode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
