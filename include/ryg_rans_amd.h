@@ -235,6 +235,26 @@ enum rans_amd_option_more {
                                               Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
 };
 int rans_amd_ctx_set_option(rans_amd_ctx *ctx, int option, int value);
+/* Options added behind those two enums (which stay as they are, in front of the call's declaration): the same call takes them. */
+enum rans_amd_option_third {
+    RANS_AMD_OPT_BATCH_ENCODE_ALIAS_PAIRS = 12 /* 1 = rans_amd_encode_batch[_ordered] codes THIRTY-TWO streams per wavefront
+                                              where the batch is that same shape (alias format, u8 symbols, n_ways 2,
+                                              scale_bits 8..16, a power-of-two alphabet of at most 256 symbols, at least 32
+                                              streams, a 16-byte aligned d_out, a model that carries the encoder's LDS tables --
+                                              every such model does): k_encode_batch_alias_pairs, the same bytes, offsets and
+                                              lengths; every other shape takes the wave-per-stream kernels as before.  The
+                                              stream is the byte format's, so the plan is RANS_AMD_OPT_BATCH_ENCODE_PAIRS';
+                                              the put gathers alias_remap from LDS (2 << scale_bits bytes: 128 KiB at 16 bits,
+                                              where a block is 13 wavefronts, one per CU; two blocks of 16 up to 14 bits).
+                                              Independent of options 5 to 11 (RANS_AMD_OPT_BATCH_ALIAS_PAIRS is the decoder's
+                                              alone); rans_amd_encode_batch_adaptive and every decoder are not affected.
+                                              Measured with d_order on 181 992 streams of up to 64 Ki symbols under a 16-bit
+                                              model: 3.86 ms against 58.23 ms on k_encode_batch<alias, LDS remap> with the same
+                                              d_order (15.09 x; its slowest pass beats the wave kernel's fastest); without an
+                                              order 8.92 against 67.42 ms; at 12 bits 3.86 against 58.43 ms; the byte pair
+                                              encoder at 16 bits on the same counts: 3.58 ms.
+                                              Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
+};
 
 /* ---- model building (SymbolStats, main.cpp:49-129) ---------------------- */
 
@@ -469,10 +489,10 @@ int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, u
  * reported as failed by that decoder.  A fourth shape packs thirty-two streams into a wavefront: the 2-way alias layout
  * main_alias.cpp writes (alias format, u8 symbols, n_ways 2, scale_bits 8..16, a power-of-two alphabet of at most 256 symbols)
  * in a batch of at least 32 streams, decoded by rans_amd_decode_batch on a context with RANS_AMD_OPT_BATCH_ALIAS_PAIRS = 1
- * (the decoder's alone: alias batches are coded one stream per wavefront) -- the same bytes, the same advice as for the byte
- * pairs: pass d_order, and sym_align = 4 is the fast layout.  Every other interleave stays one stream per wavefront in both
- * directions; ragged forms of the other lane kernels (1-, 4- and 8-way interleaves) and of the alias pairs ENCODER are later
- * work.  A stream of 0 symbols is the n_ways flushed initial
+ * and coded by rans_amd_encode_batch[_ordered] on a context with RANS_AMD_OPT_BATCH_ENCODE_ALIAS_PAIRS = 1 (independent again,
+ * the same bytes), the same advice as for the byte pairs: pass d_order, and sym_align = 4 is the fast layout.  Every other
+ * interleave stays one stream per wavefront in both directions; ragged forms of the other lane kernels (1-, 4- and 8-way
+ * interleaves) are later work.  A stream of 0 symbols is the n_ways flushed initial
  * states.
  * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
  * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).

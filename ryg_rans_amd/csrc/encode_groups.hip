@@ -547,6 +547,117 @@ __device__ __forceinline__ void encode_pairs_8rounds(uint32_t &x, uint32_t &c, u
 #undef RANS_PE_FOUR
 #undef RANS_PE_ROUND
 
+// The alias format's round (k_encode_batch_alias_pairs, behind the byte kernel; RansEncPutAlias, main_alias.cpp:241-250: the byte
+// format's renormalisation, then x = ((x / freq) << scale_bits) + alias_remap[(x % freq) + start]).  The renormalisation, the DPP
+// exchange of the counts and the two ds_write_b8 are RANS_PE_ROUND's, instruction for instruction; the put is new.  Records
+// {rcp, (2^24 - freq) | rshift << 24, start | inc << 16, x_max} at LDS address sym << 4, remap16 behind them (the ds_read_u16's
+// offset field is its base), v56..v59 the record:
+//   v_mul_hi, v_lshrrev (SDWA)  q0 = mulhi(x, rcp) >> rshift: Alverson's reciprocal, exact for x < 2^31 -- but for freq == 1,
+//   v_add (SDWA word 1)         where mulhi(x, 2^32 - 1) = x - 1: that record's inc is 1.  q = q0 + inc
+//   v_mad_u32_u24               t2 = q * (2^24 - freq) + x: its low 24 bits are x - q * freq = x % freq (q < 2^23, freq < 2^16)
+//   v_add_lshl, v_and           byte offset of the gather = 2 (t2 + start) under mask2 = (2^scale_bits - 1) << 1: whatever the
+//                               lane holds -- a dead pair, no stream, no record -- the read stays inside remap16 (inc << 16 is
+//                               shifted to bit 17, the high bits of t2 above that: both outside the mask)
+//   ds_read_u16                 the one new LDS round trip; the NEXT round's record is asked for behind it (its address comes
+//                               from the symbol byte alone, v56..v59 are free from here), so the wait for the gather --
+//   s_waitcnt lgkmcnt(1)        -- leaves that read in flight, and the next round's lgkmcnt(0) finds it (nearly) there
+//   v_lshl_add                  x = (q << scale_bits) + remap16[...]
+// 23 VALU (+ 1 with TRACK) + 4 LDS per round (profiles/batch_encode_alias_pairs_isa.md).  A byte value without a record: {0, ~0, 0, ~0} -- it never emits (the count is
+// still the lane's own two compares: at most 2 bytes per lane and round, whatever x is), q = 0, and bit 31 of its second word is
+// TRACK's.
+#define RANS_AE_LOAD(ACC, SEL)                                                                                         \
+    "v_lshlrev_b32_sdwa %[t3], %[k4], " ACC " dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:" SEL "\n\t"   \
+    "ds_read_b128 v[56:59], %[t3]\n\t"
+#define RANS_AE_ROUND(NEXT, WAIT, TRACKSTR)                                                                            \
+    "v_lshrrev_b32_e32 %[t1], 8, %[x]\n\t"                                                                             \
+    "s_waitcnt lgkmcnt(0)\n\t"                                                                                         \
+    "v_cmp_ge_u32_e64 %[n1], %[x], v59\n\t"                                                                            \
+    "v_cmp_ge_u32_e64 %[n2], %[t1], v59\n\t"                                                                           \
+    TRACKSTR                                                                                                           \
+    "v_addc_co_u32_e64 %[t2], %[dm], %[c], 0, %[n1]\n\t"                                                               \
+    "v_addc_co_u32_e64 %[t2], %[dm], %[t2], 0, %[n2]\n\t"                                                              \
+    "s_nop 1\n\t"                                                                                                      \
+    "v_cndmask_b32_dpp %[t3], %[t2], %[c], vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"                      \
+    "v_add_u32_dpp %[t0], %[t2], %[t2] quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"                              \
+    "v_sub_u32_e32 %[c], %[t0], %[c]\n\t"                                                                              \
+    "v_and_b32_e32 %[t0], 63, %[t3]\n\t"                                                                               \
+    "v_sub_u32_e32 %[t0], %[top], %[t0]\n\t"                                                                           \
+    "v_add_u32_e32 %[t3], 1, %[t3]\n\t"                                                                                \
+    "v_and_b32_e32 %[t3], 63, %[t3]\n\t"                                                                               \
+    "v_sub_u32_e32 %[t3], %[top], %[t3]\n\t"                                                                           \
+    "s_mov_b64 exec, %[n1]\n\t"                                                                                        \
+    "ds_write_b8 %[t0], %[x]\n\t"                                                                                      \
+    "v_mov_b32_e32 %[x], %[t1]\n\t"                                                                                    \
+    "s_mov_b64 exec, %[n2]\n\t"                                                                                        \
+    "ds_write_b8 %[t3], %[t1]\n\t"                                                                                     \
+    "v_lshrrev_b32_e32 %[x], 8, %[x]\n\t"                                                                              \
+    "s_mov_b64 exec, -1\n\t"                                                                                           \
+    "v_mul_hi_u32 %[t0], %[x], v56\n\t"                                                                                \
+    "v_lshrrev_b32_sdwa %[t0], v57, %[t0] dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_3 src1_sel:DWORD\n\t"        \
+    "v_add_u32_sdwa %[t0], %[t0], v58 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1\n\t"            \
+    "v_mad_u32_u24 %[t2], %[t0], v57, %[x]\n\t"                                                                        \
+    "v_add_lshl_u32 %[t2], %[t2], v58, 1\n\t"                                                                          \
+    "v_and_b32_e32 %[t2], %[mask2], %[t2]\n\t"                                                                         \
+    "ds_read_u16 %[t2], %[t2] offset:4096\n\t"                                                                         \
+    NEXT                                                                                                               \
+    WAIT                                                                                                               \
+    "v_lshl_add_u32 %[x], %[t0], %[sbv], %[t2]\n\t"
+#define RANS_AE_NEXT(ACC, SEL, TRACKSTR) RANS_AE_ROUND(RANS_AE_LOAD(ACC, SEL), "s_waitcnt lgkmcnt(1)\n\t", TRACKSTR)
+#define RANS_AE_EIGHT(TRACKSTR)                                                                                        \
+    asm volatile("s_mov_b64 vcc, %[odds]\n\t" RANS_AE_LOAD("%[hi]", "BYTE_3")                                            \
+                 RANS_AE_NEXT("%[hi]", "BYTE_2", TRACKSTR) RANS_AE_NEXT("%[hi]", "BYTE_1", TRACKSTR)                     \
+                 RANS_AE_NEXT("%[hi]", "BYTE_0", TRACKSTR) RANS_AE_NEXT("%[lo]", "BYTE_3", TRACKSTR)                     \
+                 RANS_AE_NEXT("%[lo]", "BYTE_2", TRACKSTR) RANS_AE_NEXT("%[lo]", "BYTE_1", TRACKSTR)                     \
+                 RANS_AE_NEXT("%[lo]", "BYTE_0", TRACKSTR) RANS_AE_ROUND("", "s_waitcnt lgkmcnt(0)\n\t", TRACKSTR)       \
+                 : [x] "+v"(x), [c] "+v"(c), [worst] "+v"(worst), [t0] "=&v"(t0), [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), \
+                   [n1] "=&s"(n1), [n2] "=&s"(n2), [dm] "=&s"(dm)                                                       \
+                 : [hi] "v"(hi), [lo] "v"(lo), [k4] "v"(k4), [top] "v"(top), [sbv] "v"(sbv), [mask2] "v"(mask2),       \
+                   [odds] "s"(0xaaaaaaaaaaaaaaaaull)                                                                   \
+                 : "vcc", "memory", "v56", "v57", "v58", "v59")
+// eight rounds of an alias pair, the last first (encode_pairs_8rounds' arguments + the two constants of the put)
+template <bool TRACK>
+__device__ __forceinline__ void encode_alias_pairs_8rounds(uint32_t &x, uint32_t &c, uint32_t &worst, uint32_t hi, uint32_t lo, uint32_t k4, uint32_t top,
+                                                           uint32_t sbv, uint32_t mask2)
+{
+    uint32_t t0, t1, t2, t3;
+    uint64_t n1, n2, dm;
+    if constexpr (TRACK)
+        RANS_AE_EIGHT("v_or_b32_e32 %[worst], %[worst], v57\n\t");
+    else
+        RANS_AE_EIGHT("s_nop 0\n\t");
+}
+#undef RANS_AE_EIGHT
+#undef RANS_AE_NEXT
+#undef RANS_AE_ROUND
+#undef RANS_AE_LOAD
+
+// One compiler-scheduled round of an alias pair: groups_common.hpp's encode_pair_round with the alias put (the same
+// instructions as RANS_AE_ROUND's, in C++).  Lanes without a symbol sit the round out; an active lane whose byte value has no
+// record emits nothing, tracks bit 31 and gathers under the mask like every other.
+__device__ __forceinline__ void encode_alias_pair_round(uint32_t &x, uint32_t &c, uint32_t &worst, uint32_t sym, bool active, uint32_t odd, uint32_t top,
+                                                        int lane_o, uint32_t sbv, uint32_t mask2)
+{
+    const u32x4 rec = *reinterpret_cast<RANS_LDS const u32x4 *>((uintptr_t)(sym << 4));
+    uint32_t n = 0;
+    if (active)
+        n = (uint32_t)(x >= rec.w) + (uint32_t)((x >> 8) >= rec.w);
+    const uint32_t n_other = (uint32_t)__builtin_amdgcn_ds_bpermute(lane_o, (int)n);
+    const uint32_t at = c + (odd ? 0u : n_other);
+    c += n + n_other;
+    if (n >= 1u)
+        *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(top - (at & 63u))) = (uint8_t)x;
+    if (n >= 2u)
+        *reinterpret_cast<RANS_LDS uint8_t *>((uintptr_t)(top - ((at + 1u) & 63u))) = (uint8_t)(x >> 8);
+    x >>= 8u * n;
+    if (active) {
+        const uint32_t q = (__umulhi(x, rec.x) >> ((rec.y >> 24) & 31u)) + (rec.z >> 16);
+        const uint32_t t = (q & 0xffffffu) * (rec.y & 0xffffffu) + x; // low 24 bits: x - q * freq
+        const uint32_t at2 = ((t + rec.z) << 1) & mask2;              // inside remap16 whatever the lane holds
+        x = (q << sbv) + *reinterpret_cast<RANS_LDS const uint16_t *>((uintptr_t)(kEncPairTable + at2));
+        worst |= rec.y;
+    }
+}
+
 // The inverse of decode_groups.hip's pair_lines: 32 bytes of a pair's stream of symbols, bytes [0, 16) in the even lane and
 // [16, 32) in the odd one, -> d0..d3, the four dwords of this lane's state (byte J of d_m: round 4 m + J of the piece's
 // sixteen).  The lanes first swap dwords so that the even lane holds dwords 0, 2, 4, 6 of the piece and the odd lane 1, 3, 5,
@@ -580,24 +691,51 @@ __device__ __forceinline__ void piece_to_states(const u32x4 &v, uint32_t &d0, ui
 // The sixteen rounds of a piece that piece_to_states has taken apart, last round first.  flush(have_bytes) is the kernel's
 // flush_block: the block that the eight rounds before may have finished leaves in front of the next eight.  (A dead pair's
 // check may be true -- its cursor moves -- and its flush_block then only counts the block.)
-template <bool TRACK, class FLUSH>
+// ALIAS: the alias format's rounds (sbv, mask2: the constants of their put; the byte kernel passes zeros that nobody reads).
+template <bool ALIAS, bool TRACK, class FLUSH>
 __device__ __forceinline__ void encode_piece(uint32_t d0, uint32_t d1, uint32_t d2, uint32_t d3, uint32_t &x, uint32_t &c, uint32_t &worst,
-                                             const uint32_t &fb, uint32_t k4, uint32_t top, FLUSH &&flush)
+                                             const uint32_t &fb, uint32_t k4, uint32_t top, uint32_t sbv, uint32_t mask2, FLUSH &&flush)
 {
     if (c >= kPairBlock * (fb + 1u))
         flush(c);
-    encode_pairs_8rounds<TRACK>(x, c, worst, d3, d2, k4, top); // rounds 15 .. 8
+    if constexpr (ALIAS)
+        encode_alias_pairs_8rounds<TRACK>(x, c, worst, d3, d2, k4, top, sbv, mask2);
+    else
+        encode_pairs_8rounds<TRACK>(x, c, worst, d3, d2, k4, top); // rounds 15 .. 8
     if (c >= kPairBlock * (fb + 1u))
         flush(c);
-    encode_pairs_8rounds<TRACK>(x, c, worst, d1, d0, k4, top); // rounds 7 .. 0
+    if constexpr (ALIAS)
+        encode_alias_pairs_8rounds<TRACK>(x, c, worst, d1, d0, k4, top, sbv, mask2);
+    else
+        encode_pairs_8rounds<TRACK>(x, c, worst, d1, d0, k4, top); // rounds 7 .. 0
 }
 
-template <bool TRACK>
-__global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_byte_pairs(const EncParams p)
+// The body of k_encode_batch_byte_pairs and, with ALIAS, of k_encode_batch_alias_pairs (behind it): everything but the tables, the
+// rings' base and the rounds is the same code.
+template <bool ALIAS, bool TRACK> __device__ __forceinline__ void encode_batch_pairs(const EncParams p)
 {
-    using Tr = FmtTraits<FMT_BYTE>;
+    using Tr = FmtTraits<FMT_BYTE>; // (the alias format's states are the byte format's: RANS_BYTE_L, 32 bits)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    {   // EncRec {freq | rshift << 24, bias, rcp, -} -> the sequence's records (k_encode<byte>'s prologue), 256 of them
+    if constexpr (ALIAS) {
+        // {freq | start << 16, floor(2^32 / freq)} (padded to 256 by the host) -> the sequence's records {rcp, (2^24 - freq) | rshift
+        // << 24, start | inc << 16, x_max}: Alverson's reciprocal (rans_byte.h:201-243) from the frequency, inc = 1 for freq == 1
+        const uint2 *g0 = reinterpret_cast<const uint2 *>(p.alias_recs8);
+        uint4 *l0 = reinterpret_cast<uint4 *>(smem);
+        for (uint32_t k = threadIdx.x; k < 256u; k += blockDim.x) {
+            const uint2 r = g0[k];
+            const uint32_t freq = k < p.nsyms ? r.x & 0xffffu : 0u, start = r.x >> 16;
+            uint4 rec = {0u, 0xffffffffu, 0u, 0xffffffffu}; // no frequency: nothing leaves, q = 0, bit 31 for TRACK
+            if (freq == 1u) {
+                rec = uint4{0xffffffffu, 0xffffffu, start | 0x10000u, 1u << (31u - p.scale_bits)};
+            } else if (freq) {
+                const uint32_t sh = 32u - (uint32_t)__builtin_clz(freq - 1u); // ceil(log2 freq), 1..16
+                const uint32_t rcp = (uint32_t)(((1ull << (sh + 31u)) + freq - 1u) / freq);
+                rec = uint4{rcp, (0x1000000u - freq) | ((sh - 1u) << 24), start, freq << (31u - p.scale_bits)};
+            }
+            l0[k] = rec;
+        }
+        stage_table(smem + kEncPairTable, p.alias_remap16, 2u << p.scale_bits); // remap16 behind the records
+    } else { // EncRec {freq | rshift << 24, bias, rcp, -} -> the sequence's records (k_encode<byte>'s prologue), 256 of them
         const uint4 *g0 = reinterpret_cast<const uint4 *>(p.enc_recs);
         uint4 *l0 = reinterpret_cast<uint4 *>(smem);
         for (uint32_t k = threadIdx.x; k < 256u; k += blockDim.x) {
@@ -616,15 +754,25 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_byte_pairs(cons
     const uint32_t lane = lane_id();
     const uint32_t wave = uniform(threadIdx.x >> 6);
     const uint32_t waves_per_block = blockDim.x >> 6;
-    uint32_t ring = kEncPairTable + wave * kPairWaveLds + (lane >> 1) * kPairRow; // raw LDS byte address of the pair's ring
-    uint32_t ring_i = ring + 16u * (lane & 1u);                                   // where this lane's 16 bytes of a block lie
+    uint32_t rings_at = kEncPairTable; // the rows, behind the tables
+    if constexpr (ALIAS)
+        rings_at += 2u << p.scale_bits;
+    uint32_t ring = rings_at + wave * kPairWaveLds + (lane >> 1) * kPairRow; // raw LDS byte address of the pair's ring
+    uint32_t ring_i = ring + 16u * (lane & 1u);                              // where this lane's 16 bytes of a block lie
     uint32_t top = ring + (kPairRing - 1u), k4 = 4u;
     uint32_t sel = (lane & 1u) ? 0x03010705u : 0x06040200u;
+    uint32_t sbv = 0u, mask2 = 0u; // ALIAS: the put's shift, and what keeps its gather inside remap16
     pin_vgpr(ring);
     pin_vgpr(ring_i);
     pin_vgpr(top);
     pin_vgpr(k4);
     pin_vgpr(sel);
+    if constexpr (ALIAS) {
+        sbv = p.scale_bits;
+        mask2 = ((1u << p.scale_bits) - 1u) << 1;
+        pin_vgpr(sbv);
+        pin_vgpr(mask2);
+    }
     const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 31u) >> 5); // wave-loads, one per claim (the last one may hold fewer than 32
                                                                          // streams); stream indices are 32-bit
 
@@ -693,7 +841,10 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_byte_pairs(cons
                 const bool in = k < tail_rounds; // (the same for both lanes of a pair)
                 const uint32_t r = tail_rounds - 1u - k;
                 const bool active = in && 2u * r + i < tail; // (an odd count: state 1 sits the first round out)
-                encode_pair_round(x, c, worst, active ? (uint32_t)tsrc[(uint64_t)r * 2u] : 0u, active, i, top, lane_o);
+                if constexpr (ALIAS)
+                    encode_alias_pair_round(x, c, worst, active ? (uint32_t)tsrc[(uint64_t)r * 2u] : 0u, active, i, top, lane_o, sbv, mask2);
+                else
+                    encode_pair_round(x, c, worst, active ? (uint32_t)tsrc[(uint64_t)r * 2u] : 0u, active, i, top, lane_o);
                 // (at least every eight rounds of any pair; never true for a pair that sits out: its c stands still)
                 if ((k & 7u) == 7u && c >= kPairBlock * (fb + 1u))
                     flush_block(c);
@@ -743,12 +894,43 @@ __global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_byte_pairs(cons
             piece_to_states(next, d0, d1, d2, d3, sel);
             next = load_piece(q + 1u < pieces);
             const uint32_t worst_keep = worst;
-            encode_piece<TRACK>(d0, d1, d2, d3, x, c, worst, fb, k4, top, flush_block); // (under full exec: see the head)
+            encode_piece<ALIAS, TRACK>(d0, d1, d2, d3, x, c, worst, fb, k4, top, sbv, mask2, flush_block); // (under full exec: see the head)
             worst = run ? worst : worst_keep;
         }
     }
     if (TRACK && __builtin_amdgcn_ballot_w64((worst >> 31) != 0) != 0 && lane == 0)
         atomicOr(p.flags, 1u);
+}
+
+template <bool TRACK> __global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_byte_pairs(const EncParams p)
+{
+    encode_batch_pairs<false, TRACK>(p);
+}
+
+// ---------------------------------------------------------------------------
+// k_encode_batch_alias_pairs -- the alias format's 2-way layout (main_alias.cpp:241-250, 306-330: two states, one pointer that
+// moves DOWN) for rans_amd_encode_batch[_ordered] under RANS_AMD_OPT_BATCH_ENCODE_ALIAS_PAIRS: THIRTY-TWO streams per wave, the
+// mirror image of decode_groups.hip's k_decode_batch_alias_pairs.  An alias stream IS a byte-format stream -- the same
+// renormalisation, the same two states, one pointer, the same flush -- so this is k_encode_batch_byte_pairs' body
+// (encode_batch_pairs<ALIAS = true>): the unit of work, tail first and then 32-byte pieces, piece_to_states and load_piece, the
+// rings and flush_block with its two guards, the finalise, "dead from then on", the slot check, the flags, 64-bit addressing,
+// the scalar claim compare.  Only the put differs (RANS_AE_ROUND): x = ((x / freq) << scale_bits) + remap16[x % freq + start],
+// one more LDS gather in sequence.  Two hazards the byte kernel does not have, and their answers:
+//   1. the gather's index.  A dead pair, a pair without a stream, a tail lane that sits out (the tail's round gathers under
+//      `active` only) and a byte value without a record all run the sequence under full exec, and their start + rem is garbage:
+//      the byte offset is ANDed with (2^scale_bits - 1) << 1 in front of every read, so it lies inside remap16 whatever the lane
+//      holds.  Nothing relies on what an out-of-range LDS read returns.
+//   2. a byte value without a record (frequency 0, or >= nsyms of a 64-symbol model): its record's x_max is ~0, and the count is
+//      still the lane's own two compares -- never more than 2 bytes per lane and round, so the slot bound holds by construction.
+//      TRACK ORs bit 31 of its second word into `worst` (the call reports RANS_AMD_E_MODEL; what the state becomes is free); a
+//      DEAD pair reading the record of byte value 0 raises nothing: `worst` is put back behind every piece, as in the byte kernel.
+// LDS: 4 KiB of records at address 0, remap16 (2 << scale_bits bytes) behind them, then the waves' rows (kPairWaveLds each).  The
+// block is the launcher's (pairs_plan.hpp enc_alias_pairs_plan): 16 waves, twice per CU up to 14 bits, once at 15; at 16 bits
+// the tables leave room for 13 waves.  The kernel works from blockDim.x.
+// ---------------------------------------------------------------------------
+template <bool TRACK> __global__ void __launch_bounds__(kGrpThreads, 8) k_encode_batch_alias_pairs(const EncParams p)
+{
+    encode_batch_pairs<true, TRACK>(p);
 }
 
 } // namespace
@@ -825,6 +1007,46 @@ hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipSt
     const uint64_t loads = (p.nchunks + 31u) / 32u;
     return p.dense256 ? launch_group_kernel<k_encode_batch_byte_pairs<false>, EncParams>(loads, lds, 0, num_cus, stream, p)
                       : launch_group_kernel<k_encode_batch_byte_pairs<true>, EncParams>(loads, lds, 0, num_cus, stream, p);
+}
+
+// the ragged form of the alias format's 2-way layout over u8 symbols, from 32 streams on, at the shapes the alias pair decoder
+// takes (a batch that decodes on pairs also encodes on pairs), for models that carry the encoder's LDS tables; counts, symbol
+// addresses and slots are the kernel's to check
+bool encode_batch_alias_pairs_applicable(const EncParams &p)
+{
+    return p.n_ways == 2 && p.sym_bytes == 1 && p.nsyms >= 2 && p.nsyms <= 256 && (p.nsyms & (p.nsyms - 1u)) == 0 && p.scale_bits >= 8 &&
+           p.scale_bits <= 16 && p.nchunks >= 32 && (reinterpret_cast<uintptr_t>(p.scratch) & 15u) == 0 && p.alias_recs8 && p.alias_remap16;
+}
+
+// One wave-load per wave; the block and its LDS are enc_alias_pairs_plan's (pairs_plan.hpp) -- launch_group_kernel's blocks are
+// kGrpThreads wide, and at 16 bits the tables leave room for 13 waves only, so the few lines of the launch stand here.
+template <auto KERN> static hipError_t launch_alias_pairs_kernel(const EncAliasPairsPlan &plan, const EncParams &p, int num_cus, hipStream_t stream)
+{
+    static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
+    if (hipError_t e = allow_large_lds(reinterpret_cast<const void *>(KERN), (int)kGrpLdsCap, lds_ok); e != hipSuccess)
+        return e;
+    const uint64_t loads = (p.nchunks + 31u) / 32u;
+    const uint64_t want_blocks = (loads + plan.waves - 1u) / plan.waves;
+    const uint64_t cap = (uint64_t)num_cus * plan.blocks_per_cu;
+    const uint32_t grid = (uint32_t)(want_blocks < cap ? want_blocks : cap);
+    RANS_LAUNCH(KERN, dim3(grid), dim3(64u * plan.waves), (size_t)plan.lds_bytes, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_encode_batch_alias_pairs(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name)
+{
+    if (!encode_batch_alias_pairs_applicable(p) || !p.sym_offsets || !p.sym_counts || !p.slot_offsets || !p.lengths || !p.offsets || !p.flags)
+        return hipErrorInvalidValue;
+    const EncAliasPairsPlan plan = enc_alias_pairs_plan(p.scale_bits);
+    static_assert(kEncAliasPairsRecBytes == kEncPairTable && kEncAliasPairsWaveLds == kPairWaveLds && kEncAliasPairsLdsCap == kGrpLdsCap &&
+                      kEncAliasPairsMaxWaves * 64u == kGrpThreads && kEncPairTable == 4096u,
+                  "pairs_plan.hpp restates these; RANS_AE_ROUND's gather carries kEncPairTable as its offset");
+    if (plan.waves == 0 || plan.lds_bytes > kGrpLdsCap || num_cus <= 0)
+        return hipErrorInvalidValue;
+    if (name)
+        *name = KernelId::encode_batch_alias_pairs;
+    return p.dense256 ? launch_alias_pairs_kernel<k_encode_batch_alias_pairs<false>>(plan, p, num_cus, stream)
+                      : launch_alias_pairs_kernel<k_encode_batch_alias_pairs<true>>(plan, p, num_cus, stream);
 }
 
 } // namespace rans_amd

@@ -1,6 +1,6 @@
-// groups_common.hpp -- what the eight group kernels share (internal): decode_groups.hip's k_decode_word_groups,
+// groups_common.hpp -- what the nine group kernels share (internal): decode_groups.hip's k_decode_word_groups,
 // k_decode_batch_word_groups, k_decode_byte_pairs, k_decode_batch_byte_pairs, k_decode_batch_alias_pairs and encode_groups.hip's k_encode_word_groups,
-// k_encode_batch_word_groups, k_encode_batch_byte_pairs.  Every piece is written once here, forceinline, and where the kernels differ the difference is
+// k_encode_batch_word_groups, k_encode_batch_byte_pairs, k_encode_batch_alias_pairs.  Every piece is written once here, forceinline, and where the kernels differ the difference is
 // an argument or a template parameter that is constant at the call site (profiles/groups_common_isa.md: what each kernel
 // compiles to with them).  The hand-scheduled sequences stay with their kernels.  Helpers that took the place of a lambda
 // take their arguments as the lambda did -- what it captured by `const T &`, its own parameters by value: the register

@@ -18,8 +18,12 @@
 // Its ids follow the first list's in KernelId, its rows are kAliasPairKernelEntries; kKernelEntries (what
 // tests/kernel_names_driver.cpp prints and tests/_kernel_rows.py reads) is the first list alone, and
 // tests/kernel_names_alias_pairs_driver.cpp with tests/_batch_alias_pairs.py hold the second list to its rows.
-// kernel_entry(), kernel_name() and kernel_family() resolve ids from both.  (Folding the two into one list is a later refactor:
-// the row module has to know the family first, and the first list's printed lines and count are pinned by tests.)
+// A third list follows the second: RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS_ENCODE, the family
+//   batch_alias_pairs_encode  ... encoder (RANS_AMD_OPT_BATCH_ENCODE_ALIAS_PAIRS)
+// Its ids follow the second list's, its rows are kAliasPairEncodeKernelEntries; tests/kernel_names_alias_pairs_encode_driver.cpp
+// with tests/_batch_encode_alias_pairs.py hold it to its rows.
+// kernel_entry(), kernel_name() and kernel_family() resolve ids from all three.  (Folding the three into one list is a later refactor:
+// the row module has to know the families first, and the printed lines and counts of the first two lists are pinned by tests.)
 // Nine families in the first list: a new kernel is one more row at the list's end (an id is its row's place, counted from 1, and the
 // ids that exist stay where they are); tests/kernel_names_driver.cpp prints every row and tests/_kernel_rows.py reads them.
 #pragma once
@@ -84,6 +88,9 @@ namespace rans_amd {
 #define RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS(X)                                                      \
     X(decode_batch_alias_pairs, "k_decode_batch_alias_pairs", batch_alias_pairs_decode)
 
+#define RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS_ENCODE(X)                                               \
+    X(encode_batch_alias_pairs, "k_encode_batch_alias_pairs", batch_alias_pairs_encode)
+
 enum class KernelFamily {
     uniform,
     batch,
@@ -95,6 +102,7 @@ enum class KernelFamily {
     batch_r64_lanes_decode,
     batch_r64_lanes_encode,
     batch_alias_pairs_decode,
+    batch_alias_pairs_encode,
 };
 
 enum class KernelId {
@@ -102,6 +110,7 @@ enum class KernelId {
 #define X(id, name, family) id,
     RANS_AMD_KERNEL_NAMES(X)
     RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS(X) // (behind the first list: an id of this one is kKernelEntryCount + 1 + its row)
+    RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS_ENCODE(X) // (behind the second: kKernelEntryCount + kAliasPairKernelEntryCount + 1 + its row)
 #undef X
 };
 
@@ -128,14 +137,26 @@ constexpr KernelEntry kAliasPairKernelEntries[] = {
 };
 constexpr int kAliasPairKernelEntryCount = (int)(sizeof(kAliasPairKernelEntries) / sizeof(kAliasPairKernelEntries[0]));
 
+// the third list's entries, in its order
+constexpr KernelEntry kAliasPairEncodeKernelEntries[] = {
+#define X(id, name, family) {KernelId::id, name, KernelFamily::family, #family},
+    RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS_ENCODE(X)
+#undef X
+};
+constexpr int kAliasPairEncodeKernelEntryCount = (int)(sizeof(kAliasPairEncodeKernelEntries) / sizeof(kAliasPairEncodeKernelEntries[0]));
+
 constexpr const KernelEntry &kernel_entry(KernelId id) // (not for KernelId::none)
 {
-    return (int)id <= kKernelEntryCount ? kKernelEntries[(int)id - 1] : kAliasPairKernelEntries[(int)id - 1 - kKernelEntryCount];
+    return (int)id <= kKernelEntryCount                                ? kKernelEntries[(int)id - 1]
+           : (int)id <= kKernelEntryCount + kAliasPairKernelEntryCount ? kAliasPairKernelEntries[(int)id - 1 - kKernelEntryCount]
+                                                                       : kAliasPairEncodeKernelEntries[(int)id - 1 - kKernelEntryCount - kAliasPairKernelEntryCount];
 }
 constexpr const char *kernel_name(KernelId id) { return id == KernelId::none ? "" : kernel_entry(id).name; }
 constexpr KernelFamily kernel_family(KernelId id) { return kernel_entry(id).family; } // (not for KernelId::none)
 static_assert(kernel_entry(KernelId::encode_batch_r64_lanes).id == KernelId::encode_batch_r64_lanes &&
-                  kernel_entry(KernelId::decode_batch_alias_pairs).id == KernelId::decode_batch_alias_pairs,
-              "ids of both lists resolve to their own rows");
+                  kernel_entry(KernelId::decode_batch_alias_pairs).id == KernelId::decode_batch_alias_pairs &&
+                  kernel_entry(KernelId::encode_batch_alias_pairs).id == KernelId::encode_batch_alias_pairs &&
+                  (int)KernelId::encode_batch_alias_pairs == 55,
+              "ids of all three lists resolve to their own rows");
 
 } // namespace rans_amd

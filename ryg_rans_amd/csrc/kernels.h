@@ -37,6 +37,7 @@ constexpr uint32_t kVarBatchEncPairs = 256u; // ... in the ENCODER as well (k_en
 constexpr uint32_t kVarBatchLanes = 512u;    // ragged batches of the 2-way rans64 layout: 64 streams per wave (k_decode_batch_r64_lanes)
 constexpr uint32_t kVarBatchEncLanes = 1024u; // ... in the ENCODER as well (k_encode_batch_r64_lanes)
 constexpr uint32_t kVarBatchAliasPairs = 2048u; // ragged batches of the 2-way alias layout: 32 streams per wave (k_decode_batch_alias_pairs)
+constexpr uint32_t kVarBatchEncAliasPairs = 4096u; // ... in the ENCODER as well (k_encode_batch_alias_pairs)
 
 constexpr uint32_t kWorkPools = 8;       // chunk hand-out counters per launch (one per XCD)
 constexpr uint32_t kWorkPoolStride = 16; // in uint32: every counter on its own 64-byte line
@@ -184,7 +185,7 @@ struct EncParams {
     uint64_t ovf_base;          // redo: byte offset of the overflow region (= nchunks * the first launch's slot_bytes)
     uint32_t no_lanes;          // the request goes to the wave encoders whatever its interleave (sized slots the lane encoders cannot take)
     // Ragged batches (rans_amd_encode_batch[_ordered]; k_encode's MODE 4, k_encode_batch_word_groups,
-    // k_encode_batch_byte_pairs and k_encode_batch_r64_lanes, nobody else reads these): stream c codes the sym_counts[c] symbols at syms + sym_offsets[c] * sym_bytes into the slot [slot_offsets[c],
+    // k_encode_batch_byte_pairs, k_encode_batch_alias_pairs and k_encode_batch_r64_lanes, nobody else reads these): stream c codes the sym_counts[c] symbols at syms + sym_offsets[c] * sym_bytes into the slot [slot_offsets[c],
     // slot_offsets[c + 1]) of `scratch` (the caller's container, out_cap bytes), ending at the slot's end; claim k takes
     // stream order[k] -- every stream lands in its OWN slot whatever its position, the order decides who codes it and when
     const uint64_t *sym_offsets;
@@ -256,8 +257,8 @@ hipError_t launch_compact(const CompactParams &p, int num_cus, hipStream_t strea
 // for the 8-way word layout eight streams per wave, in the decoder under kVarBatchGroups and in the encoder under
 // kVarBatchEncGroups, and for the 2-way byte layout 32 streams per wave, in the decoder under kVarBatchPairs and in the
 // encoder under kVarBatchEncPairs, and for the 2-way rans64 layout 64 streams per wave, in the decoder under kVarBatchLanes and
-// in the encoder under kVarBatchEncLanes, and for the 2-way alias layout 32 streams per wave in the decoder under
-// kVarBatchAliasPairs.
+// in the encoder under kVarBatchEncLanes, and for the 2-way alias layout 32 streams per wave, in the decoder under
+// kVarBatchAliasPairs and in the encoder under kVarBatchEncAliasPairs.
 // `format` is the kernel-side format number.
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);

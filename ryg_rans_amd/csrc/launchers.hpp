@@ -4,6 +4,7 @@
 #pragma once
 
 #include "kernels.h"
+#include "pairs_plan.hpp" // the alias pair encoder's block and LDS (host-only)
 
 #include "../../include/ryg_rans_amd.h" // the option ids and public formats of kBatchFamilies
 
@@ -107,6 +108,11 @@ hipError_t launch_encode_batch_word_groups(const EncParams &p, int num_cus, hipS
 // with its own symbol count, symbol address and slot, from 32 streams on, scale_bits 8..16
 bool encode_batch_byte_pairs_applicable(const EncParams &p);
 hipError_t launch_encode_batch_byte_pairs(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
+// ... and the same plan for the alias format's 2-way layout (main_alias.cpp; rans_amd_encode_batch[_ordered], kBatchFamilies): 32
+// STREAMS per wave over the encoder's LDS tables (records + remap16, 2 << scale_bits bytes: the launcher sizes the block from what
+// they leave, pairs_plan.hpp), u8 symbols, a power-of-two alphabet of at most 256 symbols, scale_bits 8..16, from 32 streams on
+bool encode_batch_alias_pairs_applicable(const EncParams &p);
+hipError_t launch_encode_batch_alias_pairs(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
 
 // lane-per-stream kernels (N = 1, 2, 4, 8 with at least kLaneKernelMinChunks chunks): decode_lanes.hip, encode_lanes.hip
 constexpr uint64_t kLaneKernelMinChunks = 64;
@@ -135,6 +141,8 @@ bool encode_lanes_sized_ok(int format, const EncParams &p, int num_cus);
 // The streams-per-wave families of the ragged batches, in the order the launchers ask them: a context option sets the bit, and
 // a batch of the row's public format that the row's *_applicable accepts goes to the row's kernel; every other batch takes the
 // wave-per-stream kernels, under the options as well.  A decoder's row leaves the encoder's pair null and the other way round.
+// The format is the KERNEL-side one that the launchers are handed: an alias model with the encoder's LDS tables encodes under
+// kKernelFormatAliasLds, not RANS_AMD_FMT_ALIAS.
 // `streams` completes the option's E_ARG text.  (The ragged forms of the other lane kernels -- the 1-, 4- and 8-way interleaves -- are later
 // work: one more row each.)
 struct BatchFamily {
@@ -158,6 +166,7 @@ constexpr BatchFamily kBatchFamilies[] = {
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_GROUPS, kVarBatchEncGroups, RANS_AMD_FMT_WORD, encode_batch_word_groups, "eight 8-way word streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_PAIRS, kVarBatchEncPairs, RANS_AMD_FMT_BYTE, encode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_LANES, kVarBatchEncLanes, RANS_AMD_FMT_R64, encode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
+    RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_ALIAS_PAIRS, kVarBatchEncAliasPairs, kKernelFormatAliasLds, encode_batch_alias_pairs, "thirty-two 2-way alias streams per wave"),
 };
 #undef RANS_BATCH_DECODER
 #undef RANS_BATCH_ENCODER
