@@ -255,6 +255,34 @@ enum rans_amd_option_third {
                                               encoder at 16 bits on the same counts: 3.58 ms.
                                               Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
 };
+/* Options added behind those three enums (which stay as they are): the same call takes them. */
+enum rans_amd_batch_option {
+    RANS_AMD_OPT_BATCH_SINGLES = 13        /* 1 = rans_amd_decode_batch decodes SIXTY-FOUR streams per wavefront, one per lane,
+                                              where the batch is the NON-INTERLEAVED layout every reference program writes
+                                              first (one rANS state: n_ways 1, u8 symbols, at least 64 streams) in any of the
+                                              four formats: byte and alias at scale_bits 8..16 (alias: a power-of-two alphabet
+                                              of at most 256 symbols), word (scale_bits 12), rans64 at scale_bits 7..16, the
+                                              tables and one wavefront's stream rings inside the CU's 160 KiB of LDS:
+                                              k_decode_batch_singles<byte|word|r64|alias>, the ragged form of the lane kernel
+                                              that decodes uniform 1-way chunks.  Every other shape (u16 symbols, other
+                                              interleaves, fewer streams, rans64 outside 7..16 bits) takes the kernels it took
+                                              before, under options 5 to 12 as well; rans_amd_decode_batch_adaptive and the
+                                              encoders are not affected.  The advice is RANS_AMD_OPT_BATCH_LANES': the wavefront
+                                              lasts as long as the longest of its 64 streams (pass d_order), and sym_align 64
+                                              is the fast layout (a stream whose symbols start on a 64-byte line has its lines
+                                              written by a quad of lanes; one on the 4-byte grid in 16-byte pieces by its own
+                                              lane; any other byte by byte).  A stream of more than 2^30 bytes is reported as
+                                              failed by this decoder.
+                                              Measured with d_order on 181 992 streams of up to 64 Ki symbols at sym_align 64, this
+                                              kernel against the wave kernel with the same d_order:
+                                              byte (14 bits) 13.68 against 76.54 ms, 5.60 x;
+                                              rans64 (14 bits) 11.18 against 61.43 ms, 5.49 x;
+                                              word (12 bits) 8.95 against 61.64 ms, 6.88 x;
+                                              alias (16 bits) 14.58 against 76.71 ms, 5.26 x;
+                                              the uniform 1-way decode of the same symbols: 1.31 / 1.09 / 0.94 / 1.39 ms
+                                              (profiles/batch_singles.json).
+                                              Default 0: one stream per wavefront.  Any other value is RANS_AMD_E_ARG. */
+};
 
 /* ---- model building (SymbolStats, main.cpp:49-129) ---------------------- */
 
@@ -490,10 +518,15 @@ int rans_amd_container_slice(const uint64_t *offsets, const uint32_t *lengths, u
  * main_alias.cpp writes (alias format, u8 symbols, n_ways 2, scale_bits 8..16, a power-of-two alphabet of at most 256 symbols)
  * in a batch of at least 32 streams, decoded by rans_amd_decode_batch on a context with RANS_AMD_OPT_BATCH_ALIAS_PAIRS = 1
  * and coded by rans_amd_encode_batch[_ordered] on a context with RANS_AMD_OPT_BATCH_ENCODE_ALIAS_PAIRS = 1 (independent again,
- * the same bytes), the same advice as for the byte pairs: pass d_order, and sym_align = 4 is the fast layout.  Every other
- * interleave stays one stream per wavefront in both directions; ragged forms of the other lane kernels (1-, 4- and 8-way
- * interleaves) are later work.  A stream of 0 symbols is the n_ways flushed initial
- * states.
+ * the same bytes), the same advice as for the byte pairs: pass d_order, and sym_align = 4 is the fast layout.  A fifth shape
+ * is the layout a user of rans_byte.h / rans64.h is most likely to hold, the NON-INTERLEAVED stream with one state that all
+ * four reference programs write first (n_ways 1, u8 symbols; byte and alias at scale_bits 8..16, the alias alphabet a power
+ * of two of at most 256 symbols; word at 12; rans64 at 7..16): in a batch of at least 64 streams it is decoded sixty-four
+ * streams per wavefront, one per lane, by rans_amd_decode_batch on a context with RANS_AMD_OPT_BATCH_SINGLES = 1 (the same
+ * bytes; the advice is the rans64 lanes': pass d_order, sym_align = 64 is the fast layout, a stream of more than 2^30 bytes is
+ * reported as failed by that decoder).  Every other interleave stays one stream per wavefront in both directions; the 1-way
+ * ENCODER, the 2-way scalar word layout and ragged forms of the 4- and 8-way lane kernels are later work.  A stream of 0
+ * symbols is the n_ways flushed initial states.
  * n_streams == 0 is RANS_AMD_OK and launches nothing.  Both coding calls may be captured into a hipGraph under the rules
  * of rans_amd_encode / rans_amd_decode (run once outside the capture first; no h_bad_streams while capturing).
  *

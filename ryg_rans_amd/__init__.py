@@ -29,6 +29,7 @@ OPT_BATCH_LANES = 9
 OPT_BATCH_ENCODE_LANES = 10
 OPT_BATCH_ALIAS_PAIRS = 11
 OPT_BATCH_ENCODE_ALIAS_PAIRS = 12
+OPT_BATCH_SINGLES = 13
 
 OK, E_ARG, E_MODEL, E_SPACE, E_CORRUPT, E_UNSUPPORTED, E_HIP, E_NOMEM = range(8)
 

@@ -1106,6 +1106,261 @@ __global__ void __launch_bounds__(1024) k_decode_batch_r64_lanes(const DecParams
 }
 #undef R64B_CLOBBERS
 
+// ---------------------------------------------------------------------------
+// k_decode_batch_singles: the ragged form of k_decode_lanes_staged<FMT, 1> (rans_amd_decode_batch under
+// RANS_AMD_OPT_BATCH_SINGLES) -- the NON-INTERLEAVED stream every reference program writes first (main.cpp:173-182,
+// main64.cpp:175-184, main_simd.cpp:161-169, main_alias.cpp:300-309), sixty-four STREAMS per wave, one per lane with its one
+// state, each with its own symbol count, output address, stream offset and length.  Compiler-scheduled like the staged kernel
+// (dec_step, DecTables, LaneRing); the plan is k_decode_batch_r64_lanes', piece by piece:
+//   * a unit of work (WorkClaims) is one wave-load of the hand-out order: lane l of claim k holds stream order[64 k + l], or
+//     64 k + l without an order; a position at or past nchunks has no stream.
+//   * index entries are the caller's data, checked as fetch_stream_entry checks them with the format's own unit and state size
+//     (written out for the `again` pass, as in the rans64 kernel: a fix there has to be made here as well): the order entry
+//     names a stream, the offset is a multiple of the unit (1 byte/alias, 2 word, 4 rans64), the stream holds its state (4
+//     bytes; rans64 8) and lies inside the container, the symbol range lies inside [0, out_syms).  A stream that fails is
+//     counted once, nothing of it is fetched, nothing stored.  Ring positions are 32-bit: a stream of more than 2^30 bytes is
+//     counted as failed as well -- the one rule the wave-per-stream kernels do not have.
+//   * the window: 32-bit positions from the line of the wave-load's lowest valid stream (wave_min_offset); lanes 2^30 bytes and
+//     more above it wait for another pass over the same claim (`again`).  Every fetch is compared against the container's end
+//     rounded up to 16 bytes: reads behind it yield zeros and never touch memory.  Nothing here reads outside
+//     [container, container + container_bytes rounded up to 16) -- the initial state is one load at the stream's own address
+//     (unaligned for byte and alias streams, as in the uniform kernel), inside the stream because its length was checked first.
+//   * the rings: kLaneWaveLds per wave, a 128-byte ring per lane in rows kLaneRingStride apart, one request word per lane.  The
+//     WAVE refills before every group of 16 symbols, under full exec, exactly as the staged kernel does: lanes publish the line
+//     they need, quads fetch one lane's 64-byte line with four 16-byte loads.  The invariant is the staged kernel's: at least 64
+//     bytes ahead before a group, which is what 16 symbols can take at the most (rans64: 4 bytes per symbol); a VALID stream
+//     reaches half of that -- symbols of frequency 1 at 16 bits take 32 bytes per group in the byte, alias and rans64 formats,
+//     the word format at its 12 bits 24 (tests/test_batch_singles_host.py) --, so the invariant has 32 bytes to spare.  A lane
+//     without a stream, or whose stream has no group in this trip or tail pass, requests nothing.
+//   * whole trips: 64 symbols per lane, the wave runs max_l(count_l >> 6) of them, a lane takes part while
+//     trip < count >> 6 (plain exec masking: nothing here is asm, so nobody has to be parked).
+//   * stores: by the address of a lane's first symbol, as in the rans64 kernel.  On a 64-byte line the quad transposes
+//     (quad_transpose, under full exec) and store instruction t writes the line of the quad's lane t under "this trip < the
+//     trips of lane t"; on the 4-byte grid the lane writes its own four 16-byte pieces; any other address byte by byte.
+//     sym_align = 64 is the fast layout.  Nothing is written outside a validated stream's own [sym_offset, sym_offset + count).
+//   * the tail: count & 63 symbols in groups of sixteen, each behind a refill of its own, byte stores.
+//   * the verdict: the state is back at the format's L and consumed + state bytes == len, else the stream is counted.
+// FMT_ALIAS: the alias decoder's divider + half-bucket records over a power-of-two alphabet of at most 256 u8 symbols, as for
+// the alias pairs.  FMT_R64 is the cum2sym form (the search variant is another kernel format and stays on the wave kernel).
+// ---------------------------------------------------------------------------
+template <int FMT>
+__global__ void __launch_bounds__(1024) k_decode_batch_singles(const DecParams p)
+{
+    using Tr = FmtTraits<FMT>;
+    using state_t = typename Tr::state_t;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const unsigned long long t_start = p.span ? wall_clock64() : 0ull;
+    const uint32_t t0_bytes = (p.table0_bytes + 15u) & ~15u;
+    const uint32_t t1_bytes = (p.table1_bytes + 15u) & ~15u;
+    stage_table(smem, p.table0, t0_bytes);
+    stage_table(smem + t0_bytes, p.table1, t1_bytes);
+    __syncthreads();
+    if (!lds_starts_at_zero(smem)) { // dec_step addresses the first table by raw offsets
+        if (threadIdx.x == 0)
+            atomicAdd(p.err_count, 1ull << 32);
+        return;
+    }
+    reset_for_next_launch(p);
+    DecTables<FMT> T;
+    T.init(smem, smem + t0_bytes, p.scale_bits, p.log2nsyms);
+
+    const uint32_t lane = lane_id();
+    const uint32_t wave = uniform(threadIdx.x >> 6);
+    const uint32_t waves_per_block = blockDim.x >> 6;
+    uint8_t *rings = smem + t0_bytes + t1_bytes + wave * kLaneWaveLds;
+    uint32_t *req = reinterpret_cast<uint32_t *>(rings + 64u * kLaneRingStride);
+    const uint32_t part = lane & 3u, grp = lane >> 2;
+    const uint32_t l16 = part * 16u;
+
+    const uint64_t cbase = reinterpret_cast<uint64_t>(p.container);
+    const uint64_t glimit = cbase + ((p.container_bytes + 15u) & ~uint64_t(15)); // (the container is 16-byte aligned: api.cpp)
+    const uint32_t loads = (uint32_t)(((uint64_t)p.nchunks + 63u) >> 6); // wave-loads, one per claim; stream indices are 32-bit
+    uint32_t nbad = 0;
+    WorkClaims work;
+    work.init(p.work_counter, wave, waves_per_block);
+    uint64_t again = 0; // lanes of the wave-load in hand whose streams lay beyond the last pass's window (wave_min_offset)
+    uint64_t load = 0;
+    for (;;) {
+        if (again == 0) {
+            load = work.take(lane);
+            if ((load >> 32) != 0 || (uint32_t)load >= loads) // (scalar compares)
+                break;
+        }
+        // ---- this lane's stream: its index entries, all of them the caller's data
+        const uint64_t pos = load * 64u + lane;
+        const bool mine = pos < p.nchunks && (again == 0 || ((again >> lane) & 1u)); // a position this pass looks at
+        uint64_t s = pos;
+        if (mine && p.order)
+            s = p.order[pos];
+        bool valid = mine && s < p.nchunks;
+        uint64_t off = 0, first = 0;
+        uint32_t len = 0, count = 0;
+        if (valid) {
+            off = p.offsets[s];
+            len = p.lengths[s];
+            first = p.sym_offsets[s];
+            count = p.sym_counts[s];
+        }
+        valid = valid && (off & (Tr::kUnit - 1u)) == 0 && len >= Tr::kStateBytes && len <= (1u << 30) && off <= p.container_bytes &&
+                len <= p.container_bytes - off && first <= p.out_syms && count <= p.out_syms - first;
+        if (mine && !valid)
+            nbad++; // (a rejected entry is seen in one pass only: it never joins `again`)
+        // the window: the line of the lowest valid stream of this pass
+        const uint64_t rb = wave_min_offset(off, valid) & ~uint64_t(kLaneLine - 1);
+        const bool far = valid && off - rb >= (1u << 30);
+        again = __builtin_amdgcn_ballot_w64(far);
+        valid = valid && !far;
+
+        // ---- the lane's own counts and where its symbols go ([dst, dst + count) lies inside the output)
+        const uint64_t dst = reinterpret_cast<uint64_t>(p.out) + first;
+        const uint32_t trips = valid ? count >> 6 : 0u;
+        const uint32_t tail = valid ? count & 63u : 0u;
+        const bool by_quad = (dst & 63u) == 0, by_dwords = (dst & 3u) == 0;
+        // store instruction t writes the line of the quad's lane t, this lane its piece -- while that lane has trips left
+        const uint32_t qtrips = by_quad ? trips : 0u;
+        uint64_t at[4];
+        uint32_t tq[4];
+        {
+            const uint32_t dlo = (uint32_t)dst, dhi = (uint32_t)(dst >> 32);
+            at[0] = (((uint64_t)quad_perm<0x00>(dhi) << 32) | quad_perm<0x00>(dlo)) + l16;
+            at[1] = (((uint64_t)quad_perm<0x55>(dhi) << 32) | quad_perm<0x55>(dlo)) + l16;
+            at[2] = (((uint64_t)quad_perm<0xAA>(dhi) << 32) | quad_perm<0xAA>(dlo)) + l16;
+            at[3] = (((uint64_t)quad_perm<0xFF>(dhi) << 32) | quad_perm<0xFF>(dlo)) + l16;
+            tq[0] = quad_perm<0x00>(qtrips);
+            tq[1] = quad_perm<0x55>(qtrips);
+            tq[2] = quad_perm<0xAA>(qtrips);
+            tq[3] = quad_perm<0xFF>(qtrips);
+        }
+
+        // ---- the initial state (RansDecInit): one load at the stream's own address, inside the stream (len was checked)
+        state_t x = Tr::kL;
+        if (valid) {
+            const uint8_t RANS_GLOBAL *src = (const uint8_t RANS_GLOBAL *)p.container + off;
+            if constexpr (FMT == FMT_R64) {
+                const u32x2 v = *reinterpret_cast<const u32x2 RANS_GLOBAL *>(src);
+                x = (uint64_t)v.x | ((uint64_t)v.y << 32);
+            } else {
+                x = *reinterpret_cast<const uint32_t RANS_GLOBAL *>(src);
+            }
+        }
+        LaneRing<FMT> W;
+        W.row = rings + lane * kLaneRingStride;
+        W.cur = valid ? (uint32_t)(off - rb) + Tr::kStateBytes : 0u;
+        W.used = 0;
+        uint32_t ld = W.cur & ~(kLaneLine - 1u); // next line this lane has not staged yet
+
+        // the whole wave takes part (also lanes without a stream, under full exec): lane -> which line its stream needs
+        // (live: it has a group to decode behind this refill), then lane (4 g + part) moves 16 bytes of stream (16 j + g)'s
+        // line, j = 0..3
+        auto refill = [&](bool live) {
+            const bool need = live && (int32_t)(ld - W.cur) < (int32_t)kLaneLine;
+            req[lane] = need ? (ld | 1u) : 0u;
+            if (need)
+                ld += kLaneLine;
+            uint32_t r[4];
+            u32x4 v[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                r[j] = req[16 * j + grp]; // LDS ops of one wave execute in order: sees the writes above
+                v[j] = u32x4{0u, 0u, 0u, 0u};
+                const uint64_t a = cbase + rb + (r[j] & ~(kLaneLine - 1u)) + l16;
+                if ((r[j] & 1u) && a < glimit) // behind the container's last 16-byte granule: zeros, no access
+                    v[j] = __builtin_nontemporal_load(reinterpret_cast<gvec_cptr>(a));
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (r[j] & 1u) {
+                    uint8_t *to = rings + (16u * j + grp) * kLaneRingStride + (r[j] & kLaneLine) + l16;
+                    reinterpret_cast<u32x2 *>(to)[0] = u32x2{v[j].x, v[j].y}; // rows are 8-byte aligned
+                    reinterpret_cast<u32x2 *>(to)[1] = u32x2{v[j].z, v[j].w};
+                }
+        };
+        // 16 symbols into four dwords
+        auto decode16 = [&]() -> u32x4 {
+            uint32_t pk[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                uint32_t sy = dec_step<FMT>(T, x);
+                if constexpr (Tr::kSymByte == 3)
+                    sy >>= 24;
+                pk[k / 4] |= (sy & 0xffu) << (8 * (k % 4));
+                W.renorm(x, true);
+            }
+            return u32x4{pk[0], pk[1], pk[2], pk[3]};
+        };
+
+        refill(valid && count != 0u); // two lines ahead before the first group: this one and the group's own
+
+        // ---- whole trips: 64 symbols per lane, four groups of 16 with a refill before each
+        for (uint32_t trip = 0; __builtin_amdgcn_ballot_w64(trip < trips) != 0; ++trip) {
+            const bool run = trip < trips;
+            u32x4 q0 = {0u, 0u, 0u, 0u}, q1 = q0, q2 = q0, q3 = q0;
+            refill(run);
+            if (run)
+                q0 = decode16();
+            refill(run);
+            if (run)
+                q1 = decode16();
+            refill(run);
+            if (run)
+                q2 = decode16();
+            refill(run);
+            if (run)
+                q3 = decode16();
+            const uint64_t o = (uint64_t)trip << 6;
+            if (run && !by_quad) { // the lane's own 64 bytes, from its own registers
+                if (by_dwords) {
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o) = q0;
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o + 16u) = q1;
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o + 32u) = q2;
+                    *reinterpret_cast<lanes_u32x4_a4 RANS_GLOBAL *>(dst + o + 48u) = q3;
+                } else {
+                    uint8_t RANS_GLOBAL *d = reinterpret_cast<uint8_t RANS_GLOBAL *>(dst + o);
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        d[j] = (uint8_t)(q0[j >> 2] >> (8 * (j & 3)));
+                        d[16 + j] = (uint8_t)(q1[j >> 2] >> (8 * (j & 3)));
+                        d[32 + j] = (uint8_t)(q2[j >> 2] >> (8 * (j & 3)));
+                        d[48 + j] = (uint8_t)(q3[j >> 2] >> (8 * (j & 3)));
+                    }
+                }
+            }
+            quad_transpose(q0, q1, q2, q3, lane); // (full exec: the moves read all four lanes)
+            if (trip < tq[0])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[0] + o) = q0;
+            if (trip < tq[1])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[1] + o) = q1;
+            if (trip < tq[2])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[2] + o) = q2;
+            if (trip < tq[3])
+                *reinterpret_cast<u32x4 RANS_GLOBAL *>(at[3] + o) = q3;
+        }
+
+        // ---- count & 63 symbols: sixteen at a time behind a refill of their own, byte stores
+        uint8_t RANS_GLOBAL *tdst = reinterpret_cast<uint8_t RANS_GLOBAL *>(dst + ((uint64_t)trips << 6));
+        for (uint32_t j0 = 0; __builtin_amdgcn_ballot_w64(j0 < tail) != 0; j0 += 16u) {
+            const bool live = j0 < tail;
+            refill(live);
+            if (live) {
+                const uint32_t cnt = tail - j0 < 16u ? tail - j0 : 16u;
+                for (uint32_t i = 0; i < cnt; ++i) {
+                    uint32_t sy = dec_step<FMT>(T, x);
+                    if constexpr (Tr::kSymByte == 3)
+                        sy >>= 24;
+                    tdst[j0 + i] = (uint8_t)sy;
+                    W.renorm(x, true);
+                }
+            }
+        }
+        // RansDec end state: the state back at L, every byte of the stream consumed (the reference has no check; ours)
+        if (valid && (x != Tr::kL || W.used + Tr::kStateBytes != len))
+            nbad++;
+    }
+    if (nbad)
+        atomicAdd(p.err_count, (unsigned long long)nbad);
+    record_span(p, t_start, smem, threadIdx.x);
+}
+
 template <int FMT, int NW>
 __global__ void __launch_bounds__(256) k_decode_lanes(const DecParams p)
 {
@@ -1352,6 +1607,66 @@ hipError_t launch_decode_batch_r64_lanes(const DecParams &p, int num_cus, hipStr
         *name = KernelId::decode_batch_r64_lanes;
     return launch_lanes(k_decode_batch_r64_lanes, lds_ok, 160 * 1024, lanes_grid(loads, sw, num_cus), 64 * sw,
                         table_lds + (size_t)sw * kR64WaveLds, stream, p);
+}
+
+// The ragged form of the staged 1-way lane decoder, one instantiation per format (`format` is the kernel-side number, so the
+// rans64 search variant and the word format over u16 symbols are not asked): u8 symbols, from 64 streams on, the scale_bits the
+// format's uniform lane kernel takes -- byte and alias 8..16 (dec_step's 24-bit product; alias: the builder's power-of-two
+// alphabet of at most 256 symbols, so that the table sizes say it, as for the alias pairs), word 12, rans64 7..16 (cum2sym) --,
+// both tables and at least one wave's rings inside the CU's 160 KiB of LDS; any symbol count, any output address.
+bool decode_batch_singles_applicable(int format, const DecParams &p)
+{
+    bool bits = false;
+    switch (format) {
+    case FMT_BYTE: bits = p.scale_bits >= 8 && p.scale_bits <= 16; break;
+    case FMT_ALIAS:
+        bits = p.scale_bits >= 8 && p.scale_bits <= 16 && p.log2nsyms <= 8 && p.table0_bytes == (16u << p.log2nsyms) &&
+               p.table1_bytes == (4u << p.log2nsyms);
+        break;
+    case FMT_WORD: bits = p.scale_bits == 12; break;
+    case FMT_R64: bits = p.scale_bits >= 7 && p.scale_bits <= 16; break;
+    default: break;
+    }
+    return bits && p.n_ways == 1 && p.sym_bytes == 1 && p.nchunks >= 64 && p.sym_offsets && p.sym_counts && !p.trace &&
+           batch_lanes_tables(p) + kLaneWaveLds <= 160 * 1024;
+}
+
+template <int FMT> static hipError_t launch_decode_batch_singles_t(const DecParams &p, int num_cus, hipStream_t stream)
+{
+    // one block per CU, as many waves as the tables leave rings for (16 up to 14 bits; byte at 16 bits, 64 KiB of cum2sym: 10); a
+    // batch that does not fill them spreads its wave-loads evenly (lanes_even_waves)
+    const size_t table_lds = batch_lanes_tables(p);
+    const uint32_t room = (uint32_t)((160 * 1024 - table_lds) / kLaneWaveLds);
+    const uint32_t max_waves = room > 16 ? 16 : room;
+    const uint64_t loads = (p.nchunks + 63) / 64;
+    const uint32_t sw = loads >= (uint64_t)num_cus * max_waves ? max_waves : lanes_even_waves(loads, num_cus, max_waves);
+    static std::atomic<uint64_t> lds_ok{0}; // per instantiation, one bit per device
+    return launch_lanes(k_decode_batch_singles<FMT>, lds_ok, 160 * 1024, lanes_grid(loads, sw, num_cus), 64 * sw,
+                        table_lds + (size_t)sw * kLaneWaveLds, stream, p);
+}
+
+hipError_t launch_decode_batch_singles(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
+{
+    if (!decode_batch_singles_applicable(format, p)) // (kBatchFamilies has asked; a missing kernel is an error, never another path)
+        return hipErrorInvalidValue;
+    switch (format) {
+    case FMT_BYTE:
+        if (name)
+            *name = KernelId::decode_batch_singles_byte;
+        return launch_decode_batch_singles_t<FMT_BYTE>(p, num_cus, stream);
+    case FMT_WORD:
+        if (name)
+            *name = KernelId::decode_batch_singles_word;
+        return launch_decode_batch_singles_t<FMT_WORD>(p, num_cus, stream);
+    case FMT_R64:
+        if (name)
+            *name = KernelId::decode_batch_singles_r64;
+        return launch_decode_batch_singles_t<FMT_R64>(p, num_cus, stream);
+    default:
+        if (name)
+            *name = KernelId::decode_batch_singles_alias;
+        return launch_decode_batch_singles_t<FMT_ALIAS>(p, num_cus, stream);
+    }
 }
 
 #undef R64_LOOKUP

@@ -29,7 +29,8 @@ hipError_t launch_decode(int format, const DecParams &p, int num_cus, hipStream_
 }
 
 // ragged batches: the first streams-per-wave family that takes the batch (kBatchFamilies, launchers.hpp: word groups, byte
-// pairs, rans64 lanes and alias pairs, each with a decoder's row and an encoder's), else the wave-per-stream kernels, whatever the interleave
+// pairs, rans64 lanes and alias pairs, each with a decoder's row and an encoder's, and the 1-way singles of the four formats with a
+// decoder's row each), else the wave-per-stream kernels, whatever the interleave
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
 {
     if (const BatchFamily *f = decode_batch_family(p.variant, format, p))

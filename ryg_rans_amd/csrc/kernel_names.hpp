@@ -22,7 +22,11 @@
 //   batch_alias_pairs_encode  ... encoder (RANS_AMD_OPT_BATCH_ENCODE_ALIAS_PAIRS)
 // Its ids follow the second list's, its rows are kAliasPairEncodeKernelEntries; tests/kernel_names_alias_pairs_encode_driver.cpp
 // with tests/_batch_encode_alias_pairs.py hold it to its rows.
-// kernel_entry(), kernel_name() and kernel_family() resolve ids from all three.  (Folding the three into one list is a later refactor:
+// A fourth list follows the third: RANS_AMD_KERNEL_NAMES_SINGLES, the family
+//   batch_singles_decode      ragged 1-way streams of all four formats, 64 per wave, decoder (RANS_AMD_OPT_BATCH_SINGLES)
+// Its ids follow the third list's (56..59), its rows are kSinglesKernelEntries; tests/kernel_names_singles_driver.cpp with
+// tests/_batch_singles.py hold it to its rows.
+// kernel_entry(), kernel_name() and kernel_family() resolve ids from all four.  (Folding the lists into one is a later refactor:
 // the row module has to know the families first, and the printed lines and counts of the first two lists are pinned by tests.)
 // Nine families in the first list: a new kernel is one more row at the list's end (an id is its row's place, counted from 1, and the
 // ids that exist stay where they are); tests/kernel_names_driver.cpp prints every row and tests/_kernel_rows.py reads them.
@@ -91,6 +95,12 @@ namespace rans_amd {
 #define RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS_ENCODE(X)                                               \
     X(encode_batch_alias_pairs, "k_encode_batch_alias_pairs", batch_alias_pairs_encode)
 
+#define RANS_AMD_KERNEL_NAMES_SINGLES(X)                                                          \
+    X(decode_batch_singles_byte, "k_decode_batch_singles<byte>", batch_singles_decode)            \
+    X(decode_batch_singles_word, "k_decode_batch_singles<word>", batch_singles_decode)            \
+    X(decode_batch_singles_r64, "k_decode_batch_singles<r64>", batch_singles_decode)              \
+    X(decode_batch_singles_alias, "k_decode_batch_singles<alias>", batch_singles_decode)
+
 enum class KernelFamily {
     uniform,
     batch,
@@ -103,6 +113,7 @@ enum class KernelFamily {
     batch_r64_lanes_encode,
     batch_alias_pairs_decode,
     batch_alias_pairs_encode,
+    batch_singles_decode,
 };
 
 enum class KernelId {
@@ -111,6 +122,7 @@ enum class KernelId {
     RANS_AMD_KERNEL_NAMES(X)
     RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS(X) // (behind the first list: an id of this one is kKernelEntryCount + 1 + its row)
     RANS_AMD_KERNEL_NAMES_ALIAS_PAIRS_ENCODE(X) // (behind the second: kKernelEntryCount + kAliasPairKernelEntryCount + 1 + its row)
+    RANS_AMD_KERNEL_NAMES_SINGLES(X) // (behind the third: ... + kAliasPairEncodeKernelEntryCount + 1 + its row)
 #undef X
 };
 
@@ -145,18 +157,31 @@ constexpr KernelEntry kAliasPairEncodeKernelEntries[] = {
 };
 constexpr int kAliasPairEncodeKernelEntryCount = (int)(sizeof(kAliasPairEncodeKernelEntries) / sizeof(kAliasPairEncodeKernelEntries[0]));
 
+// the fourth list's entries, in its order
+constexpr KernelEntry kSinglesKernelEntries[] = {
+#define X(id, name, family) {KernelId::id, name, KernelFamily::family, #family},
+    RANS_AMD_KERNEL_NAMES_SINGLES(X)
+#undef X
+};
+constexpr int kSinglesKernelEntryCount = (int)(sizeof(kSinglesKernelEntries) / sizeof(kSinglesKernelEntries[0]));
+
 constexpr const KernelEntry &kernel_entry(KernelId id) // (not for KernelId::none)
 {
-    return (int)id <= kKernelEntryCount                                ? kKernelEntries[(int)id - 1]
-           : (int)id <= kKernelEntryCount + kAliasPairKernelEntryCount ? kAliasPairKernelEntries[(int)id - 1 - kKernelEntryCount]
-                                                                       : kAliasPairEncodeKernelEntries[(int)id - 1 - kKernelEntryCount - kAliasPairKernelEntryCount];
+    constexpr int second = kKernelEntryCount, third = second + kAliasPairKernelEntryCount, fourth = third + kAliasPairEncodeKernelEntryCount;
+    return (int)id <= second   ? kKernelEntries[(int)id - 1]
+           : (int)id <= third  ? kAliasPairKernelEntries[(int)id - 1 - second]
+           : (int)id <= fourth ? kAliasPairEncodeKernelEntries[(int)id - 1 - third]
+                               : kSinglesKernelEntries[(int)id - 1 - fourth];
 }
 constexpr const char *kernel_name(KernelId id) { return id == KernelId::none ? "" : kernel_entry(id).name; }
 constexpr KernelFamily kernel_family(KernelId id) { return kernel_entry(id).family; } // (not for KernelId::none)
 static_assert(kernel_entry(KernelId::encode_batch_r64_lanes).id == KernelId::encode_batch_r64_lanes &&
                   kernel_entry(KernelId::decode_batch_alias_pairs).id == KernelId::decode_batch_alias_pairs &&
                   kernel_entry(KernelId::encode_batch_alias_pairs).id == KernelId::encode_batch_alias_pairs &&
-                  (int)KernelId::encode_batch_alias_pairs == 55,
-              "ids of all three lists resolve to their own rows");
+                  (int)KernelId::encode_batch_alias_pairs == 55 &&
+                  kernel_entry(KernelId::decode_batch_singles_byte).id == KernelId::decode_batch_singles_byte &&
+                  kernel_entry(KernelId::decode_batch_singles_alias).id == KernelId::decode_batch_singles_alias &&
+                  (int)KernelId::decode_batch_singles_byte == 56 && (int)KernelId::decode_batch_singles_alias == 59,
+              "ids of all four lists resolve to their own rows");
 
 } // namespace rans_amd

@@ -38,6 +38,7 @@ constexpr uint32_t kVarBatchLanes = 512u;    // ragged batches of the 2-way rans
 constexpr uint32_t kVarBatchEncLanes = 1024u; // ... in the ENCODER as well (k_encode_batch_r64_lanes)
 constexpr uint32_t kVarBatchAliasPairs = 2048u; // ragged batches of the 2-way alias layout: 32 streams per wave (k_decode_batch_alias_pairs)
 constexpr uint32_t kVarBatchEncAliasPairs = 4096u; // ... in the ENCODER as well (k_encode_batch_alias_pairs)
+constexpr uint32_t kVarBatchSingles = 8192u; // ragged batches of the 1-way layout of all four formats: 64 streams per wave (k_decode_batch_singles)
 
 constexpr uint32_t kWorkPools = 8;       // chunk hand-out counters per launch (one per XCD)
 constexpr uint32_t kWorkPoolStride = 16; // in uint32: every counter on its own 64-byte line
@@ -258,7 +259,8 @@ hipError_t launch_compact(const CompactParams &p, int num_cus, hipStream_t strea
 // kVarBatchEncGroups, and for the 2-way byte layout 32 streams per wave, in the decoder under kVarBatchPairs and in the
 // encoder under kVarBatchEncPairs, and for the 2-way rans64 layout 64 streams per wave, in the decoder under kVarBatchLanes and
 // in the encoder under kVarBatchEncLanes, and for the 2-way alias layout 32 streams per wave, in the decoder under
-// kVarBatchAliasPairs and in the encoder under kVarBatchEncAliasPairs.
+// kVarBatchAliasPairs and in the encoder under kVarBatchEncAliasPairs, and for the non-interleaved (1-way) layout of the byte,
+// word, rans64 and alias formats 64 streams per wave in the decoder under kVarBatchSingles.
 // `format` is the kernel-side format number.
 hipError_t launch_decode_batch(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
 hipError_t launch_encode_batch(int format, const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);

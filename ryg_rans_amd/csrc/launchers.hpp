@@ -132,6 +132,18 @@ hipError_t launch_decode_batch_r64_lanes(const DecParams &p, int num_cus, hipStr
 // launcher sizes the block: 8 KiB of records and 8 KiB of ring per wave)
 bool encode_batch_r64_lanes_applicable(const EncParams &p);
 hipError_t launch_encode_batch_r64_lanes(const EncParams &p, int num_cus, hipStream_t stream, KernelId *name);
+// the ragged form of the staged 1-way lane decoder (rans_amd_decode_batch, kBatchFamilies; decode_lanes.hip): 64 STREAMS per wave,
+// one per lane with ONE state each, for the non-interleaved layout of the byte, word, rans64 (cum2sym) and alias formats over u8
+// symbols, from 64 streams on; scale_bits 8..16 (byte, alias: a power-of-two alphabet of at most 256 symbols), 12 (word), 7..16
+// (rans64); the tables and at least one wave's rings inside the CU's 160 KiB of LDS (the launcher sizes the block from what the
+// tables leave).  `format` is the kernel-side one; a row of kBatchFamilies names an instantiation of the templates.
+bool decode_batch_singles_applicable(int format, const DecParams &p);
+hipError_t launch_decode_batch_singles(int format, const DecParams &p, int num_cus, hipStream_t stream, KernelId *name);
+template <int FORMAT> bool decode_batch_singles_applicable(const DecParams &p) { return decode_batch_singles_applicable(FORMAT, p); }
+template <int FORMAT> hipError_t launch_decode_batch_singles(const DecParams &p, int num_cus, hipStream_t stream, KernelId *name)
+{
+    return launch_decode_batch_singles(FORMAT, p, num_cus, stream, name);
+}
 // true when launch_encode_lanes would take the staged kernel for this request -- the one that can place its chunks
 // itself (EncParams::status); everything but status / offsets / out / out_cap must be filled in
 bool encode_lanes_fused(const EncParams &p, int num_cus);
@@ -143,8 +155,9 @@ bool encode_lanes_sized_ok(int format, const EncParams &p, int num_cus);
 // wave-per-stream kernels, under the options as well.  A decoder's row leaves the encoder's pair null and the other way round.
 // The format is the KERNEL-side one that the launchers are handed: an alias model with the encoder's LDS tables encodes under
 // kKernelFormatAliasLds, not RANS_AMD_FMT_ALIAS.
-// `streams` completes the option's E_ARG text.  (The ragged forms of the other lane kernels -- the 1-, 4- and 8-way interleaves -- are later
-// work: one more row each.)
+// `streams` completes the option's E_ARG text.  The rows of the 1-way layout, one per format under one option and one bit, stand
+// behind the other decoders' rows: a batch that had a family keeps it.  (The 1-way ENCODER, the 2-way scalar word layout and the
+// ragged forms of the 4- and 8-way lane kernels are later work: one more row each.)
 struct BatchFamily {
     int option; // RANS_AMD_OPT_*
     const char *option_name;
@@ -158,11 +171,18 @@ struct BatchFamily {
 };
 #define RANS_BATCH_DECODER(opt, bit, fmt, kern, streams) {opt, #opt, bit, fmt, kern##_applicable, launch_##kern, nullptr, nullptr, streams}
 #define RANS_BATCH_ENCODER(opt, bit, fmt, kern, streams) {opt, #opt, bit, fmt, nullptr, nullptr, kern##_applicable, launch_##kern, streams}
+#define RANS_BATCH_SINGLES(fmt)                                                                                                                \
+    {RANS_AMD_OPT_BATCH_SINGLES, "RANS_AMD_OPT_BATCH_SINGLES", kVarBatchSingles, fmt, decode_batch_singles_applicable<fmt>, launch_decode_batch_singles<fmt>, \
+     nullptr, nullptr, "sixty-four 1-way streams per wave"}
 constexpr BatchFamily kBatchFamilies[] = {
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_GROUPS, kVarBatchGroups, RANS_AMD_FMT_WORD, decode_batch_word_groups, "eight 8-way word streams per wave"),
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_PAIRS, kVarBatchPairs, RANS_AMD_FMT_BYTE, decode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_LANES, kVarBatchLanes, RANS_AMD_FMT_R64, decode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
     RANS_BATCH_DECODER(RANS_AMD_OPT_BATCH_ALIAS_PAIRS, kVarBatchAliasPairs, RANS_AMD_FMT_ALIAS, decode_batch_alias_pairs, "thirty-two 2-way alias streams per wave"),
+    RANS_BATCH_SINGLES(RANS_AMD_FMT_BYTE),
+    RANS_BATCH_SINGLES(RANS_AMD_FMT_WORD),
+    RANS_BATCH_SINGLES(RANS_AMD_FMT_R64),
+    RANS_BATCH_SINGLES(RANS_AMD_FMT_ALIAS),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_GROUPS, kVarBatchEncGroups, RANS_AMD_FMT_WORD, encode_batch_word_groups, "eight 8-way word streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_PAIRS, kVarBatchEncPairs, RANS_AMD_FMT_BYTE, encode_batch_byte_pairs, "thirty-two 2-way byte streams per wave"),
     RANS_BATCH_ENCODER(RANS_AMD_OPT_BATCH_ENCODE_LANES, kVarBatchEncLanes, RANS_AMD_FMT_R64, encode_batch_r64_lanes, "sixty-four 2-way rans64 streams per wave"),
@@ -170,6 +190,7 @@ constexpr BatchFamily kBatchFamilies[] = {
 };
 #undef RANS_BATCH_DECODER
 #undef RANS_BATCH_ENCODER
+#undef RANS_BATCH_SINGLES
 
 // the first family whose option is on and that takes this batch, or null: the wave-per-stream kernels
 inline const BatchFamily *decode_batch_family(uint32_t variant, int format, const DecParams &p)
